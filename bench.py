@@ -12,8 +12,10 @@ bin/selfplay.py:177-199 spawns one worker per core), relays rank 0's single JSON
 fails.  Under torch.distributed.run (WORLD_SIZE already set) the process is a rank; it derives the same plan and pins itself
 to its slice (BK_BENCH_NO_PIN=1: off).  `--plan` prints the launch plan and exits without touching a GPU.  BK_BENCH_BACKEND=gloo BK_BENCH_DEVICE=0 rehearses the N-rank path on one card.
 
-The headline (`value`, `dtype`, `roofline`) is the EXACT-fp32 kernel -- the reference's arithmetic width
-(torch fp32, bokego/nnet.py:31-57,73-113) -- timed over exactly --steps launches between barriers.  Beside it:
+The headline (`value`, `dtype`, `ms_per_step`) is the EXACT-fp32 kernel -- the reference's arithmetic width
+(torch fp32, bokego/nnet.py:31-57,73-113) -- timed over exactly --steps launches between barriers after --warmup ones.  A plain
+run does only that: set up, warm up, time, write the last timed step's outputs (--dump-outputs DIR), print the line.  With
+--full the line also carries (the fields a plain run leaves null):
   sustained     the same launches looped for >= 2 s (DVFS / power settle), reported next to the --steps figure
   parity        measured IN THIS RUN on the timed engine through the timed entry point: max |dlogit| / |dprob| /
                 |dvalue| against the reference's recorded outputs for the 536 golden positions (the cpu_baseline leg
@@ -370,7 +372,7 @@ def launch(args, argv):
     device = int(os.environ["BK_BENCH_DEVICE"]) if "BK_BENCH_DEVICE" in os.environ else None
     plan = launch_plan(args.gpus, device=device)
     plan.update(master_addr="127.0.0.1", master_port=free_port(), backend=backend, job=os.urandom(8).hex(),
-                argv=[a for a in argv if a != "--plan"])
+                argv=[a for a in argv if a != "--plan"] + (["--dump-outputs", args.dump_outputs] if args.dump_outputs else []))
     if args.plan:
         print(json.dumps(plan), flush=True)
         return 0
@@ -516,9 +518,9 @@ def parity_in_run(eng, torch):
             "tolerance": TOL, "against": "reference outputs recorded in tests/golden/nets.npz"}
 
 
-def measure(eng, x, steps, warmup, barrier, reduce_max, sustain_s, torch):
+def measure(eng, x, steps, warmup, barrier, reduce_max, sustain_s, torch, spread=True):
     """Times exactly `steps` launches between barriers (the contract's figure), then the same launch looped for
-    >= sustain_s seconds, then a per-launch spread.  Kernel durations come from HIP events on the launch stream."""
+    >= sustain_s seconds, then (spread) a per-launch spread.  Kernel durations come from HIP events on the launch stream."""
     B = x.shape[0]
     run = lambda: eng.eval_device(x, logits=True, probs=True, value=True)  # noqa: E731
     for _ in range(warmup):
@@ -552,13 +554,32 @@ def measure(eng, x, steps, warmup, barrier, reduce_max, sustain_s, torch):
         sust = {"seconds": t_s, "launches": n, "leaf_evals_per_s": n * B / t_s,
                 "kernel_ms": (s1["kernel_ms_sum"] - s0["kernel_ms_sum"]) / max(1, s1["kernel_ms_count"] - s0["kernel_ms_count"])}
     each = []
-    for _ in range(30):
+    for _ in range(30 if spread else 0):
         run()
         torch.cuda.synchronize()
         each.append(eng.stats()["last_kernel_ms"])
     eng.set_profiling(False)
     return {"dt": dt, "dt_local": dt_local, "kernel_ms": kern_ms, "sustained": sust, "out": out,
-            "p10_p50_p90": [float(np.percentile(each, q)) for q in (10, 50, 90)]}
+            "p10_p50_p90": [float(np.percentile(each, q)) for q in (10, 50, 90)] if spread else None}
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, out, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: the arrays one timed call returned (logits, probs, value), as path/<name>.npy in float32, so that two
+    builds can be compared output for output on the same seeded workload.  Above `limit` bytes in all, every array keeps the
+    same rows: a sample drawn with a fixed seed, in order."""
+    arrays = {k: v.cpu().numpy().astype(np.float32) for k, v in out.items() if not k.startswith("_")}
+    rows = min(len(a) for a in arrays.values())
+    keep = max(1, limit // sum(a[0].nbytes for a in arrays.values()))
+    if rows > keep:
+        sel = np.sort(np.random.default_rng(0).choice(rows, keep, replace=False))
+        arrays = {k: a[sel] for k, a in arrays.items()}
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, f"{k}.npy"), a)
+    return sorted(arrays)
 
 
 PMC_PASSES = (("FETCH_SIZE",), ("WRITE_SIZE",), ("GRBM_GUI_ACTIVE",),
@@ -763,7 +784,14 @@ def main():
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--pmc-device", type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument("--plan", action="store_true", help="print the N-rank launch plan (devices, CPU slices, port) and exit; no GPU call")
+    ap.add_argument("--full", action="store_true", help="also every secondary measurement and check: sustained loop, parity, f16x2, "
+                    "roofline and counter passes, host-buffer rates, small-batch latency, self-play, CPU baselines (off: the headline alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step returned (rank 0) to DIR/<name>.npy, float32")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs:
+        args.dump_outputs = os.path.abspath(args.dump_outputs)     # the launcher's ranks run in the repository
 
     if args.plan or (args.gpus > 1 and "WORLD_SIZE" not in os.environ):
         sys.exit(launch(args, sys.argv[1:]))
@@ -841,19 +869,19 @@ def main():
         dist.all_gather(outl, t)
         return [float(o.item()) for o in outl]
 
-    # ---- headline: exactly --steps launches of the reference-width kernel, then the sustained loop -------------
+    # ---- headline: exactly --steps launches of the reference-width kernel (--full: then the sustained loop) -----
     progress(f"engine up, workload made; timing {args.steps} steps")
-    head = measure(eng, x, args.steps, args.warmup, barrier, reduce_max, args.sustain, torch)
-    head_parity = parity_in_run(eng, torch)
+    head = measure(eng, x, args.steps, args.warmup, barrier, reduce_max, args.sustain if args.full else 0, torch, spread=args.full)
+    if args.dump_outputs and rank == 0:
+        progress(f"outputs of the last timed step -> {args.dump_outputs}: {', '.join(dump_outputs(args.dump_outputs, head['out']))}")
+    head_parity = parity_in_run(eng, torch) if args.full else None
     per_rank = gather(args.batch * args.steps / head["dt_local"])
     assert eng.stats()["f16_device_overflow"] == 0
-
-    head_logits, head_values = head["out"]["logits"].cpu().numpy(), head["out"]["value"].cpu().numpy()   # for the CPU leg's cross-check
 
     # ---- nested: the opt-in f16x2 variant, same engine, same measurements --------------------------------------------
     other = None
     other_name = "f16x2" if args.precision == "f32" else "f32"
-    if not args.no_f16x2:
+    if args.full and not args.no_f16x2:
         progress("headline timed; nested f16x2 block")
         eng.set_precision(other_name)
         m = measure(eng, x, args.steps, args.warmup, barrier, reduce_max, args.sustain, torch)
@@ -870,7 +898,7 @@ def main():
     # (b) what the ABI is built for: uint8 planes, three tickets in flight (the engine runs H2D, kernels
     #     and D2H on three streams chained by events); (c) 192-byte position records, planes encoded on the GPU.
     e2e = e2e_u8 = e2e_pos = None
-    if rank == 0:
+    if args.full and rank == 0:
         eng.eval(x_host, logits=False, probs=True, value=True)
         t1 = time.perf_counter()
         for _ in range(3):
@@ -897,7 +925,7 @@ def main():
     # 40..70 value rows, latency-bound.  Kernel time of such a batch with one CU per board against the cooperative
     # launch (4 CUs per board here; 12 for the single position of configs[0]).
     small = None
-    if rank == 0 and args.precision == "f32":
+    if args.full and rank == 0 and args.precision == "f32":
         def kernel_us(B, reps=20):
             xs = x_u8[:B]
             for _ in range(3):
@@ -944,7 +972,7 @@ def main():
     # Secondary measurement (outside the timed region above): BASELINE configs[3] -- 512 self-play games,
     # 400 rollouts/move, sharded over the ranks (gid % world), one all-reduce of the statistics at the end.
     sp = None
-    if not args.no_selfplay:
+    if args.full and not args.no_selfplay:
         from bokego_amd import selfplay
         # host cores are shared by the ranks: a launch() child got its slice and thread count from the plan, a
         # torch.distributed.run rank sees every CPU and takes 1/world of them (of the cgroup quota when there is one)
@@ -1082,15 +1110,15 @@ def main():
         return
     dist = None
 
-    progress("collectives over; rank 0 alone: counter passes")
     live = None
-    if not args.no_live_pmc:
+    if args.full and not args.no_live_pmc:
+        progress("collectives over; rank 0 alone: counter passes")
         live = live_counters(args.batch, args.precision, device=local_rank)
 
     cpu = None
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         progress("CPU baselines")
-        cpu = cpu_baseline(pw, vw, x_host, head_logits, head_values)
+        cpu = cpu_baseline(pw, vw, x_host, head["out"]["logits"].cpu().numpy(), head["out"]["value"].cpu().numpy())   # + the cross-check
         if sp is not None:
             sp["cpu_baseline"] = selfplay_cpu_baseline(cpu["cores"])
 
@@ -1109,7 +1137,7 @@ def main():
                        "parity_workload_sample": cpu["timed_output_vs_oracle_sample"] if cpu else None,
                        "sharding": f"positions x{world}, no data-path collective"},
             "sustained": head["sustained"],
-            "roofline": roofline(args.precision, args.batch, head["kernel_ms"], head["sustained"], head["p10_p50_p90"], live),
+            "roofline": roofline(args.precision, args.batch, head["kernel_ms"], head["sustained"], head["p10_p50_p90"], live) if args.full else None,
             other_name: other,
             "cpu_baseline": cpu,
             "selfplay": sp,

@@ -39,6 +39,32 @@ def _run_bench(args, env=None, timeout=180):
                           cwd=REPO, env=e)
 
 
+def test_dump_outputs_writes_float32_and_samples_the_same_rows_above_the_limit(tmp_path):
+    """--dump-outputs: one .npy per returned array (not the keep-alive), float32; over the size limit every array keeps the same
+    seeded rows, in order, from run to run."""
+    import torch
+    B = 1000
+    out = {"logits": torch.arange(B * 81, dtype=torch.float32).reshape(B, 81), "probs": torch.rand(B, 81),
+           "value": torch.arange(B, dtype=torch.float64), "_keepalive": torch.zeros(3)}
+    assert bench.dump_outputs(str(tmp_path / "all"), out) == ["logits", "probs", "value"]
+    assert sorted(os.listdir(tmp_path / "all")) == ["logits.npy", "probs.npy", "value.npy"]
+    v = np.load(tmp_path / "all" / "value.npy")
+    assert v.dtype == np.float32 and np.array_equal(v, np.arange(B))
+    row = (81 + 81 + 1) * 4
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), out, limit=100 * row)
+    got = {k: np.load(tmp_path / "a" / f"{k}.npy") for k in ("logits", "probs", "value")}
+    rows = got["value"].astype(int)
+    assert len(rows) == 100 and np.all(np.diff(rows) > 0) and sum(a.nbytes for a in got.values()) <= 100 * row
+    assert np.array_equal(got["logits"], out["logits"].numpy()[rows]) and np.array_equal(got["probs"], out["probs"].numpy()[rows])
+    assert all(np.array_equal(got[k], np.load(tmp_path / "b" / f"{k}.npy")) for k in got)
+
+
+def test_steps_must_be_positive():
+    out = _run_bench(["--steps", "0"], timeout=60)
+    assert out.returncode == 2 and "--steps must be >= 1" in out.stderr
+
+
 def test_cpulist_round_trip():
     assert bench.parse_cpulist("0-3,8,10-11\n") == [0, 1, 2, 3, 8, 10, 11]
     assert bench.format_cpulist([11, 0, 1, 2, 3, 8, 10]) == "0-3,8,10-11"
@@ -119,6 +145,8 @@ def test_plan_flag_prints_the_plan_and_starts_nothing():
     plan = json.loads(out.stdout)
     assert plan["world"] == 4 and len(plan["ranks"]) == 4 and plan["master_addr"] == "127.0.0.1" and plan["master_port"] > 0
     assert plan["argv"] == ["--gpus", "4", "--steps", "3"] and plan["backend"] == "nccl"
+    rel = json.loads(_run_bench(["--gpus", "2", "--plan", "--dump-outputs", "outs"]).stdout)      # the ranks run in the repository
+    assert rel["argv"][-2:] == ["--dump-outputs", os.path.join(REPO, "outs")]
     every = [c for r in plan["ranks"] for c in bench.parse_cpulist(r["cpus"])]
     assert len(every) == len(set(every)) and set(every) <= set(os.sched_getaffinity(0))      # nothing shared, nothing foreign
     if not plan["gpu_numa_nodes"]:           # no GPU topology in sysfs (the build container): everything allowed is dealt out;

@@ -1,5 +1,6 @@
-"""-m gpu: bench.py's one-line contract on a short run (the driver's invocation with fewer steps and without the CPU and
-self-play legs): the keys the driver reads, the headline's arithmetic, roofline consistency, parity measured in the run."""
+"""-m gpu: bench.py's one-line contract on a short run -- the plain run (the headline alone, and the outputs it dumps), and
+--full with fewer steps and without the CPU leg: the keys the driver reads, the headline's arithmetic, roofline consistency,
+parity measured in the run."""
 import json
 import os
 import subprocess
@@ -13,8 +14,8 @@ pytestmark = pytest.mark.gpu
 
 
 def test_bench_line_contract():
-    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1", "--sustain", "0.3",
-                          "--no-cpu-baseline", "--selfplay-games", "64"], capture_output=True, text=True, timeout=600, cwd=REPO)
+    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1", "--full", "--sustain",
+                          "0.3", "--no-cpu-baseline", "--selfplay-games", "64"], capture_output=True, text=True, timeout=600, cwd=REPO)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, "bench.py prints exactly one line"
@@ -71,6 +72,39 @@ def test_bench_line_contract():
     assert d["selfplay"]["games_per_min"] == d["selfplay"]["f32"]["games_per_min"]
 
 
+def test_plain_bench_run_is_the_headline_and_dumps_its_outputs(tmp_path):
+    """`bench.py --gpus 1 --steps N --warmup W` without --full: the headline alone (every secondary field null), and
+    --dump-outputs writes what the last timed step returned -- the oracle's outputs for the seeded workload."""
+    import numpy as np
+    from bokego_amd.bkw import load_bkw
+    from oracle.oracle import OraclePolicy, OracleValue
+    from conftest import GOLDEN
+    import bench
+    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2", "--dump-outputs",
+                          str(tmp_path / "dump")], capture_output=True, text=True, timeout=300, cwd=REPO)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, "bench.py prints exactly one line"
+    d = json.loads(lines[0])
+    assert d["metric"] == "leaf-evals/sec (policy+value, batched 9x9 positions)" and d["unit"] == "leaf-evals/s"
+    assert d["higher_is_better"] is True and d["dtype"] == "f32" and d["steps"] == 7 and d["warmup"] == 2
+    B = d["config"]["batch_per_gpu"]
+    assert B == 4096 and abs(d["value"] - B * 1e3 / d["ms_per_step"]) < 1e-6 * d["value"]
+    for k in ("sustained", "roofline", "f16x2", "cpu_baseline", "selfplay", "small_batch_latency", "host_buffer_e2e_leaf_evals_per_s"):
+        assert d[k] is None, k
+    assert d["config"]["parity"] is None
+    got = {k: np.load(tmp_path / "dump" / f"{k}.npy") for k in ("logits", "probs", "value")}
+    assert sorted(os.listdir(tmp_path / "dump")) == ["logits.npy", "probs.npy", "value.npy"]
+    assert got["logits"].shape == got["probs"].shape == (B, 81) and got["value"].shape == (B,)
+    assert all(a.dtype == np.float32 for a in got.values())
+    x = bench.make_workload(B, 0)[0]
+    sel = np.linspace(0, B - 1, 24).astype(int)
+    lg, pr = OraclePolicy(load_bkw(os.path.join(GOLDEN, "policy_19.bkw")))(x[sel], want_probs=True)
+    va = OracleValue(load_bkw(os.path.join(GOLDEN, "value_synth.bkw")))(x[sel])
+    assert np.abs(got["logits"][sel] - lg).max() < 2e-4 and np.abs(got["probs"][sel] - pr).max() < 1e-5
+    assert np.abs(got["value"][sel] - va).max() < 1e-4
+
+
 def test_bench_starts_its_own_ranks():
     """`python3 bench.py --gpus 2` with no torch.distributed.run around it: the parent starts two
     fresh ranks and relays one line.  On a one-GPU box the two ranks share the card and meet over gloo (RCCL refuses two
@@ -82,8 +116,8 @@ def test_bench_starts_its_own_ranks():
     real = torch.cuda.device_count() >= 2
     if not real:
         env.update(BK_BENCH_BACKEND="gloo", BK_BENCH_DEVICE="0")
-    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--sustain", "0",
-                          "--no-f16x2", "--selfplay-games", "32"], capture_output=True, text=True, timeout=900, cwd=REPO, env=env)
+    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full", "--sustain",
+                          "0", "--no-f16x2", "--selfplay-games", "32"], capture_output=True, text=True, timeout=900, cwd=REPO, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, out.stdout[-2000:]

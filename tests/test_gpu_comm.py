@@ -33,8 +33,8 @@ def test_bench_line_over_rccl_at_one_rank():
     import sys
     from conftest import REPO
     env = dict(os.environ, BK_BENCH_FORCE_DIST="1", RANK="0", WORLD_SIZE="1", LOCAL_RANK="0", MASTER_ADDR="127.0.0.1", MASTER_PORT="29541")
-    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "3", "--warmup", "1", "--sustain", "0", "--no-cpu-baseline",
-                          "--no-live-pmc", "--selfplay-games", "32", "--no-f16x2"], capture_output=True, text=True, timeout=600, cwd=REPO, env=env)
+    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "3", "--warmup", "1", "--full", "--sustain", "0",
+                          "--no-cpu-baseline", "--no-live-pmc", "--selfplay-games", "32", "--no-f16x2"], capture_output=True, text=True, timeout=600, cwd=REPO, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
     d = json.loads([ln for ln in out.stdout.splitlines() if ln.strip()][-1])
     assert d["collective_backend"] == "nccl" and d["collective_ranks_seen"] == 1

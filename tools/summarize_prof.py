@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Condense a tools/profile_bench.sh output directory into profiles/<tag>_*.{csv,md,json} (tracked).
 
-    profiles/<tag>_kernel_stats.csv      rocprofv3 --kernel-trace --stats of the default bench (both kernels)
+    profiles/<tag>_kernel_stats.csv      rocprofv3 --kernel-trace --stats of bench.py --full (both kernels)
     profiles/<tag>_bench.json            the un-profiled bench line of the same box
     profiles/<tag>_pmc_<precision>.json  PMC means per dispatch of that precision's kernel (+ HBM traffic)
     profiles/<tag>_summary.md            the table the DESIGN / VERDICT numbers are read from
@@ -61,7 +61,7 @@ def bench_block(prec):
 
 
 with open(os.path.join(dst, f"{tag}_summary.md"), "w") as o:
-    o.write(f"# rocprofv3 summary {tag} (MI355X, `python3 bench.py`, batch {B})\n\n")
+    o.write(f"# rocprofv3 summary {tag} (MI355X, `python3 bench.py --full`, batch {B})\n\n")
     o.write("## --kernel-trace --stats (one run: fp32 headline + nested f16x2 block)\n\n| kernel | calls | avg ms | min ms | max ms | % |\n|---|---|---|---|---|---|\n")
     for r in rows[:6]:
         o.write(f"| `{r['Name'][:80]}` | {r['Calls']} | {float(r['AverageNs'])/1e6:.4f} | {float(r['MinNs'])/1e6:.4f} | "
