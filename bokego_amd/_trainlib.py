@@ -1,0 +1,192 @@
+"""ctypes binding of libbktrain.so (C ABI: include/bokego_train.h), the training kernels of the trunk.
+
+Every call takes torch tensors on the GPU, checks their shapes, and enqueues on torch's current stream.  The library
+allocates nothing: outputs and scratch are torch tensors allocated here.  There is no CPU fallback.
+"""
+import ctypes
+import os
+
+import torch
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+LIB_PATH = os.path.join(_HERE, "libbktrain.so")
+
+BKT_ABI_VERSION = 1
+COUT = 128
+BN_EPS = 1e-5
+BN_MOMENTUM = 0.1
+STATUS_NAMES = {0: "BKT_OK", -1: "BKT_ERR_ARG", -2: "BKT_ERR_HIP"}
+
+_P = ctypes.c_void_p
+_I, _F, _Z = ctypes.c_int, ctypes.c_float, ctypes.c_size_t
+SYMBOLS = {
+    "bkt_abi_version": (_I, []),
+    "bkt_conv_pack": (_I, [_P, _I, _I, _P, _P]),
+    "bkt_conv_forward": (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),
+    "bkt_conv_pack_dgrad": (_I, [_P, _P, _P]),
+    "bkt_conv_dgrad": (_I, [_P, _P, _P, _I, _P]),
+    "bkt_conv_wgrad_workspace": (_Z, [_I, _I, _I]),
+    "bkt_conv_wgrad": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _Z, _P]),
+    "bkt_bn_workspace": (_Z, [_I, _I]),
+    "bkt_bn_relu_train": (_I, [_P, _P, _P, _P, _P, _P, _F, _F, _P, _P, _P, _P, _Z, _I, _I, _P]),
+    "bkt_bn_relu_backward": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _I, _I, _P]),
+    "bkt_bn_relu_eval": (_I, [_P, _P, _P, _P, _P, _F, _P, _I, _I, _P]),
+}
+
+_lib = None
+
+
+def load(path=None):
+    global _lib
+    if _lib is not None and path is None:
+        return _lib
+    p = path or LIB_PATH
+    if not os.path.exists(p):
+        raise OSError(f"{p} not found: build it with `make -C bokego_amd/csrc all`")
+    lib = ctypes.CDLL(p)
+    for name, (res, args) in SYMBOLS.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = res, args
+    if lib.bkt_abi_version() != BKT_ABI_VERSION:
+        raise OSError(f"{p}: ABI version {lib.bkt_abi_version()}, expected {BKT_ABI_VERSION}")
+    if path is None:
+        _lib = lib
+    return lib
+
+
+def _check(rc, what):
+    if rc != 0:
+        raise RuntimeError(f"{what} failed: {STATUS_NAMES.get(rc, rc)}")
+
+
+def _dev(t, name, shape=None, dtype=torch.float32):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise ValueError(f"{name} must be a tensor on the GPU")
+    if t.dtype != dtype:
+        raise ValueError(f"{name} must be {dtype}, got {t.dtype}")
+    if not t.is_contiguous():
+        raise ValueError(f"{name} must be contiguous")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name} must have shape {tuple(shape)}, got {tuple(t.shape)}")
+    return t.data_ptr()
+
+
+def _stream(t):
+    return ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
+
+
+def _conv_shape(w):
+    if w.dim() != 4 or w.shape[0] != COUT or w.shape[2] != w.shape[3] or w.shape[2] not in (3, 5):
+        raise ValueError(f"conv weight must be [128, Cin, k, k] with k 3 or 5, got {tuple(w.shape)}")
+    return int(w.shape[1]), int(w.shape[2])
+
+
+def _batch(x, c):
+    if x.dim() != 4 or tuple(x.shape[1:]) != (c, 9, 9):
+        raise ValueError(f"expected [B, {c}, 9, 9], got {tuple(x.shape)}")
+    return int(x.shape[0])
+
+
+def conv_pack(w):
+    """[128, Cin, k, k] -> [Cin*k*k, 128], the forward operand."""
+    cin, k = _conv_shape(w)
+    wt = torch.empty((cin * k * k, COUT), dtype=torch.float32, device=w.device)
+    _check(load().bkt_conv_pack(_dev(w, "w"), cin, k, _dev(wt, "wt"), _stream(w)), "bkt_conv_pack")
+    return wt
+
+
+def conv_forward(x, w, bias=None, wt=None):
+    """conv2d(x, w, bias, padding=k//2) on the 9x9 board; wt: conv_pack(w) when the caller already has it."""
+    cin, k = _conv_shape(w)
+    B = _batch(x, cin)
+    wt = conv_pack(w) if wt is None else wt
+    y = torch.empty((B, COUT, 9, 9), dtype=torch.float32, device=x.device)
+    bp = None if bias is None else _dev(bias, "bias", (COUT,))
+    _check(load().bkt_conv_forward(_dev(x, "x"), _dev(wt, "wt", (cin * k * k, COUT)), bp, _dev(y, "y"), B, cin, k,
+                                   _stream(x)), "bkt_conv_forward")
+    return y
+
+
+def conv_dgrad(dy, w):
+    """dL/dx of the 3x3 128->128 convolution with weights w, from dy = dL/dy."""
+    cin, k = _conv_shape(w)
+    if (cin, k) != (COUT, 3):
+        raise ValueError("the input gradient is built for the 3x3 128->128 convolution only")
+    B = _batch(dy, COUT)
+    lib, s = load(), _stream(dy)
+    wd = torch.empty((COUT * 9, COUT), dtype=torch.float32, device=dy.device)
+    _check(lib.bkt_conv_pack_dgrad(_dev(w, "w"), _dev(wd, "wt_dgrad"), s), "bkt_conv_pack_dgrad")
+    dx = torch.empty_like(dy)
+    _check(lib.bkt_conv_dgrad(_dev(dy, "dy"), _dev(wd, "wt_dgrad"), _dev(dx, "dx"), B, s), "bkt_conv_dgrad")
+    return dx
+
+
+def conv_wgrad(x, dy, w_shape, need_bias=True):
+    """(dL/dw [128, Cin, k, k], dL/dbias [128] or None) from the layer input x and dy = dL/dy."""
+    cin, k = int(w_shape[1]), int(w_shape[2])
+    B = _batch(x, cin)
+    _batch(dy, COUT)
+    if dy.shape[0] != B:
+        raise ValueError("x and dy have different batches")
+    lib = load()
+    nbytes = lib.bkt_conv_wgrad_workspace(B, cin, k)
+    if nbytes == 0:
+        raise ValueError(f"unsupported convolution: B={B} Cin={cin} k={k}")
+    ws = torch.empty((nbytes // 8,), dtype=torch.float64, device=x.device)  # 8-byte aligned: it holds double partials
+    dw = torch.empty((COUT, cin, k, k), dtype=torch.float32, device=x.device)
+    db = torch.empty((COUT,), dtype=torch.float32, device=x.device) if need_bias else None
+    _check(lib.bkt_conv_wgrad(_dev(x, "x"), _dev(dy, "dy"), _dev(dw, "dw"), None if db is None else _dev(db, "db"), B,
+                              cin, k, _dev(ws, "workspace", dtype=torch.float64), nbytes, _stream(x)), "bkt_conv_wgrad")
+    return dw, db
+
+
+def _bn_workspace(B, C, device):
+    nbytes = load().bkt_bn_workspace(B, C)
+    if nbytes == 0:
+        raise ValueError(f"unsupported BatchNorm: B={B} C={C}")
+    return torch.empty((nbytes // 8,), dtype=torch.float64, device=device), nbytes
+
+
+def bn_relu_train(x, gamma, beta, running_mean=None, running_var=None, num_batches_tracked=None,
+                  momentum=BN_MOMENTUM, eps=BN_EPS):
+    """Train-mode BatchNorm2d + ReLU; updates the running buffers in place.  -> (y, save_mean, save_invstd)"""
+    C = int(gamma.shape[0])
+    B = _batch(x, C)
+    y = torch.empty_like(x)
+    sm = torch.empty((C,), dtype=torch.float32, device=x.device)
+    si = torch.empty_like(sm)
+    rm = None if running_mean is None else _dev(running_mean, "running_mean", (C,))
+    rv = None if running_var is None else _dev(running_var, "running_var", (C,))
+    nbt = None if num_batches_tracked is None else _dev(num_batches_tracked, "num_batches_tracked", (), torch.int64)
+    ws, nbytes = _bn_workspace(B, C, x.device)
+    _check(load().bkt_bn_relu_train(_dev(x, "x"), _dev(gamma, "gamma", (C,)), _dev(beta, "beta", (C,)), rm, rv, nbt,
+                                    float(momentum), float(eps), _dev(y, "y"), _dev(sm, "mean"), _dev(si, "invstd"),
+                                    _dev(ws, "workspace", dtype=torch.float64), nbytes, B, C, _stream(x)),
+           "bkt_bn_relu_train")
+    return y, sm, si
+
+
+def bn_relu_backward(dy, y, x, gamma, save_mean, save_invstd):
+    """-> (dx, dgamma, dbeta) of bn_relu_train."""
+    C = int(gamma.shape[0])
+    B = _batch(x, C)
+    dx = torch.empty_like(x)
+    dg = torch.empty((C,), dtype=torch.float32, device=x.device)
+    db = torch.empty_like(dg)
+    ws, nbytes = _bn_workspace(B, C, x.device)
+    _check(load().bkt_bn_relu_backward(_dev(dy, "dy", x.shape), _dev(y, "y", x.shape), _dev(x, "x"),
+                                       _dev(gamma, "gamma", (C,)), _dev(save_mean, "mean", (C,)),
+                                       _dev(save_invstd, "invstd", (C,)), _dev(dx, "dx"), _dev(dg, "dgamma"),
+                                       _dev(db, "dbeta"), _dev(ws, "workspace", dtype=torch.float64), nbytes, B, C,
+                                       _stream(x)), "bkt_bn_relu_backward")
+    return dx, dg, db
+
+
+def bn_relu_eval(x, gamma, beta, running_mean, running_var, eps=BN_EPS):
+    C = int(gamma.shape[0])
+    B = _batch(x, C)
+    y = torch.empty_like(x)
+    _check(load().bkt_bn_relu_eval(_dev(x, "x"), _dev(gamma, "gamma", (C,)), _dev(beta, "beta", (C,)),
+                                   _dev(running_mean, "running_mean", (C,)), _dev(running_var, "running_var", (C,)),
+                                   float(eps), _dev(y, "y"), B, C, _stream(x)), "bkt_bn_relu_eval")
+    return y

@@ -1,0 +1,516 @@
+// bk_train.hip -- training kernels of the 9x9 trunk (include/bokego_train.h): implicit-GEMM convolutions (forward,
+// input gradient, weight gradient) on fp32 MFMA, and train/eval BatchNorm2d + ReLU.  Stateless: the caller owns
+// every buffer and the stream.  Nothing here uses float atomics, so every result is a fixed-order sum.
+#include <hip/hip_runtime.h>
+
+#include "../../include/bokego_train.h"
+
+namespace {
+
+constexpr int P = 81;                 // points of the board
+constexpr int BM = BKT_COUT;          // output channels: one GEMM tile spans all of them
+constexpr int BN = 64;                // GEMM columns per workgroup
+constexpr int BK = 16;                // reduction depth per LDS stage
+constexpr int PAD = 16;               // LDS row padding: the four k-rows of one MFMA operand read land in different banks
+constexpr int NT = 256;               // four waves: a 2x2 grid of 64x32 wave tiles
+constexpr int RT = 256;               // threads of the per-channel reductions
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+// One BK-deep stage of the 128 x 64 workgroup tile: wave w owns rows (w & 1) * 64 .. +64, columns (w >> 1) * 32 .. +32,
+// as 4 x 2 tiles of 16 x 16.  16x16x4 f32 MFMA operands: lane l holds A[l & 15][k = l >> 4] and B[k = l >> 4][l & 15].
+__device__ __forceinline__ void mma_stage(const float (*As)[BM + PAD], const float (*Bs)[BN + PAD], f32x4 (&acc)[4][2],
+                                          int lane, int wm, int wn) {
+    const int c = lane & 15;
+#pragma unroll
+    for (int kq = 0; kq < BK; kq += 4) {
+        const int kr = kq + (lane >> 4);
+        float a[4], b[2];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) a[i] = As[kr][wm + 16 * i + c];
+#pragma unroll
+        for (int j = 0; j < 2; ++j) b[j] = Bs[kr][wn + 16 * j + c];
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i], b[j], acc[i][j], 0, 0, 0);
+    }
+}
+
+// A stage's 16-deep products go into fresh accumulators, which are then added to the running sums with Kahan
+// compensation: a dot product of K = 1152 carries the rounding of a 16-term MFMA chain plus O(eps^2), not of a
+// 1152-term chain.  This matters where a gradient is a small difference of large partial sums (measured: 5e-4 relative
+// error of the deep layers' gradients in the value net with plain chains).
+__device__ __forceinline__ void stage_into(const float (*As)[BM + PAD], const float (*Bs)[BN + PAD], f32x4 (&acc)[4][2],
+                                           f32x4 (&comp)[4][2], int lane, int wm, int wn) {
+    f32x4 part[4][2];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) part[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    mma_stage(As, Bs, part, lane, wm, wn);
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const f32x4 y = part[i][j] - comp[i][j];
+            const f32x4 t = acc[i][j] + y;
+            comp[i][j] = (t - acc[i][j]) - y;
+            acc[i][j] = t;
+        }
+}
+
+// ---- forward: y[b][m][p] = sum_k wt[k][m] * im2col(x)[k][b*81 + p] (+ bias[m]) ----------------------------------------
+// Also the input gradient (wt = the rotated, channel-swapped filters, x = dy, no bias).
+template <int KS>
+__global__ __launch_bounds__(NT) void conv_fwd_kernel(const float *__restrict__ x, const float *__restrict__ wt,
+                                                      const float *__restrict__ bias, float *__restrict__ y, int batch,
+                                                      int cin) {
+    __shared__ float As[BK][BM + PAD];
+    __shared__ float Bs[BK][BN + PAD];
+    constexpr int KK = KS * KS, H = KS / 2;
+    const int K = cin * KK, N = batch * P;
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    const int n0 = blockIdx.x * BN;
+    // A (weights, K-major): this thread loads row am of k-rows ak, ak + 2, ...; B (gathered input): column bn of
+    // k-rows bk, bk + 4, ...  Both are coalesced along the lanes.
+    const int am = t & (BM - 1), ak = t >> 7;
+    const int bn = t & (BN - 1), bk = t >> 6;
+    const int n = n0 + bn;
+    const bool nvalid = n < N;
+    const int b = nvalid ? n / P : 0, p = nvalid ? n - (n / P) * P : 0;
+    const int py = p / 9, px = p - (p / 9) * 9;
+    const float *xb = x + (size_t)b * cin * P;
+
+    float ra[8], rb[4];
+    auto load = [&](int k0) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const int kk = k0 + ak + 2 * i;
+            ra[i] = kk < K ? wt[(size_t)kk * BM + am] : 0.f;
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int kk = k0 + bk + 4 * i;
+            float v = 0.f;
+            if (nvalid && kk < K) {
+                const int ci = kk / KK, tap = kk - ci * KK;
+                const int yy = py + tap / KS - H, xx = px + (tap - (tap / KS) * KS) - H;
+                if ((unsigned)yy < 9u && (unsigned)xx < 9u) v = xb[ci * P + yy * 9 + xx];
+            }
+            rb[i] = v;
+        }
+    };
+
+    f32x4 acc[4][2], comp[4][2];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) acc[i][j] = comp[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const int wm = (w & 1) * 64, wn = (w >> 1) * 32;
+
+    load(0);
+    for (int k0 = 0; k0 < K; k0 += BK) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) As[ak + 2 * i][am] = ra[i];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) Bs[bk + 4 * i][bn] = rb[i];
+        __syncthreads();
+        if (k0 + BK < K) load(k0 + BK);  // the next stage's global loads overlap this stage's MFMAs
+        stage_into(As, Bs, acc, comp, lane, wm, wn);
+        __syncthreads();
+    }
+
+    // C/D of 16x16x4: lane l, register r -> row (l >> 4) * 4 + r, column l & 15
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int nn = n0 + wn + 16 * j + (lane & 15);
+        if (nn >= N) continue;
+        const int ob = nn / P, op = nn - ob * P;
+        float *yb = y + (size_t)ob * BM * P + op;
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int m = wm + 16 * i + (lane >> 4) * 4 + r;
+                yb[m * P] = acc[i][j][r] + (bias ? bias[m] : 0.f);
+            }
+    }
+}
+
+// ---- weight gradient: part[chunk][m][n] = sum over the chunk's (b, p) of dy[b][m][p] * im2col(x)[n][b*81 + p] ----------
+template <int KS>
+__global__ __launch_bounds__(NT) void conv_wgrad_kernel(const float *__restrict__ x, const float *__restrict__ dy,
+                                                        float *__restrict__ part, int batch, int cin) {
+    __shared__ float As[BK][BM + PAD];
+    __shared__ float Bs[BK][BN + PAD];
+    constexpr int KK = KS * KS, H = KS / 2;
+    const int NC = cin * KK;
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    const int n0 = blockIdx.x * BN, chunk = blockIdx.y;
+    const int b_end = min(batch, (chunk + 1) * BKT_WGRAD_CHUNK);
+    const int K0 = chunk * BKT_WGRAD_CHUNK * P, K1 = b_end * P;
+    // both operands: k-row kr = t & 15 (consecutive lanes walk consecutive points), rows / columns (t >> 4) + 16 i
+    const int kr = t & 15, r0 = t >> 4;
+    int coff[4], cy[4], cx[4];
+    bool cval[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int nn = n0 + r0 + 16 * i;
+        cval[i] = nn < NC;
+        const int ci = cval[i] ? nn / KK : 0, tap = cval[i] ? nn - (nn / KK) * KK : 0;
+        coff[i] = ci * P;
+        cy[i] = tap / KS - H;
+        cx[i] = tap - (tap / KS) * KS - H;
+    }
+
+    float ra[8], rb[4];
+    auto load = [&](int k0) {
+        const int k = k0 + kr;
+        const bool kv = k < K1;
+        const int b = kv ? k / P : 0, p = kv ? k - (k / P) * P : 0;
+        const int py = p / 9, px = p - (p / 9) * 9;
+        const float *dyb = dy + (size_t)b * BM * P + p;
+        const float *xb = x + (size_t)b * cin * P;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) ra[i] = kv ? dyb[(r0 + 16 * i) * P] : 0.f;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int yy = py + cy[i], xx = px + cx[i];
+            rb[i] = (kv && cval[i] && (unsigned)yy < 9u && (unsigned)xx < 9u) ? xb[coff[i] + yy * 9 + xx] : 0.f;
+        }
+    };
+
+    f32x4 acc[4][2], comp[4][2];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) acc[i][j] = comp[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const int wm = (w & 1) * 64, wn = (w >> 1) * 32;
+
+    load(K0);
+    for (int k0 = K0; k0 < K1; k0 += BK) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) As[kr][r0 + 16 * i] = ra[i];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) Bs[kr][r0 + 16 * i] = rb[i];
+        __syncthreads();
+        if (k0 + BK < K1) load(k0 + BK);
+        stage_into(As, Bs, acc, comp, lane, wm, wn);
+        __syncthreads();
+    }
+
+    float *pc = part + (size_t)chunk * BM * NC;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int nn = n0 + wn + 16 * j + (lane & 15);
+        if (nn >= NC) continue;
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) pc[(size_t)(wm + 16 * i + (lane >> 4) * 4 + r) * NC + nn] = acc[i][j][r];
+    }
+}
+
+// dw[i] = sum over chunks, in chunk order, of part[chunk][i]
+__global__ __launch_bounds__(256) void chunk_sum_kernel(const float *__restrict__ part, float *__restrict__ dw, int n,
+                                                        int chunks) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    float s = 0.f;
+    for (int c = 0; c < chunks; ++c) s += part[(size_t)c * n + i];
+    dw[i] = s;
+}
+
+__global__ __launch_bounds__(256) void pack_kernel(const float *__restrict__ w, float *__restrict__ wt, int K) {
+    const int i = blockIdx.x * 256 + threadIdx.x;  // i = k * 128 + m
+    if (i >= K * BM) return;
+    const int k = i / BM, m = i - k * BM;
+    wt[i] = w[(size_t)m * K + k];
+}
+
+// wt[(co * 9 + tap) * 128 + ci] = w[co][ci][8 - tap]: the 3x3 filters turned by 180 degrees, input and output swapped
+__global__ __launch_bounds__(256) void pack_dgrad_kernel(const float *__restrict__ w, float *__restrict__ wt) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= BM * BM * 9) return;
+    const int ci = i % BM, k = i / BM, co = k / 9, tap = k - co * 9;
+    wt[i] = w[((size_t)co * BM + ci) * 9 + (8 - tap)];
+}
+
+// ---- per-channel reductions over B*81 values, in two fixed-order steps: workgroup (c, s) sums slice s (boards
+// 16 s .. 16 s + 15) of channel c -- a thread's strided serial sum, then an LDS tree -- into part[s][c]; a finalize kernel adds
+// the slices of a channel in slice order.  Sums are kept in double: they feed every element of the BatchNorm outputs.
+__device__ __forceinline__ void tree_sum2(double &a, double &b, double (*sh)[RT]) {
+    const int t = threadIdx.x;
+    sh[0][t] = a;
+    sh[1][t] = b;
+    __syncthreads();
+#pragma unroll
+    for (int s = RT / 2; s > 0; s >>= 1) {
+        if (t < s) {
+            sh[0][t] += sh[0][t + s];
+            sh[1][t] += sh[1][t + s];
+        }
+        __syncthreads();
+    }
+    a = sh[0][0];
+    b = sh[1][0];
+}
+
+enum { SUM_X_XX = 0, SUM_DZ_DZXHAT = 1, SUM_DY = 2 };
+
+// part[(s * C + c) * 2 + {0, 1}]:  SUM_X_XX: sum x, sum x^2;  SUM_DZ_DZXHAT: sum dz, sum dz * xhat (dz = dy where y > 0);
+// SUM_DY: sum dy
+template <int MODE>
+__global__ __launch_bounds__(RT) void chan_partial_kernel(const float *__restrict__ a, const float *__restrict__ y,
+                                                          const float *__restrict__ x, const float *__restrict__ mean,
+                                                          const float *__restrict__ invstd, double *__restrict__ part,
+                                                          int batch, int C) {
+    __shared__ double sh[2][RT];
+    const int c = blockIdx.x, s = blockIdx.y;
+    const int b0 = s * BKT_WGRAD_CHUNK, nb = min(batch - b0, BKT_WGRAD_CHUNK);
+    float mu = 0.f, is = 0.f;
+    if (MODE == SUM_DZ_DZXHAT) {
+        mu = mean[c];
+        is = invstd[c];
+    }
+    double s0 = 0.0, s1 = 0.0;
+    for (int i = threadIdx.x; i < nb * P; i += RT) {
+        const int b = b0 + i / P;
+        const size_t j = ((size_t)b * C + c) * P + (i - (i / P) * P);
+        if (MODE == SUM_X_XX) {
+            const double v = a[j];
+            s0 += v;
+            s1 += v * v;
+        } else if (MODE == SUM_DZ_DZXHAT) {
+            const float dz = y[j] > 0.f ? a[j] : 0.f;
+            s0 += dz;
+            s1 += (double)dz * (double)((x[j] - mu) * is);
+        } else {
+            s0 += a[j];
+        }
+    }
+    tree_sum2(s0, s1, sh);
+    if (threadIdx.x == 0) {
+        part[((size_t)s * C + c) * 2] = s0;
+        part[((size_t)s * C + c) * 2 + 1] = s1;
+    }
+}
+
+__device__ __forceinline__ void slice_sums(const double *__restrict__ part, int slices, int C, int c, double &s0,
+                                           double &s1) {
+    s0 = s1 = 0.0;
+    for (int s = 0; s < slices; ++s) {
+        s0 += part[((size_t)s * C + c) * 2];
+        s1 += part[((size_t)s * C + c) * 2 + 1];
+    }
+}
+
+// mean, biased variance, inverse std, running statistics (torch's update: unbiased variance into running_var)
+__global__ __launch_bounds__(256) void bn_stats_finalize_kernel(const double *__restrict__ part, int slices,
+                                                                float *running_mean, float *running_var, int64_t *nbt,
+                                                                float momentum, float eps,
+                                                                float *__restrict__ save_mean,
+                                                                float *__restrict__ save_invstd, int batch, int C) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c == 0 && nbt) *nbt += 1;
+    if (c >= C) return;
+    double s0, s1;
+    slice_sums(part, slices, C, c, s0, s1);
+    const double n = (double)batch * P;
+    const double mean = s0 / n;
+    const double var = fmax(s1 / n - mean * mean, 0.0);
+    save_mean[c] = (float)mean;
+    save_invstd[c] = (float)(1.0 / sqrt(var + (double)eps));
+    if (running_mean) running_mean[c] = (float)((1.0 - momentum) * running_mean[c] + momentum * mean);
+    if (running_var) running_var[c] = (float)((1.0 - momentum) * running_var[c] + momentum * (var * n / (n - 1.0)));
+}
+
+__global__ __launch_bounds__(256) void bn_bwd_finalize_kernel(const double *__restrict__ part, int slices,
+                                                              float *__restrict__ dgamma, float *__restrict__ dbeta,
+                                                              int C) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= C) return;
+    double s0, s1;
+    slice_sums(part, slices, C, c, s0, s1);
+    dbeta[c] = (float)s0;
+    dgamma[c] = (float)s1;
+}
+
+__global__ __launch_bounds__(256) void chan_sum_finalize_kernel(const double *__restrict__ part, int slices,
+                                                                float *__restrict__ out, int C) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= C) return;
+    double s0, s1;
+    slice_sums(part, slices, C, c, s0, s1);
+    out[c] = (float)s0;
+}
+
+__global__ __launch_bounds__(256) void bn_apply_kernel(const float *__restrict__ x, const float *__restrict__ mean,
+                                                       const float *__restrict__ invstd, const float *__restrict__ gamma,
+                                                       const float *__restrict__ beta, float *__restrict__ y,
+                                                       size_t total, int C) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const int c = (int)((i / P) % C);
+    y[i] = fmaxf((x[i] - mean[c]) * invstd[c] * gamma[c] + beta[c], 0.f);
+}
+
+__global__ __launch_bounds__(256) void bn_eval_kernel(const float *__restrict__ x, const float *__restrict__ gamma,
+                                                      const float *__restrict__ beta, const float *__restrict__ rmean,
+                                                      const float *__restrict__ rvar, float eps, float *__restrict__ y,
+                                                      size_t total, int C) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const int c = (int)((i / P) % C);
+    y[i] = fmaxf((x[i] - rmean[c]) * (1.f / sqrtf(rvar[c] + eps)) * gamma[c] + beta[c], 0.f);
+}
+
+__global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float *__restrict__ dy, const float *__restrict__ y,
+                                                           const float *__restrict__ x, const float *__restrict__ gamma,
+                                                           const float *__restrict__ mean,
+                                                           const float *__restrict__ invstd,
+                                                           const float *__restrict__ dgamma,
+                                                           const float *__restrict__ dbeta, float *__restrict__ dx,
+                                                           size_t total, int C, float inv_n) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const int c = (int)((i / P) % C);
+    const float is = invstd[c];
+    const float dz = y[i] > 0.f ? dy[i] : 0.f;
+    const float xhat = (x[i] - mean[c]) * is;
+    dx[i] = gamma[c] * is * (dz - dbeta[c] * inv_n - xhat * (dgamma[c] * inv_n));
+}
+
+inline hipStream_t S(void *s) { return (hipStream_t)s; }
+inline int launched() { return hipGetLastError() == hipSuccess ? BKT_OK : BKT_ERR_HIP; }
+inline bool ok_batch(int b) { return b >= 1 && b <= BKT_MAX_BATCH; }
+inline bool ok_conv(int cin, int ks) { return cin >= 1 && cin <= 4096 && (ks == 3 || ks == 5); }
+inline unsigned blocks(size_t n, int per) { return (unsigned)((n + per - 1) / per); }
+inline int slices_of(int batch) { return (batch + BKT_WGRAD_CHUNK - 1) / BKT_WGRAD_CHUNK; }
+
+}  // namespace
+
+extern "C" {
+
+int bkt_abi_version(void) { return BKT_ABI_VERSION; }
+
+int bkt_conv_pack(const float *w, int cin, int ksize, float *wt, void *stream) {
+    if (!w || !wt || !ok_conv(cin, ksize)) return BKT_ERR_ARG;
+    const int K = cin * ksize * ksize;
+    hipLaunchKernelGGL(pack_kernel, dim3(blocks((size_t)K * BM, 256)), dim3(256), 0, S(stream), w, wt, K);
+    return launched();
+}
+
+int bkt_conv_pack_dgrad(const float *w, float *wt_dgrad, void *stream) {
+    if (!w || !wt_dgrad) return BKT_ERR_ARG;
+    hipLaunchKernelGGL(pack_dgrad_kernel, dim3(blocks((size_t)BM * BM * 9, 256)), dim3(256), 0, S(stream), w,
+                       wt_dgrad);
+    return launched();
+}
+
+int bkt_conv_forward(const float *x, const float *wt, const float *bias, float *y, int batch, int cin, int ksize,
+                     void *stream) {
+    if (!x || !wt || !y || !ok_batch(batch) || !ok_conv(cin, ksize)) return BKT_ERR_ARG;
+    const dim3 grid(blocks((size_t)batch * P, BN));
+    if (ksize == 5)
+        hipLaunchKernelGGL(conv_fwd_kernel<5>, grid, dim3(NT), 0, S(stream), x, wt, bias, y, batch, cin);
+    else
+        hipLaunchKernelGGL(conv_fwd_kernel<3>, grid, dim3(NT), 0, S(stream), x, wt, bias, y, batch, cin);
+    return launched();
+}
+
+int bkt_conv_dgrad(const float *dy, const float *wt_dgrad, float *dx, int batch, void *stream) {
+    return bkt_conv_forward(dy, wt_dgrad, nullptr, dx, batch, BM, 3, stream);
+}
+
+size_t bkt_bn_workspace(int batch, int channels) {
+    if (!ok_batch(batch) || channels < 1 || channels > 4096) return 0;
+    return (size_t)slices_of(batch) * channels * 2 * sizeof(double);
+}
+
+size_t bkt_conv_wgrad_workspace(int batch, int cin, int ksize) {
+    if (!ok_batch(batch) || !ok_conv(cin, ksize)) return 0;
+    return bkt_bn_workspace(batch, BM) + (size_t)slices_of(batch) * BM * cin * ksize * ksize * sizeof(float);
+}
+
+int bkt_conv_wgrad(const float *x, const float *dy, float *dw, float *db, int batch, int cin, int ksize,
+                   void *workspace, size_t workspace_bytes, void *stream) {
+    if (!x || !dy || !dw || !workspace || !ok_batch(batch) || !ok_conv(cin, ksize)) return BKT_ERR_ARG;
+    if (workspace_bytes < bkt_conv_wgrad_workspace(batch, cin, ksize)) return BKT_ERR_ARG;
+    const int chunks = slices_of(batch);
+    const int NC = cin * ksize * ksize;
+    double *bpart = (double *)workspace;
+    float *part = (float *)((char *)workspace + bkt_bn_workspace(batch, BM));
+    const dim3 grid(blocks(NC, BN), chunks);
+    if (ksize == 5)
+        hipLaunchKernelGGL(conv_wgrad_kernel<5>, grid, dim3(NT), 0, S(stream), x, dy, part, batch, cin);
+    else
+        hipLaunchKernelGGL(conv_wgrad_kernel<3>, grid, dim3(NT), 0, S(stream), x, dy, part, batch, cin);
+    if (launched() != BKT_OK) return BKT_ERR_HIP;
+    hipLaunchKernelGGL(chunk_sum_kernel, dim3(blocks((size_t)BM * NC, 256)), dim3(256), 0, S(stream), part, dw,
+                       BM * NC, chunks);
+    if (launched() != BKT_OK) return BKT_ERR_HIP;
+    if (db) {
+        hipLaunchKernelGGL(chan_partial_kernel<SUM_DY>, dim3(BM, chunks), dim3(RT), 0, S(stream), dy, nullptr, nullptr,
+                           nullptr, nullptr, bpart, batch, BM);
+        if (launched() != BKT_OK) return BKT_ERR_HIP;
+        hipLaunchKernelGGL(chan_sum_finalize_kernel, dim3(1), dim3(256), 0, S(stream), bpart, chunks, db, BM);
+        return launched();
+    }
+    return BKT_OK;
+}
+
+int bkt_bn_relu_train(const float *x, const float *gamma, const float *beta, float *running_mean, float *running_var,
+                      int64_t *num_batches_tracked, float momentum, float eps, float *y, float *save_mean,
+                      float *save_invstd, void *workspace, size_t workspace_bytes, int batch, int channels,
+                      void *stream) {
+    if (!x || !gamma || !beta || !y || !save_mean || !save_invstd || !workspace || !ok_batch(batch) || channels < 1 ||
+        channels > 4096 || workspace_bytes < bkt_bn_workspace(batch, channels))
+        return BKT_ERR_ARG;
+    const int slices = slices_of(batch);
+    double *part = (double *)workspace;
+    hipLaunchKernelGGL(chan_partial_kernel<SUM_X_XX>, dim3(channels, slices), dim3(RT), 0, S(stream), x, nullptr,
+                       nullptr, nullptr, nullptr, part, batch, channels);
+    if (launched() != BKT_OK) return BKT_ERR_HIP;
+    hipLaunchKernelGGL(bn_stats_finalize_kernel, dim3(blocks(channels, 256)), dim3(256), 0, S(stream), part, slices,
+                       running_mean, running_var, num_batches_tracked, momentum, eps, save_mean, save_invstd, batch,
+                       channels);
+    if (launched() != BKT_OK) return BKT_ERR_HIP;
+    const size_t total = (size_t)batch * channels * P;
+    hipLaunchKernelGGL(bn_apply_kernel, dim3(blocks(total, 256)), dim3(256), 0, S(stream), x, save_mean, save_invstd,
+                       gamma, beta, y, total, channels);
+    return launched();
+}
+
+int bkt_bn_relu_backward(const float *dy, const float *y, const float *x, const float *gamma, const float *save_mean,
+                         const float *save_invstd, float *dx, float *dgamma, float *dbeta, void *workspace,
+                         size_t workspace_bytes, int batch, int channels, void *stream) {
+    if (!dy || !y || !x || !gamma || !save_mean || !save_invstd || !dx || !dgamma || !dbeta || !workspace ||
+        !ok_batch(batch) || channels < 1 || channels > 4096 || workspace_bytes < bkt_bn_workspace(batch, channels))
+        return BKT_ERR_ARG;
+    const int slices = slices_of(batch);
+    double *part = (double *)workspace;
+    hipLaunchKernelGGL(chan_partial_kernel<SUM_DZ_DZXHAT>, dim3(channels, slices), dim3(RT), 0, S(stream), dy, y, x,
+                       save_mean, save_invstd, part, batch, channels);
+    if (launched() != BKT_OK) return BKT_ERR_HIP;
+    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(blocks(channels, 256)), dim3(256), 0, S(stream), part, slices,
+                       dgamma, dbeta, channels);
+    if (launched() != BKT_OK) return BKT_ERR_HIP;
+    const size_t total = (size_t)batch * channels * P;
+    hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(blocks(total, 256)), dim3(256), 0, S(stream), dy, y, x, gamma,
+                       save_mean, save_invstd, dgamma, dbeta, dx, total, channels, 1.f / (float)(batch * P));
+    return launched();
+}
+
+int bkt_bn_relu_eval(const float *x, const float *gamma, const float *beta, const float *running_mean,
+                     const float *running_var, float eps, float *y, int batch, int channels, void *stream) {
+    if (!x || !gamma || !beta || !running_mean || !running_var || !y || !ok_batch(batch) || channels < 1 ||
+        channels > 4096)
+        return BKT_ERR_ARG;
+    const size_t total = (size_t)batch * channels * P;
+    hipLaunchKernelGGL(bn_eval_kernel, dim3(blocks(total, 256)), dim3(256), 0, S(stream), x, gamma, beta,
+                       running_mean, running_var, eps, y, total, channels);
+    return launched();
+}
+
+}  // extern "C"

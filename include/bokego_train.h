@@ -1,0 +1,100 @@
+/*
+ * bokego_train.h -- C ABI of the training kernels (libbktrain.so): the trunk of the reference's PolicyNet / ValueNet
+ * (bokego/nnet.py:31-57, 73-113) with gradients, for bokego_amd/train.py.
+ *
+ * Conventions:
+ *   - Stateless.  No entry point allocates device memory or keeps anything between calls: every buffer is a device
+ *     pointer the caller owns (torch tensors in bokego_amd/train.py, so torch's caching allocator holds all memory),
+ *     scratch included (bkt_conv_wgrad_workspace, bkt_bn_workspace).
+ *   - Every kernel is enqueued on `stream` (a hipStream_t; NULL = the null stream) and the call returns without
+ *     waiting.  Returns BKT_OK (0) or a negative bkt_status; BKT_ERR_HIP means a launch failed.
+ *   - Tensors are contiguous fp32 NCHW on the 9x9 board, [B, C, 9, 9]; conv weights are torch's [Cout, Cin, k, k]
+ *     with Cout = 128.  Supported convolutions: k = 5 (pad 2) and k = 3 (pad 1), any Cin >= 1; the network uses
+ *     5x5 27->128 and 3x3 128->128.  1 <= B <= BKT_MAX_BATCH.
+ *   - Arithmetic: fp32 in, fp32 accumulate (v_mfma_f32_16x16x4_f32).  Every result is deterministic: sums run in
+ *     an order fixed by the shapes alone (no float atomics), so equal inputs give equal bits.
+ */
+#ifndef BOKEGO_TRAIN_H
+#define BOKEGO_TRAIN_H
+
+#include <stddef.h>
+#include <stdint.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define BKT_ABI_VERSION 1
+#define BKT_MAX_BATCH 65536
+#define BKT_COUT 128
+
+typedef enum bkt_status {
+    BKT_OK = 0,
+    BKT_ERR_ARG = -1, /* null pointer, unsupported shape, workspace too small */
+    BKT_ERR_HIP = -2  /* a kernel launch failed                              */
+} bkt_status;
+
+int bkt_abi_version(void);
+
+/* ---- convolution (implicit GEMM: M = 128 output channels, N = B*81 points, K = Cin*k*k) ------------------------ */
+
+/* w [128, cin, k, k] -> wt [cin*k*k, 128] (K-major), the operand layout of bkt_conv_forward. */
+int bkt_conv_pack(const float *w, int cin, int ksize, float *wt, void *stream);
+
+/* y = conv(x, w) + bias (bias may be NULL).  x [B, cin, 9, 9], wt from bkt_conv_pack, y [B, 128, 9, 9].
+ * Taps that fall off the board read zero. */
+int bkt_conv_forward(const float *x, const float *wt, const float *bias, float *y, int batch, int cin, int ksize,
+                     void *stream);
+
+/* 3x3 128->128 only: w [128, 128, 3, 3] -> wt_dgrad [128*9, 128], the filters rotated by 180 degrees with input and
+ * output channels swapped, packed as bkt_conv_pack packs. */
+int bkt_conv_pack_dgrad(const float *w, float *wt_dgrad, void *stream);
+
+/* dx = dL/dx of the 3x3 128->128 convolution: the forward problem on dy with the bkt_conv_pack_dgrad filters.
+ * dy, dx [B, 128, 9, 9]. */
+int bkt_conv_dgrad(const float *dy, const float *wt_dgrad, float *dx, int batch, void *stream);
+
+/* The batch is reduced in fixed slices of BKT_WGRAD_CHUNK boards: one partial result per slice, then the slices are
+ * added in slice order. */
+#define BKT_WGRAD_CHUNK 16
+
+/* Bytes of scratch bkt_conv_wgrad needs: a [128, cin*k*k] fp32 partial and 128 x 2 double partials per slice
+ * (0 for unsupported arguments). */
+size_t bkt_conv_wgrad_workspace(int batch, int cin, int ksize);
+
+/* dw [128, cin, k, k] = dL/dw and db [128] = dL/dbias (db may be NULL), from the layer input x [B, cin, 9, 9] and
+ * dy = dL/dy [B, 128, 9, 9].  The batch is split into fixed chunks whose partial products go to `workspace`; a
+ * second kernel sums the chunks in chunk order.  Overwrites dw and db (no accumulation into them). */
+int bkt_conv_wgrad(const float *x, const float *dy, float *dw, float *db, int batch, int cin, int ksize,
+                   void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---- BatchNorm2d + ReLU over `channels` channels of B*81 values each ------------------------------------------------ */
+
+/* Bytes of scratch bkt_bn_relu_train / bkt_bn_relu_backward need: channels x 2 doubles per slice of boards. */
+size_t bkt_bn_workspace(int batch, int channels);
+
+/* Train mode: batch mean and biased variance (per-slice sums of x and x^2 in double),
+ * y = relu((x - mean) * invstd * gamma + beta), invstd = 1/sqrt(var + eps).
+ * save_mean / save_invstd [channels] keep what bkt_bn_relu_backward needs.  When running_mean / running_var are
+ * not NULL they are updated as torch does: r = (1 - momentum) * r + momentum * s, with the UNBIASED variance
+ * var * n / (n - 1) (n = B*81) going into running_var; num_batches_tracked (int64, may be NULL) is incremented. */
+int bkt_bn_relu_train(const float *x, const float *gamma, const float *beta, float *running_mean, float *running_var,
+                      int64_t *num_batches_tracked, float momentum, float eps, float *y, float *save_mean,
+                      float *save_invstd, void *workspace, size_t workspace_bytes, int batch, int channels,
+                      void *stream);
+
+/* Gradients of bkt_bn_relu_train: dy = dL/dy, y its output (the ReLU mask is y > 0), x its input.
+ * Writes dx [B, channels, 9, 9], dgamma and dbeta [channels]. */
+int bkt_bn_relu_backward(const float *dy, const float *y, const float *x, const float *gamma, const float *save_mean,
+                         const float *save_invstd, float *dx, float *dgamma, float *dbeta, void *workspace,
+                         size_t workspace_bytes, int batch, int channels, void *stream);
+
+/* Eval mode: y = relu((x - running_mean) / sqrt(running_var + eps) * gamma + beta). */
+int bkt_bn_relu_eval(const float *x, const float *gamma, const float *beta, const float *running_mean,
+                     const float *running_var, float eps, float *y, int batch, int channels, void *stream);
+
+#ifdef __cplusplus
+}
+#endif
+
+#endif /* BOKEGO_TRAIN_H */
