@@ -11,14 +11,14 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libbktrain.so")
 
-BKT_ABI_VERSION = 1
+BKT_ABI_VERSION = 2
 COUT = 128
 BN_EPS = 1e-5
 BN_MOMENTUM = 0.1
 STATUS_NAMES = {0: "BKT_OK", -1: "BKT_ERR_ARG", -2: "BKT_ERR_HIP"}
 
 _P = ctypes.c_void_p
-_I, _F, _Z = ctypes.c_int, ctypes.c_float, ctypes.c_size_t
+_I, _F, _Z, _U64 = ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.c_uint64
 SYMBOLS = {
     "bkt_abi_version": (_I, []),
     "bkt_conv_pack": (_I, [_P, _I, _I, _P, _P]),
@@ -31,6 +31,8 @@ SYMBOLS = {
     "bkt_bn_relu_train": (_I, [_P, _P, _P, _P, _P, _P, _F, _F, _P, _P, _P, _P, _Z, _I, _I, _P]),
     "bkt_bn_relu_backward": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _I, _I, _P]),
     "bkt_bn_relu_eval": (_I, [_P, _P, _P, _P, _P, _F, _P, _I, _I, _P]),
+    "bkt_bn_relu_eval_backward": (_I, [_P, _P, _P, _P, _P, _P, _F, _P, _P, _P, _P, _Z, _I, _I, _P]),
+    "bkt_sample_moves": (_I, [_P, _P, _I, _U64, _P, _P, _P, _P]),
 }
 
 _lib = None
@@ -190,3 +192,37 @@ def bn_relu_eval(x, gamma, beta, running_mean, running_var, eps=BN_EPS):
                                    _dev(running_mean, "running_mean", (C,)), _dev(running_var, "running_var", (C,)),
                                    float(eps), _dev(y, "y"), B, C, _stream(x)), "bkt_bn_relu_eval")
     return y
+
+
+def bn_relu_eval_backward(dy, y, x, gamma, running_mean, running_var, eps=BN_EPS):
+    """-> (dx, dgamma, dbeta) of bn_relu_eval: the frozen-statistics gradient (no term through the batch statistics)."""
+    C = int(gamma.shape[0])
+    B = _batch(x, C)
+    dx = torch.empty_like(x)
+    dg = torch.empty((C,), dtype=torch.float32, device=x.device)
+    db = torch.empty_like(dg)
+    ws, nbytes = _bn_workspace(B, C, x.device)
+    _check(load().bkt_bn_relu_eval_backward(_dev(dy, "dy", x.shape), _dev(y, "y", x.shape), _dev(x, "x"),
+                                            _dev(gamma, "gamma", (C,)), _dev(running_mean, "running_mean", (C,)),
+                                            _dev(running_var, "running_var", (C,)), float(eps), _dev(dx, "dx"),
+                                            _dev(dg, "dgamma"), _dev(db, "dbeta"),
+                                            _dev(ws, "workspace", dtype=torch.float64), nbytes, B, C, _stream(x)),
+           "bkt_bn_relu_eval_backward")
+    return dx, dg, db
+
+
+def sample_moves(logits, planes, seed, counters):
+    """One move per row: logits [B,81] f32, planes uint8 [B,27,9,9] (plane 5: legal points), counters int32 [B,4]
+    (the Philox counter words, read as uint32) -> (moves int32 [B], -1 where no point is legal; logp f32 [B])."""
+    if logits.dim() != 2 or logits.shape[1] != 81:
+        raise ValueError(f"logits must be [B, 81], got {tuple(logits.shape)}")
+    B = int(logits.shape[0])
+    moves = torch.empty((B,), dtype=torch.int32, device=logits.device)
+    logp = torch.empty((B,), dtype=torch.float32, device=logits.device)
+    if B == 0:
+        return moves, logp
+    _check(load().bkt_sample_moves(_dev(logits, "logits"), _dev(planes, "planes", (B, 27, 9, 9), torch.uint8), B,
+                                   int(seed) & (2 ** 64 - 1), _dev(counters, "counters", (B, 4), torch.int32),
+                                   _dev(moves, "moves", dtype=torch.int32), _dev(logp, "logp"), _stream(logits)),
+           "bkt_sample_moves")
+    return moves, logp

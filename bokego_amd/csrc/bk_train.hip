@@ -1,6 +1,7 @@
 // bk_train.hip -- training kernels of the 9x9 trunk (include/bokego_train.h): implicit-GEMM convolutions (forward,
-// input gradient, weight gradient) on fp32 MFMA, and train/eval BatchNorm2d + ReLU.  Stateless: the caller owns
-// every buffer and the stream.  Nothing here uses float atomics, so every result is a fixed-order sum.
+// input gradient, weight gradient) on fp32 MFMA, train/eval BatchNorm2d + ReLU with their gradients, and the move
+// sampler of the REINFORCE playouts.  Stateless: the caller owns every buffer and the stream.  Nothing here uses float
+// atomics, so every result is a fixed-order sum.
 #include <hip/hip_runtime.h>
 
 #include "../../include/bokego_train.h"
@@ -381,6 +382,135 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float *__restri
     dx[i] = gamma[c] * is * (dz - dbeta[c] * inv_n - xhat * (dgamma[c] * inv_n));
 }
 
+// Eval-mode (frozen statistics) analogue of chan_partial_kernel<SUM_DZ_DZXHAT>: part[(s * C + c) * 2 + {0, 1}] = sum dz,
+// sum dz * (x - running_mean) * invstd over slice s, dz = dy where y > 0, invstd = 1/sqrt(running_var + eps) in double.
+__global__ __launch_bounds__(RT) void bn_eval_bwd_partial_kernel(const float *__restrict__ dy, const float *__restrict__ y,
+                                                                 const float *__restrict__ x,
+                                                                 const float *__restrict__ rmean,
+                                                                 const float *__restrict__ rvar, float eps,
+                                                                 double *__restrict__ part, int batch, int C) {
+    __shared__ double sh[2][RT];
+    const int c = blockIdx.x, s = blockIdx.y;
+    const int b0 = s * BKT_WGRAD_CHUNK, nb = min(batch - b0, BKT_WGRAD_CHUNK);
+    const double mu = rmean[c], is = 1.0 / sqrt((double)rvar[c] + (double)eps);
+    double s0 = 0.0, s1 = 0.0;
+    for (int i = threadIdx.x; i < nb * P; i += RT) {
+        const int b = b0 + i / P;
+        const size_t j = ((size_t)b * C + c) * P + (i - (i / P) * P);
+        const float dz = y[j] > 0.f ? dy[j] : 0.f;
+        s0 += dz;
+        s1 += (double)dz * (((double)x[j] - mu) * is);
+    }
+    tree_sum2(s0, s1, sh);
+    if (threadIdx.x == 0) {
+        part[((size_t)s * C + c) * 2] = s0;
+        part[((size_t)s * C + c) * 2 + 1] = s1;
+    }
+}
+
+// dx = dy * [y > 0] * gamma / sqrt(running_var + eps): the scale bn_eval_kernel applies, in the same fp32 form
+__global__ __launch_bounds__(256) void bn_eval_bwd_apply_kernel(const float *__restrict__ dy, const float *__restrict__ y,
+                                                                const float *__restrict__ gamma,
+                                                                const float *__restrict__ rvar, float eps,
+                                                                float *__restrict__ dx, size_t total, int C) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const int c = (int)((i / P) % C);
+    const float dz = y[i] > 0.f ? dy[i] : 0.f;
+    dx[i] = dz * (gamma[c] * (1.f / sqrtf(rvar[c] + eps)));
+}
+
+// ---- move sampling: Philox4x32-10 (Salmon et al., SC'11; the Random123 constants) and one wave64 per row ---------------
+constexpr int SAMPLE_WAVES = 4;       // rows per workgroup
+constexpr int LEGAL_PLANE = 5;        // nnet.features' "legal" plane
+
+__device__ __forceinline__ void philox4x32_10(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        if (r) {
+            k0 += 0x9E3779B9u;
+            k1 += 0xBB67AE85u;
+        }
+        const uint32_t lo0 = 0xD2511F53u * c[0], hi0 = __umulhi(0xD2511F53u, c[0]);
+        const uint32_t lo1 = 0xCD9E8D57u * c[2], hi1 = __umulhi(0xCD9E8D57u, c[2]);
+        const uint32_t n0 = hi1 ^ c[1] ^ k0, n2 = hi0 ^ c[3] ^ k1;
+        c[0] = n0;
+        c[1] = lo1;
+        c[2] = n2;
+        c[3] = lo0;
+    }
+}
+
+// Lane l holds points l and 64 + l (the second only for l < 17).  Every branch below is uniform over the wave.
+__global__ __launch_bounds__(64 * SAMPLE_WAVES) void sample_moves_kernel(const float *__restrict__ logits,
+                                                                         const uint8_t *__restrict__ planes, int batch,
+                                                                         uint32_t k0, uint32_t k1,
+                                                                         const uint32_t *__restrict__ counters,
+                                                                         int32_t *__restrict__ moves,
+                                                                         float *__restrict__ logp) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * SAMPLE_WAVES + (threadIdx.x >> 6);
+    if (row >= batch) return;
+    const float *x = logits + (size_t)row * P;
+    const uint8_t *legal = planes + ((size_t)row * 27 + LEGAL_PLANE) * P;
+    const bool has1 = lane < P - 64;
+    const float xa = x[lane], xb = has1 ? x[64 + lane] : -INFINITY;
+    float m = fmaxf(xa, xb);
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) m = fmaxf(m, __shfl_xor(m, d));
+    const float pa = expf(xa - m), pb = has1 ? expf(xb - m) : 0.f;
+    float sa = pa, sb = pb;  // inclusive prefixes of p over points 0..63 and 64..80
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const float ta = __shfl_up(sa, d), tb = __shfl_up(sb, d);
+        if (lane >= d) {
+            sa += ta;
+            sb += tb;
+        }
+    }
+    sb += __shfl(sa, 63);
+    const float S = __shfl(sb, P - 64 - 1);
+
+    uint32_t c[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) c[k] = counters[(size_t)row * 4 + k];
+    philox4x32_10(c, k0, k1);
+    const float thr = (float)(c[0] >> 8) * 0x1p-24f * S;
+    const unsigned long long ga = __ballot(sa > thr), gb = __ballot(has1 && sb > thr);
+    int mv;
+    if (ga)
+        mv = __ffsll(ga) - 1;
+    else if (gb)
+        mv = 64 + __ffsll(gb) - 1;
+    else {  // no prefix above u * S (not expected: u * S < S in fp32): the last point with p > 0
+        const unsigned long long za = __ballot(pa > 0.f), zb = __ballot(has1 && pb > 0.f);
+        mv = zb ? 64 + 63 - __clzll(zb) : (za ? 63 - __clzll(za) : 0);
+    }
+    const unsigned long long la = __ballot(legal[lane] != 0), lb = __ballot(has1 && legal[64 + lane] != 0);
+    const bool ok = mv < 64 ? (la >> mv) & 1ull : (lb >> (mv - 64)) & 1ull;
+    if (!ok) {
+        if (!(la | lb)) {
+            mv = -1;
+        } else {  // the legal point of the largest logit, lowest index on ties
+            float bv = -INFINITY;
+            int bi = 1 << 30;
+            if ((la >> lane) & 1ull) bv = xa, bi = lane;
+            if (((lb >> lane) & 1ull) && (bi == (1 << 30) || xb > bv)) bv = xb, bi = 64 + lane;
+#pragma unroll
+            for (int d = 32; d > 0; d >>= 1) {
+                const float ov = __shfl_xor(bv, d);
+                const int oi = __shfl_xor(bi, d);
+                if (ov > bv || (ov == bv && oi < bi)) bv = ov, bi = oi;
+            }
+            mv = bi;
+        }
+    }
+    if (lane == 0) {
+        moves[row] = mv;
+        logp[row] = mv >= 0 ? (x[mv] - m) - logf(S) : 0.f;
+    }
+}
+
 inline hipStream_t S(void *s) { return (hipStream_t)s; }
 inline int launched() { return hipGetLastError() == hipSuccess ? BKT_OK : BKT_ERR_HIP; }
 inline bool ok_batch(int b) { return b >= 1 && b <= BKT_MAX_BATCH; }
@@ -510,6 +640,35 @@ int bkt_bn_relu_eval(const float *x, const float *gamma, const float *beta, cons
     const size_t total = (size_t)batch * channels * P;
     hipLaunchKernelGGL(bn_eval_kernel, dim3(blocks(total, 256)), dim3(256), 0, S(stream), x, gamma, beta,
                        running_mean, running_var, eps, y, total, channels);
+    return launched();
+}
+
+int bkt_bn_relu_eval_backward(const float *dy, const float *y, const float *x, const float *gamma,
+                              const float *running_mean, const float *running_var, float eps, float *dx, float *dgamma,
+                              float *dbeta, void *workspace, size_t workspace_bytes, int batch, int channels,
+                              void *stream) {
+    if (!dy || !y || !x || !gamma || !running_mean || !running_var || !dx || !dgamma || !dbeta || !workspace ||
+        !ok_batch(batch) || channels < 1 || channels > 4096 || workspace_bytes < bkt_bn_workspace(batch, channels))
+        return BKT_ERR_ARG;
+    const int slices = slices_of(batch);
+    double *part = (double *)workspace;
+    hipLaunchKernelGGL(bn_eval_bwd_partial_kernel, dim3(channels, slices), dim3(RT), 0, S(stream), dy, y, x,
+                       running_mean, running_var, eps, part, batch, channels);
+    if (launched() != BKT_OK) return BKT_ERR_HIP;
+    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(blocks(channels, 256)), dim3(256), 0, S(stream), part, slices,
+                       dgamma, dbeta, channels);
+    if (launched() != BKT_OK) return BKT_ERR_HIP;
+    const size_t total = (size_t)batch * channels * P;
+    hipLaunchKernelGGL(bn_eval_bwd_apply_kernel, dim3(blocks(total, 256)), dim3(256), 0, S(stream), dy, y, gamma,
+                       running_var, eps, dx, total, channels);
+    return launched();
+}
+
+int bkt_sample_moves(const float *logits, const uint8_t *planes, int batch, uint64_t seed, const uint32_t *counters,
+                     int32_t *moves, float *logp, void *stream) {
+    if (!logits || !planes || !counters || !moves || !logp || batch < 1 || batch > BKT_MAX_SAMPLE_ROWS) return BKT_ERR_ARG;
+    hipLaunchKernelGGL(sample_moves_kernel, dim3(blocks(batch, SAMPLE_WAVES)), dim3(64 * SAMPLE_WAVES), 0, S(stream),
+                       logits, planes, batch, (uint32_t)seed, (uint32_t)(seed >> 32), counters, moves, logp);
     return launched();
 }
 

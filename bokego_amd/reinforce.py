@@ -1,0 +1,466 @@
+"""REINFORCE on policy-vs-policy games against a pool of earlier policies (the reference's bin/selfplay.py:59-208).
+
+    python -m bokego_amd.reinforce -w WEIGHTS_DIR [-e E] [-n N] [-b B] [--workers W] [-f STATS] [--lr 1e-5] [--seed S]
+                                   [--opponent ID|random] [--device D]
+
+The pool is the policy_<id>.pt / .bkw files of -w.  With n = (number of ids) - 1, policy_n is trained; each epoch it
+plays an opponent from the pool (policy_0 when it exists), writes policy_{n+1}.pt and three lines of statistics, and n
+grows by one.  An iteration plays W batches of b games in lock-step -- the learner is black in even batches and white
+in odd ones -- with the learner's weights as they stood at the start of the iteration, then takes one AdamW step per
+batch, in batch order, on
+
+    loss_batch = (1/b) * sum_games r_g * sum_{learner's plies} -log pi(a|s),     r_g = +1 if the learner won, else -1.
+
+Playouts (play_games): per ply one bk_features_batch_u8 call on the live games' bk_pos records, one upload, one
+fp32 LeafEngine.eval_device per side, bkt_sample_moves on the logits, and 4 bytes per game back to the host, which
+plays the moves.  The learner's rows (planes and moves) stay on the device and are the update's batch.
+
+The update differentiates the network that sampled the moves: the eval-mode TrainablePolicyNet, BatchNorm with its
+running statistics frozen (train._TrunkBlockEval), which is the function the engine computes with the statistics
+folded in.  Randomness comes only from Philox4x32-10 keyed by --seed with counter (game, ply, iteration, epoch), so
+the same seed and pool give the same checkpoints bit for bit.  DESIGN 12 lists where this departs from the reference.
+"""
+import argparse
+import ctypes
+import json
+import os
+import re
+import time
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+from . import _trainlib as T
+from . import go
+from .selfplay import POLICY_MAX_TURNS
+
+KOMI = 5.5
+LEGAL_PLANE = 5            # nnet.features' "legal" plane (reference nnet.py:198)
+POS_BYTES = 192            # sizeof(bk_pos)
+PLANE_BYTES = 27 * 81
+UPDATE_CHUNK = 32768       # rows per forward/backward of the update (libbktrain's trunk takes up to 65536)
+
+# ---- Philox4x32-10 and the sampler, host mirrors of bk_train.hip (float64) ----------------------------------------------
+PHILOX_M = (0xD2511F53, 0xCD9E8D57)
+PHILOX_W = (0x9E3779B9, 0xBB67AE85)
+_MASK32 = np.uint64(0xFFFFFFFF)
+
+
+def philox4x32_10(ctr, key):
+    """ctr uint32 [..., 4], key uint32 [..., 2] (broadcast) -> uint32 [..., 4] (Random123's philox4x32 with 10 rounds)."""
+    c = [np.asarray(ctr, np.uint64)[..., i] & _MASK32 for i in range(4)]
+    k = np.asarray(key, np.uint64)
+    k0, k1 = k[..., 0] & _MASK32, k[..., 1] & _MASK32
+    for r in range(10):
+        if r:
+            k0 = (k0 + np.uint64(PHILOX_W[0])) & _MASK32
+            k1 = (k1 + np.uint64(PHILOX_W[1])) & _MASK32
+        p0 = np.uint64(PHILOX_M[0]) * c[0]
+        p1 = np.uint64(PHILOX_M[1]) * c[2]
+        c = [(p1 >> np.uint64(32)) ^ c[1] ^ k0, p1 & _MASK32, (p0 >> np.uint64(32)) ^ c[3] ^ k1, p0 & _MASK32]
+    return np.stack(c, -1).astype(np.uint32)
+
+
+def seed_key(seed):
+    """--seed (an unsigned 64-bit integer) -> the Philox key words (low, high)."""
+    s = int(seed) & (2 ** 64 - 1)
+    return np.array([s & 0xFFFFFFFF, s >> 32], np.uint32)
+
+
+def uniform(x0):
+    """The first Philox output word -> u = (x0 >> 8) * 2^-24 in [0, 1), exact in float32 and float64."""
+    return (np.asarray(x0, np.uint32) >> np.uint32(8)).astype(np.float64) * 2.0 ** -24
+
+
+def counters(game_ids, ply, iteration, epoch):
+    """The counter words (game id, ply, iteration, epoch) of each game, as int32 [n, 4] (the bits the kernel reads)."""
+    g = np.asarray(game_ids, np.int64)
+    c = np.empty((len(g), 4), np.uint32)
+    c[:, 0] = g
+    c[:, 1] = int(ply)
+    c[:, 2] = int(iteration)
+    c[:, 3] = int(epoch)
+    return c.view(np.int32)
+
+
+def sample_host(logits, legal, u):
+    """bkt_sample_moves in float64: logits [B,81], legal bool [B,81], u [B] -> (moves int32 [B], logp float64 [B]).
+    The move is the first point whose inclusive prefix of p = exp(x - max) exceeds u * sum p; an illegal sample becomes
+    the legal point of the largest logit (lowest index on ties); -1 when no point is legal."""
+    x = np.asarray(logits, np.float64)
+    legal = np.asarray(legal, bool)
+    m = x.max(1, keepdims=True)
+    c = np.cumsum(np.exp(x - m), 1)
+    S = c[:, -1]
+    mv = np.argmax(c > (np.asarray(u, np.float64) * S)[:, None], 1)
+    rows = np.arange(len(x))
+    bad = ~legal[rows, mv]
+    fix = np.argmax(np.where(legal, x, -np.inf), 1)
+    mv = np.where(bad, fix, mv)
+    none = ~legal.any(1)
+    mv[none] = -1
+    logp = np.where(none, 0.0, x[rows, np.maximum(mv, 0)] - m[:, 0] - np.log(S))
+    return mv.astype(np.int32), logp
+
+
+def cdf_margin(logits, u):
+    """min_i |u - CDF_i| over the float64 CDF of each row: how close u lies to a boundary between two points."""
+    x = np.asarray(logits, np.float64)
+    c = np.cumsum(np.exp(x - x.max(1, keepdims=True)), 1)
+    c /= c[:, -1:]
+    return np.abs(c - np.asarray(u, np.float64)[:, None]).min(1)
+
+
+# ---- the loss ----------------------------------------------------------------------------------------------------------
+def reinforce_loss(logp, row_game, rewards, batch_size):
+    """(1/b) * sum_g r_g * sum_{rows of g} -logp: logp [R] log pi(a|s) of the learner's rows, row_game [R] the game
+    (0..b-1) of each row, rewards [b] +1 / -1 from the learner's side."""
+    return -(rewards[row_game] * logp).sum() / batch_size
+
+
+# ---- the pool ---------------------------------------------------------------------------------------------------------
+_POLICY_FILE = re.compile(r"policy_(\d+)\.(pt|bkw)$")
+
+
+def policy_pool(wdir):
+    """{id: path} of the policy_<id>.pt / policy_<id>.bkw files in wdir (.pt wins when both exist)."""
+    pool = {}
+    for name in sorted(os.listdir(wdir)):
+        m = _POLICY_FILE.fullmatch(name)
+        if m and (int(m[1]) not in pool or m[2] == "pt"):
+            pool[int(m[1])] = os.path.join(wdir, name)
+    return pool
+
+
+def learner_id(pool, wdir="."):
+    """n = (number of policies) - 1, the reference's pool numbering (selfplay.py:144-148); policy_n must exist."""
+    if not pool:
+        raise FileNotFoundError(f"no policy_<id>.pt or .bkw in {wdir}")
+    n = len(pool) - 1
+    if n not in pool:
+        raise FileNotFoundError(f"{len(pool)} policies in {wdir} but no policy_{n}: the pool must be numbered 0..{n}")
+    return n
+
+
+def choose_opponent(pool, n, seed, epoch, opponent=None):
+    """policy_0 when it exists, else a seeded uniform choice among the ids 0..n present (selfplay.py:160-166);
+    opponent: an id of the pool, or "random" for the seeded choice even when policy_0 exists."""
+    ids = sorted(i for i in pool if i <= n)
+    if opponent is not None and opponent != "random":
+        if int(opponent) not in pool:
+            raise FileNotFoundError(f"--opponent {opponent}: no policy_{opponent} in the pool")
+        return int(opponent)
+    if opponent is None and 0 in pool:
+        return 0
+    rng = np.random.default_rng([int(seed) & (2 ** 64 - 1), int(epoch)])
+    return ids[int(rng.integers(len(ids)))]
+
+
+def stats_lines(n, opp, batch_size, iterations, wins):
+    """The three lines the reference appends per epoch (selfplay.py:201-204)."""
+    return [f"Policy {n} vs. Policy {opp}", f"Batch Size: {batch_size}, Iterations: {iterations}",
+            ",".join(str(int(w)) for w in wins)]
+
+
+# ---- lock-step playouts ------------------------------------------------------------------------------------------------
+_PLAY = None
+
+
+def _play_fn():
+    """bk_pos_play taking a plain address (the records live in numpy arrays)."""
+    global _PLAY
+    if _PLAY is None:
+        _PLAY = ctypes.cast(go.golib().bk_pos_play, ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int))
+    return _PLAY
+
+
+FEATURE_THREADS = 8        # bk_features_batch_u8 calls in flight per ply (ctypes releases the GIL during each)
+FEATURE_CHUNK = 512        # positions per call
+_POOL = None
+
+
+def features_batch(recs, out_ptr):
+    """bk_features_batch_u8 over the contiguous bk_pos records recs [n, 192] into out_ptr ([n,27,9,9] uint8), split
+    into chunks encoded on FEATURE_THREADS threads: the records are independent, and so are the calls."""
+    global _POOL
+    lib, n, base = go.golib(), len(recs), recs.ctypes.data
+    if n <= FEATURE_CHUNK:
+        lib.bk_features_batch_u8(base, n, POS_BYTES, out_ptr, 0)
+        return
+    if _POOL is None:
+        from concurrent.futures import ThreadPoolExecutor
+        _POOL = ThreadPoolExecutor(FEATURE_THREADS, thread_name_prefix="bk-features")
+    jobs = [_POOL.submit(lib.bk_features_batch_u8, base + POS_BYTES * s, min(FEATURE_CHUNK, n - s), POS_BYTES,
+                         out_ptr + PLANE_BYTES * s, 0) for s in range(0, n, FEATURE_CHUNK)]
+    for j in jobs:
+        j.result()
+
+
+def initial_positions(n):
+    """n empty-board bk_pos records, uint8 [n, 192]."""
+    one = np.frombuffer(bytes(go.Game()._pos), np.uint8)
+    return np.tile(one, (n, 1))
+
+
+class Playouts:
+    """What play_games returns.
+
+    moves         int16 [G, 71]  the moves of each game (PASS = -1 pads after its end), game g in batch g // b
+    length        int [G]        plies played
+    black_wins    bool [G]       area score with komi 5.5 > 0
+    learner_black bool [G]       the learner plays black (even batches)
+    reward        float32 [G]    +1 / -1 from the learner's side
+    planes        uint8 [R,27,9,9] on the device: the positions where the learner moved, in ply order, games ascending
+    played        int64 [R] on the device: the learner's move in each
+    logp          float32 [R] on the device: bkt_sample_moves' log-probability of it
+    row_game      int64 [R] (host): the game of each row
+    """
+
+    def batch_rows(self, w, b):
+        """Device index of the rows of batch w (games w*b .. w*b + b - 1) and their games within the batch."""
+        sel = np.nonzero(self.row_game // b == w)[0]
+        dev = self.planes.device
+        return torch.from_numpy(sel).to(dev), torch.from_numpy(self.row_game[sel] - w * b).to(dev)
+
+
+def play_games(learner, opponent, n_batches, batch_size, seed, iteration=0, epoch=0, device=None, timing=None,
+               max_turns=POLICY_MAX_TURNS):
+    """n_batches * batch_size games in lock-step between two fp32 LeafEngines (policy weights); the learner is black in
+    even batches.  timing: a dict that receives seconds spent in 'host' (features, staging, playing the moves),
+    'engine' (upload + both evaluations) and 'sampler' (bkt_sample_moves + the copy back); the phases are then
+    separated by synchronisations, so pass it only to measure."""
+    dev = torch.device("cuda", learner.device_id) if device is None else torch.device(device)
+    G = n_batches * batch_size
+    lib, play = go.golib(), _play_fn()
+    key = int(seed) & (2 ** 64 - 1)
+    learner_black = (np.arange(G) // batch_size) % 2 == 0
+    pos = initial_positions(G)
+    hist = np.full((G, max_turns + 1), go.PASS, np.int16)
+    length = np.zeros(G, np.int64)
+    staging = torch.empty(G * (16 + PLANE_BYTES), dtype=torch.uint8).pin_memory()
+    stage = staging.numpy()
+    rows_planes, rows_moves, rows_logp, rows_game = [], [], [], []
+    live = np.arange(G)
+    clock = time.perf_counter
+
+    def lap(name, t0):
+        if timing is None:
+            return t0
+        torch.cuda.synchronize(dev)
+        t1 = clock()
+        timing[name] = timing.get(name, 0.0) + (t1 - t0)
+        return t1
+
+    t = clock()
+    for ply in range(max_turns + 1):
+        if len(live) == 0:
+            break
+        mine = learner_black[live] == (ply % 2 == 0)
+        order = np.concatenate([live[mine], live[~mine]])           # the learner's rows first
+        nl, n = int(mine.sum()), len(order)
+        recs = np.ascontiguousarray(pos[order])
+        stage[:16 * n].view(np.int32)[:] = counters(order, ply, iteration, epoch).reshape(-1)
+        features_batch(recs, stage[16 * n:].ctypes.data)
+        t = lap("host", t)
+        d = staging[:(16 + PLANE_BYTES) * n].to(dev, non_blocking=True)
+        ctr = d[:16 * n].view(torch.int32).view(n, 4)
+        planes = d[16 * n:].view(n, 27, 9, 9)
+        logits = []
+        if nl:
+            logits.append(learner.eval_device(planes[:nl], logits=True, probs=False, value=False)["logits"])
+        if n > nl:
+            logits.append(opponent.eval_device(planes[nl:], logits=True, probs=False, value=False)["logits"])
+        logits = logits[0] if len(logits) == 1 else torch.cat(logits)
+        t = lap("engine", t)
+        d_moves, d_logp = T.sample_moves(logits, planes, key, ctr)
+        moves = d_moves.cpu().numpy()
+        t = lap("sampler", t)
+        base = recs.ctypes.data
+        for r, (addr, mv) in enumerate(zip(range(base, base + POS_BYTES * n, POS_BYTES), moves.tolist())):
+            if mv >= 0 and play(addr, mv):
+                raise RuntimeError(f"game {order[r]} ply {ply}: sampled move {mv} is illegal; the legal plane and "
+                                   "the rules disagree")
+        pos[order] = recs
+        ok = moves >= 0
+        hist[order[ok], ply] = moves[ok]
+        length[order[ok]] += 1
+        if nl:
+            keep = ok[:nl]
+            if keep.all():
+                rows_planes.append(planes[:nl])
+                rows_moves.append(d_moves[:nl])
+                rows_logp.append(d_logp[:nl])
+            else:
+                k = torch.from_numpy(np.nonzero(keep)[0]).to(dev)
+                rows_planes.append(planes[:nl].index_select(0, k))
+                rows_moves.append(d_moves[:nl].index_select(0, k))
+                rows_logp.append(d_logp[:nl].index_select(0, k))
+            rows_game.append(order[:nl][keep])
+        live = np.sort(order[ok])                                   # turn > max_turns ends the game before its move
+        t = lap("host", t)
+
+    out = Playouts()
+    out.moves, out.length, out.learner_black = hist, length, learner_black
+    scores = np.array([lib.bk_pos_area_score(ctypes.cast(pos[g].ctypes.data, ctypes.POINTER(go.Pos)), KOMI)
+                       for g in range(G)], np.float64)
+    out.black_wins = scores > 0
+    out.reward = np.where(out.black_wins == learner_black, 1.0, -1.0).astype(np.float32)
+    if rows_game:
+        out.planes = torch.cat(rows_planes)
+        out.played = torch.cat(rows_moves).long()
+        out.logp = torch.cat(rows_logp)
+        out.row_game = np.concatenate(rows_game).astype(np.int64)
+    else:
+        out.planes = torch.empty((0, 27, 9, 9), dtype=torch.uint8, device=dev)
+        out.played = torch.empty((0,), dtype=torch.int64, device=dev)
+        out.logp = torch.empty((0,), dtype=torch.float32, device=dev)
+        out.row_game = np.zeros(0, np.int64)
+    lap("host", t)
+    return out
+
+
+# ---- the learner -------------------------------------------------------------------------------------------------------
+def played_logp(net, planes, played):
+    """log pi(a|s) of the rows through the network (eval mode: the function the engine sampled from)."""
+    logits = net(planes)
+    return F.log_softmax(logits, dim=1).gather(1, played.reshape(-1, 1)).reshape(-1)
+
+
+def update(net, opt, games, n_batches, batch_size, reward_override=None):
+    """One AdamW step per batch, in batch order, on that batch's REINFORCE loss; -> the losses (floats).
+    A batch without rows takes no step.  reward_override: +1 / -1 for every game (tests)."""
+    net.eval()
+    dev = games.planes.device
+    reward = games.reward if reward_override is None else np.full_like(games.reward, reward_override)
+    losses = []
+    for w in range(n_batches):
+        idx, gl = games.batch_rows(w, batch_size)
+        if len(idx) == 0:
+            losses.append(0.0)
+            continue
+        r = torch.from_numpy(np.ascontiguousarray(reward[w * batch_size:(w + 1) * batch_size])).to(dev)
+        opt.zero_grad(set_to_none=True)
+        loss = 0.0
+        for s in range(0, len(idx), UPDATE_CHUNK):     # the loss is a sum over rows: gradients of chunks add up
+            i = idx[s:s + UPDATE_CHUNK]
+            part = reinforce_loss(played_logp(net, games.planes.index_select(0, i), games.played.index_select(0, i)),
+                                  gl[s:s + UPDATE_CHUNK], r, batch_size)
+            part.backward()
+            loss += float(part.detach())
+        opt.step()
+        losses.append(loss)
+    return losses
+
+
+def wins_per_batch(games, n_batches, batch_size):
+    return [int((games.reward[w * batch_size:(w + 1) * batch_size] > 0).sum()) for w in range(n_batches)]
+
+
+def policy_engine(sd, device_id, max_batch):
+    from .engine import LeafEngine
+    return LeafEngine(sd, None, device_id=device_id, max_batch=max_batch, precision="f32")
+
+
+def engine_weights(net):
+    """The trainable net's state_dict in the form LeafEngine.set_weights takes."""
+    return {k: v.detach() for k, v in net.state_dict().items()}
+
+
+def run_epoch(net, opt, learner_eng, opp_eng, n_iters, n_batches, batch_size, seed, epoch, log=None):
+    """n_iters iterations: play, update, hand the new weights to the learner's engine.  -> wins per batch, in order."""
+    wins = []
+    for it in range(n_iters):
+        t0 = time.perf_counter()
+        games = play_games(learner_eng, opp_eng, n_batches, batch_size, seed, iteration=it, epoch=epoch)
+        losses = update(net, opt, games, n_batches, batch_size)
+        learner_eng.set_weights(engine_weights(net))
+        w = wins_per_batch(games, n_batches, batch_size)
+        wins += w
+        if log:
+            log({"iteration": it, "wins": sum(w), "games": n_batches * batch_size, "rows": len(games.row_game),
+                 "mean_loss": sum(losses) / len(losses), "seconds": time.perf_counter() - t0})
+    return wins
+
+
+def save_checkpoint(path, net, opt):
+    """The reference's checkpoint: model_state_dict and optimizer_state_dict (selfplay.py:207-208)."""
+    torch.save({"model_state_dict": {k: v.detach().cpu() for k, v in net.state_dict().items()},
+                "optimizer_state_dict": opt.state_dict()}, path)
+
+
+def _parse(argv):
+    ap = argparse.ArgumentParser(description="REINFORCE against a pool of earlier policies on the MI355X "
+                                             "(the reference's bin/selfplay.py)")
+    ap.add_argument("-w", dest="w", metavar="PATH", default=os.path.abspath(os.path.join("..", "data", "weights")),
+                    help="the pool: policy_<id>.pt / .bkw files")
+    ap.add_argument("-e", dest="e", metavar="E", type=int, default=1, help="number of epochs")
+    ap.add_argument("-n", dest="n", metavar="N", type=int, default=64, help="iterations per epoch")
+    ap.add_argument("-b", dest="b", metavar="B", type=int, default=16, help="games per batch")
+    ap.add_argument("--workers", metavar="W", type=int, default=16,
+                    help="batches per iteration (even: learner black, odd: white), one AdamW step each")
+    ap.add_argument("-f", dest="f", metavar="PATH", default=os.path.join(os.getcwd(), "RL_stats.txt"),
+                    help="file the statistics are appended to")
+    ap.add_argument("--lr", type=float, default=1e-5)
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--opponent", default=None, help="pool id of the opponent, or 'random' (default: policy_0 if any)")
+    ap.add_argument("--device", type=int, default=0)
+    args = ap.parse_args(argv)
+    for flag, v in (("-e", args.e), ("-n", args.n), ("-b", args.b), ("--workers", args.workers)):
+        if v < 1:
+            ap.error(f"{flag} must be at least 1")
+    if args.b * args.workers > 65536:
+        ap.error("-b times --workers must be at most 65536 games")
+    if args.opponent is not None and args.opponent != "random" and not re.fullmatch(r"\d+", args.opponent):
+        ap.error("--opponent must be a pool id or 'random'")
+    if not (0 <= args.seed < 2 ** 64):
+        ap.error("--seed must be an unsigned 64-bit integer")
+    if not os.path.isdir(args.w):
+        ap.error(f"-w {args.w}: not a directory")
+    return args
+
+
+def main(argv=None):
+    from .train import TrainablePolicyNet, load_weights
+
+    args = _parse(argv)
+    pool = policy_pool(args.w)
+    n = learner_id(pool, args.w)
+    dev = torch.device("cuda", args.device)
+    torch.cuda.set_device(dev)
+    G = args.b * args.workers
+    net = TrainablePolicyNet.from_state_dict(load_weights(pool[n]), device=dev).eval()
+    opt = torch.optim.AdamW(net.parameters(), lr=args.lr)
+    if pool[n].endswith(".pt"):
+        ck = torch.load(pool[n], map_location="cpu")
+        if isinstance(ck, dict) and "optimizer_state_dict" in ck:
+            opt.load_state_dict(ck["optimizer_state_dict"])
+    learner_eng = policy_engine(engine_weights(net), args.device, G)
+    print(json.dumps({"pool": sorted(pool), "learner": n, "games_per_iteration": G}), flush=True)
+    try:
+        for _ in range(args.e):
+            opp = choose_opponent(pool, n, args.seed, n, args.opponent)
+            out = os.path.join(args.w, f"policy_{n + 1}.pt")
+            if os.path.exists(out):
+                raise SystemExit(f"{out} exists: the pool must be numbered 0..{n} with nothing above")
+            opp_eng = policy_engine(load_weights(pool[opp]), args.device, G)
+            t0 = time.perf_counter()
+            try:
+                wins = run_epoch(net, opt, learner_eng, opp_eng, args.n, args.workers, args.b, args.seed, n,
+                                 log=lambda d: print(json.dumps(d), flush=True))
+            finally:
+                opp_eng.close()
+            dt = time.perf_counter() - t0
+            with open(args.f, "a+") as f:
+                f.write("\n".join(stats_lines(n, opp, args.b, args.n, wins)) + "\n")
+            save_checkpoint(out, net, opt)
+            print(json.dumps({"epoch": n, "opponent": opp, "wins": sum(wins), "games": len(wins) * args.b,
+                              "games_per_s": len(wins) * args.b / dt, "seconds": dt, "checkpoint": out}), flush=True)
+            n += 1
+            pool[n] = out
+    finally:
+        learner_eng.close()
+
+
+if __name__ == "__main__":
+    main()

@@ -6,7 +6,8 @@
 closes the loop `selfplay --out r/` -> `train --records r/` -> `selfplay --policy out/policy_1.pt`.
 
 The trunk (seven conv -> BatchNorm2d -> ReLU blocks) runs on the HIP kernels of libbktrain.so (bokego_amd/_trainlib.py),
-one torch.autograd.Function per block; torch's own convolution never runs on it.  The heads -- the untied-bias 1x1
+one torch.autograd.Function per block (train-mode BatchNorm; in eval mode with gradients enabled, BatchNorm with its
+running statistics frozen, as REINFORCE needs); torch's own convolution never runs on it.  The heads -- the untied-bias 1x1
 conv.21 (a sum over channels here), the value net's bn / lin1 / lin_bn / lin2 / tanh -- the losses and Adam are torch
 ops on the device, about 0.02 % of the FLOPs.  Parameter and buffer names are the reference's state_dict names
 (bokego/nnet.py:31-57, 73-113), so state_dict() is a reference checkpoint: HipPolicyNet.load_state_dict,
@@ -49,6 +50,29 @@ class _TrunkBlock(torch.autograd.Function):
         dw, db = T.conv_wgrad(x, dz, w.shape)
         dx = T.conv_dgrad(dz, w.detach().contiguous()) if ctx.needs_input_grad[0] else None
         return dx, dw, db, dgamma, dbeta, None, None, None, None, None
+
+
+class _TrunkBlockEval(torch.autograd.Function):
+    """conv (k = 5 or 3, pad k//2) -> eval-mode BatchNorm2d (running statistics, left unchanged) -> ReLU, with the
+    gradient of that function: the same kernels and bits forward as the no-grad eval path."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, gamma, beta, running_mean, running_var, eps):
+        x = x.contiguous()
+        z = T.conv_forward(x, w.detach().contiguous(), b.detach().contiguous())
+        y = T.bn_relu_eval(z, gamma.detach().contiguous(), beta.detach().contiguous(), running_mean, running_var, eps)
+        ctx.save_for_backward(x, w, z, y, gamma, running_mean, running_var)
+        ctx.eps = eps
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w, z, y, gamma, running_mean, running_var = ctx.saved_tensors
+        dz, dgamma, dbeta = T.bn_relu_eval_backward(dy.contiguous(), y, z, gamma.detach().contiguous(), running_mean,
+                                                    running_var, ctx.eps)
+        dw, db = T.conv_wgrad(x, dz, w.shape)
+        dx = T.conv_dgrad(dz, w.detach().contiguous()) if ctx.needs_input_grad[0] else None
+        return dx, dw, db, dgamma, dbeta, None, None, None
 
 
 class _UntiedBias1x1(torch.nn.Module):
@@ -122,12 +146,16 @@ class _Trainable(torch.nn.Module):
         if not x.is_cuda:
             raise ValueError("the trainable nets run on the GPU: move the planes there first")
         h = x.float().contiguous()
+        grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.conv.parameters())
         for l in range(N_TRUNK):
             conv, bn = self.conv[3 * l], self.conv[3 * l + 1]
             if self.training:
                 h = _TrunkBlock.apply(h, conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var,
                                       bn.num_batches_tracked, bn.momentum, bn.eps)
-            else:  # eval mode: running statistics, no autograd through the trunk
+            elif grad:  # eval mode with gradients (REINFORCE): frozen running statistics, differentiated
+                h = _TrunkBlockEval.apply(h, conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean,
+                                          bn.running_var, bn.eps)
+            else:  # eval mode under no_grad: running statistics, no autograd
                 z = T.conv_forward(h, conv.weight.detach().contiguous(), conv.bias.detach().contiguous())
                 h = T.bn_relu_eval(z, bn.weight.detach().contiguous(), bn.bias.detach().contiguous(), bn.running_mean,
                                    bn.running_var, bn.eps)

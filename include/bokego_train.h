@@ -1,6 +1,7 @@
 /*
  * bokego_train.h -- C ABI of the training kernels (libbktrain.so): the trunk of the reference's PolicyNet / ValueNet
- * (bokego/nnet.py:31-57, 73-113) with gradients, for bokego_amd/train.py.
+ * (bokego/nnet.py:31-57, 73-113) with gradients, for bokego_amd/train.py, and the move sampler of the REINFORCE
+ * playouts (bokego_amd/reinforce.py).
  *
  * Conventions:
  *   - Stateless.  No entry point allocates device memory or keeps anything between calls: every buffer is a device
@@ -24,9 +25,10 @@
 extern "C" {
 #endif
 
-#define BKT_ABI_VERSION 1
+#define BKT_ABI_VERSION 2
 #define BKT_MAX_BATCH 65536
 #define BKT_COUT 128
+#define BKT_MAX_SAMPLE_ROWS (1 << 24)
 
 typedef enum bkt_status {
     BKT_OK = 0,
@@ -92,6 +94,28 @@ int bkt_bn_relu_backward(const float *dy, const float *y, const float *x, const 
 /* Eval mode: y = relu((x - running_mean) / sqrt(running_var + eps) * gamma + beta). */
 int bkt_bn_relu_eval(const float *x, const float *gamma, const float *beta, const float *running_mean,
                      const float *running_var, float eps, float *y, int batch, int channels, void *stream);
+
+/* Gradients of bkt_bn_relu_eval (frozen statistics): m = [y > 0], invstd = 1/sqrt(running_var + eps),
+ * dx = dy * m * gamma * invstd, dbeta = sum dy * m, dgamma = sum dy * m * (x - running_mean) * invstd.
+ * y is bkt_bn_relu_eval's output, x its input.  The sums use per-slice double partials added in slice order, as
+ * bkt_bn_relu_backward does, in a bkt_bn_workspace(batch, channels) scratch.  Writes dx [B, channels, 9, 9],
+ * dgamma and dbeta [channels]. */
+int bkt_bn_relu_eval_backward(const float *dy, const float *y, const float *x, const float *gamma,
+                              const float *running_mean, const float *running_var, float eps, float *dx, float *dgamma,
+                              float *dbeta, void *workspace, size_t workspace_bytes, int batch, int channels,
+                              void *stream);
+
+/* ---- move sampling (bokego_amd/reinforce.py) ------------------------------------------------------------------------ */
+
+/* One wave64 per row b of logits [B, 81]: p_i = exp(x_i - max x), S = sum p (the inclusive prefix at i = 80).
+ * A Philox4x32-10 draw with key (seed low word, seed high word) and counter counters[b] = (c0, c1, c2, c3) gives
+ * u = (x0 >> 8) * 2^-24 in [0, 1); the move is the first i whose inclusive prefix of p exceeds u * S.  Legality is plane
+ * 5 of the uint8 feature planes [B, 27, 9, 9] (nnet.features' "legal" plane): a sample that is not legal is replaced by
+ * the legal point of the largest logit (lowest index on ties), and a row with no legal point gets -1.
+ * moves [B] (int32) and logp [B] = log softmax(x) at the move (0 where the move is -1).
+ * 1 <= B <= BKT_MAX_SAMPLE_ROWS (rows are independent: no trunk batch limit applies). */
+int bkt_sample_moves(const float *logits, const uint8_t *planes, int batch, uint64_t seed, const uint32_t *counters,
+                     int32_t *moves, float *logp, void *stream);
 
 #ifdef __cplusplus
 }
