@@ -11,7 +11,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libbktrain.so")
 
-BKT_ABI_VERSION = 2
+BKT_ABI_VERSION = 3
 COUT = 128
 BN_EPS = 1e-5
 BN_MOMENTUM = 0.1
@@ -33,7 +33,10 @@ SYMBOLS = {
     "bkt_bn_relu_eval": (_I, [_P, _P, _P, _P, _P, _F, _P, _I, _I, _P]),
     "bkt_bn_relu_eval_backward": (_I, [_P, _P, _P, _P, _P, _P, _F, _P, _P, _P, _P, _Z, _I, _I, _P]),
     "bkt_sample_moves": (_I, [_P, _P, _I, _U64, _P, _P, _P, _P]),
+    "bkt_play_moves": (_I, [_P, _P, _I, _P, _P, _P]),
 }
+MAX_BATCH = 65536          # BKT_MAX_BATCH
+POS_BYTES = 192            # sizeof(bk_pos)
 
 _lib = None
 
@@ -226,3 +229,19 @@ def sample_moves(logits, planes, seed, counters):
                                    _dev(moves, "moves", dtype=torch.int32), _dev(logp, "logp"), _stream(logits)),
            "bkt_sample_moves")
     return moves, logp
+
+
+def play_moves(pos, moves, planes=None):
+    """The Go rules on the device, in place: pos uint8 [B,192] (bk_pos records), moves int32 [B] (< 0: leave the row
+    alone) -> status int32 [B] (0 or BK_ILLEGAL_*; an illegal row is untouched).  planes: None, or uint8 [B,27,9,9]
+    that receives the features of every record as it stands afterwards (bk_features_batch_u8's)."""
+    if pos.dim() != 2 or pos.shape[1] != POS_BYTES:
+        raise ValueError(f"pos must be [B, {POS_BYTES}], got {tuple(pos.shape)}")
+    B = int(pos.shape[0])
+    if not 1 <= B <= MAX_BATCH:
+        raise ValueError(f"batch must be 1..{MAX_BATCH}, got {B}")
+    status = torch.empty((B,), dtype=torch.int32, device=pos.device)
+    pp = None if planes is None else _dev(planes, "planes", (B, 27, 9, 9), torch.uint8)
+    _check(load().bkt_play_moves(_dev(pos, "pos", dtype=torch.uint8), _dev(moves, "moves", (B,), torch.int32), B,
+                                 _dev(status, "status", dtype=torch.int32), pp, _stream(pos)), "bkt_play_moves")
+    return status

@@ -2,8 +2,10 @@
 
     python -m bokego_amd.train --records r/ --net policy|value|both [-c CKPT [CKPT]] [--init-trunk-from policy.pt]
                                -e EPOCHS -b BATCH --lr LR --seed S --out DIR
+    python -m bokego_amd.train --values values.csv [...] --net value [--records r/] ...
 
-closes the loop `selfplay --out r/` -> `train --records r/` -> `selfplay --policy out/policy_1.pt`.
+closes the loop `selfplay --out r/` -> `train --records r/` -> `selfplay --policy out/policy_1.pt`, and
+`genvals -o values.csv` -> `train --values values.csv --net value` -> `selfplay --value out/value_1.pt`.
 
 The trunk (seven conv -> BatchNorm2d -> ReLU blocks) runs on the HIP kernels of libbktrain.so (bokego_amd/_trainlib.py),
 one torch.autograd.Function per block (train-mode BatchNorm; in eval mode with gradients enabled, BatchNorm with its
@@ -312,6 +314,49 @@ class RecordDataset:
             yield (x, p, torch.from_numpy(self.has_policy[idx]).to(device), torch.from_numpy(self.value[idx]).to(device))
 
 
+class ValueRecordDataset(RecordDataset):
+    """The rows of genvals CSV files (board,ko,last,turn,val), value targets only.
+
+    planes     uint8 [N,27,9,9]  bk_pos_from_board(board, ko, last, turn) + bk_pos_features_u8(fresh=1): the reference's
+                                 Game(board=...), whose liberties are recomputed from the board
+    policy     float32 [N,81]    zero; has_policy is False everywhere
+    value      float32 [N]       val (+1 / -1 from the side to move)
+    """
+
+    def __init__(self, paths, augment=False, seed=0):
+        from .genvals import read_rows
+
+        if isinstance(paths, str):
+            paths = [paths]
+        self.files = list(paths)
+        self.augment, self.seed = bool(augment), int(seed)
+        planes, val, self.game_of = [], [], []
+        for fi, path in enumerate(self.files):
+            for i, (board, ko, last, turn, v) in enumerate(read_rows(path)):
+                if v not in (1, -1):
+                    raise ValueError(f"{path}: row {i}: val must be +1 or -1, got {v}")
+                g = go.Game(board=board, ko=None if ko < 0 else ko, last_move=last, turn=turn)
+                planes.append(g.features_u8(fresh=True))
+                val.append(float(v))
+                self.game_of.append((fi, i, -1))
+        self.planes = np.stack(planes) if planes else np.zeros((0, 27, 9, 9), np.uint8)
+        self.policy = np.zeros((len(val), 81), np.float32)
+        self.has_policy = np.zeros(len(val), bool)
+        self.value = np.array(val, np.float32)
+
+
+def merge_datasets(first, *rest):
+    """One dataset holding the positions of all, in order; batches() as first's (augment, seed)."""
+    out = object.__new__(RecordDataset)
+    parts = (first,) + rest
+    out.files = [f for d in parts for f in d.files]
+    out.augment, out.seed = first.augment, first.seed
+    out.game_of = [g for d in parts for g in d.game_of]
+    for name in ("planes", "policy", "has_policy", "value"):
+        setattr(out, name, np.concatenate([getattr(d, name) for d in parts]))
+    return out
+
+
 # ---- losses and the training loop ---------------------------------------------------------------------------------
 def policy_loss(logits, target, mask=None):
     """-sum pi * log_softmax(logits), averaged over the positions with a target (the reference's CrossEntropyLoss
@@ -339,7 +384,9 @@ def _is_value_dict(sd):
 
 def main(argv=None):
     ap = argparse.ArgumentParser(description="Train the policy / value nets from self-play records on the MI355X")
-    ap.add_argument("--records", nargs="+", required=True, help="directories (searched for games.json) or files")
+    ap.add_argument("--records", nargs="+", default=None, help="directories (searched for games.json) or files")
+    ap.add_argument("--values", nargs="+", default=None,
+                    help="genvals CSV files: value targets, trained together with those of --records")
     ap.add_argument("--net", choices=["policy", "value", "both"], default="both")
     ap.add_argument("-c", dest="checkpoint", nargs="+", default=[],
                     help="resume from policy_N.pt / value_N.pt (model + optimizer + epoch; a bare state_dict or a .bkw "
@@ -359,11 +406,20 @@ def main(argv=None):
         ap.error("-b must be at least 2: BatchNorm in train mode needs a batch")
     if args.epochs < 1:
         ap.error("-e must be at least 1")
+    if not args.records and not args.values:
+        ap.error("give --records and/or --values")
+    if args.values and not args.records and args.net != "value":
+        ap.error("--values holds value targets only: without --records use --net value")
 
     torch.manual_seed(args.seed)
     dev = torch.device("cuda", args.device)
     torch.cuda.set_device(dev)
-    data = RecordDataset(args.records, augment=args.augment, seed=args.seed)
+    if args.values:
+        parts = [RecordDataset(args.records, augment=args.augment, seed=args.seed)] if args.records else []
+        parts.append(ValueRecordDataset(args.values, augment=args.augment, seed=args.seed))
+        data = merge_datasets(*parts)
+    else:
+        data = RecordDataset(args.records, augment=args.augment, seed=args.seed)
     if len(data) < 2:
         raise SystemExit("fewer than 2 positions in the records")
     names = ["policy", "value"] if args.net == "both" else [args.net]
@@ -399,7 +455,7 @@ def main(argv=None):
         t0 = time.perf_counter()
         for x, p, has, v in data.batches(args.batch, epoch=start[names[0]] + e, device=dev):
             losses = {}
-            if "policy" in nets:
+            if "policy" in nets and not (args.values and not bool(has.any())):  # a batch of --values rows only
                 losses["policy"] = policy_loss(nets["policy"](x), p, has)
             if "value" in nets:
                 losses["value"] = value_loss(nets["value"](x), v)

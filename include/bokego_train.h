@@ -1,7 +1,7 @@
 /*
  * bokego_train.h -- C ABI of the training kernels (libbktrain.so): the trunk of the reference's PolicyNet / ValueNet
- * (bokego/nnet.py:31-57, 73-113) with gradients, for bokego_amd/train.py, and the move sampler of the REINFORCE
- * playouts (bokego_amd/reinforce.py).
+ * (bokego/nnet.py:31-57, 73-113) with gradients, for bokego_amd/train.py, the move sampler of the REINFORCE
+ * playouts (bokego_amd/reinforce.py), and the Go rules of the device-resident playouts (bokego_amd/genvals.py).
  *
  * Conventions:
  *   - Stateless.  No entry point allocates device memory or keeps anything between calls: every buffer is a device
@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define BKT_ABI_VERSION 2
+#define BKT_ABI_VERSION 3
 #define BKT_MAX_BATCH 65536
 #define BKT_COUT 128
 #define BKT_MAX_SAMPLE_ROWS (1 << 24)
@@ -116,6 +116,17 @@ int bkt_bn_relu_eval_backward(const float *dy, const float *y, const float *x, c
  * 1 <= B <= BKT_MAX_SAMPLE_ROWS (rows are independent: no trunk batch limit applies). */
 int bkt_sample_moves(const float *logits, const uint8_t *planes, int batch, uint64_t seed, const uint32_t *counters,
                      int32_t *moves, float *logp, void *stream);
+
+/* ---- the Go rules on the device (bokego_amd/genvals.py; bk_playout.hip) --------------------------------------------- */
+
+/* For each row b < batch: if moves[b] >= 0, play it on the 192-byte record pos[b] (bk_pos, include/bokego_go.h) and
+ * refresh its liberty cache, in place; status[b] = 0 or the BK_ILLEGAL_* code (record untouched).  moves[b] < 0: the
+ * record is untouched, status[b] = 0.  If planes != NULL, planes[b] = the 27 u8 planes of the record as it stands after
+ * the call (the ones bk_features_batch_u8 computes from it).  1 <= batch <= BKT_MAX_BATCH.  Stateless, enqueued on
+ * `stream`, as every bkt_* call.
+ * Byte identity with the host: every record afterwards equals what bk_pos_play(p, m) followed by
+ * bk_pos_liberties(p, tmp) leaves, all 192 bytes (board, libs, libs_valid, ko, last move, turn, hash, reserved). */
+int bkt_play_moves(void *pos, const int32_t *moves, int batch, int32_t *status, uint8_t *planes, void *stream);
 
 #ifdef __cplusplus
 }
