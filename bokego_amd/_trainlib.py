@@ -11,7 +11,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libbktrain.so")
 
-BKT_ABI_VERSION = 3
+BKT_ABI_VERSION = 4
 COUT = 128
 BN_EPS = 1e-5
 BN_MOMENTUM = 0.1
@@ -27,6 +27,13 @@ SYMBOLS = {
     "bkt_conv_dgrad": (_I, [_P, _P, _P, _I, _P]),
     "bkt_conv_wgrad_workspace": (_Z, [_I, _I, _I]),
     "bkt_conv_wgrad": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _Z, _P]),
+    "bkt_conv_packed_elems_bf16": (_Z, [_I, _I]),
+    "bkt_conv_pack_bf16": (_I, [_P, _I, _I, _P, _P]),
+    "bkt_conv_forward_bf16": (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),
+    "bkt_conv_pack_dgrad_bf16": (_I, [_P, _P, _P]),
+    "bkt_conv_dgrad_bf16": (_I, [_P, _P, _P, _I, _P]),
+    "bkt_conv_wgrad_workspace_bf16": (_Z, [_I, _I, _I]),
+    "bkt_conv_wgrad_bf16": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _Z, _P]),
     "bkt_bn_workspace": (_Z, [_I, _I]),
     "bkt_bn_relu_train": (_I, [_P, _P, _P, _P, _P, _P, _F, _F, _P, _P, _P, _P, _Z, _I, _I, _P]),
     "bkt_bn_relu_backward": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _I, _I, _P]),
@@ -36,6 +43,7 @@ SYMBOLS = {
     "bkt_play_moves": (_I, [_P, _P, _I, _P, _P, _P]),
 }
 MAX_BATCH = 65536          # BKT_MAX_BATCH
+PRECISIONS = ("fp32", "bf16")
 POS_BYTES = 192            # sizeof(bk_pos)
 
 _lib = None
@@ -92,56 +100,96 @@ def _batch(x, c):
     return int(x.shape[0])
 
 
-def conv_pack(w):
-    """[128, Cin, k, k] -> [Cin*k*k, 128], the forward operand."""
+def _precision(precision):
+    """True for "bf16", False for "fp32": the mixed-precision kernels (bf16 GEMM operands rounded once to nearest even,
+    fp32 accumulation, fp32 tensors; include/bokego_train.h) or the fp32 ones."""
+    if precision not in PRECISIONS:
+        raise ValueError(f"precision must be one of {PRECISIONS}, got {precision!r}")
+    return precision == "bf16"
+
+
+def _packed_bf16(cin, k, device):
+    n = load().bkt_conv_packed_elems_bf16(cin, k)
+    if n == 0:
+        raise ValueError(f"unsupported convolution: Cin={cin} k={k}")
+    return torch.empty((n,), dtype=torch.int16, device=device)  # bf16 bit patterns in a layout private to the library
+
+
+def conv_pack(w, precision="fp32"):
+    """[128, Cin, k, k] -> the forward operand: [Cin*k*k, 128] fp32, or with precision="bf16" the library's packed bf16
+    operand (int16 bit patterns, flat)."""
+    bf16 = _precision(precision)
     cin, k = _conv_shape(w)
+    if bf16:
+        wt = _packed_bf16(cin, k, w.device)
+        _check(load().bkt_conv_pack_bf16(_dev(w, "w"), cin, k, _dev(wt, "wt", dtype=torch.int16), _stream(w)),
+               "bkt_conv_pack_bf16")
+        return wt
     wt = torch.empty((cin * k * k, COUT), dtype=torch.float32, device=w.device)
     _check(load().bkt_conv_pack(_dev(w, "w"), cin, k, _dev(wt, "wt"), _stream(w)), "bkt_conv_pack")
     return wt
 
 
-def conv_forward(x, w, bias=None, wt=None):
-    """conv2d(x, w, bias, padding=k//2) on the 9x9 board; wt: conv_pack(w) when the caller already has it."""
+def conv_forward(x, w, bias=None, wt=None, precision="fp32"):
+    """conv2d(x, w, bias, padding=k//2) on the 9x9 board; wt: conv_pack(w, precision) when the caller already has it."""
+    bf16 = _precision(precision)
     cin, k = _conv_shape(w)
     B = _batch(x, cin)
-    wt = conv_pack(w) if wt is None else wt
+    wt = conv_pack(w, precision) if wt is None else wt
     y = torch.empty((B, COUT, 9, 9), dtype=torch.float32, device=x.device)
     bp = None if bias is None else _dev(bias, "bias", (COUT,))
+    if bf16:
+        n = load().bkt_conv_packed_elems_bf16(cin, k)
+        _check(load().bkt_conv_forward_bf16(_dev(x, "x"), _dev(wt, "wt", (n,), torch.int16), bp, _dev(y, "y"), B, cin, k,
+                                            _stream(x)), "bkt_conv_forward_bf16")
+        return y
     _check(load().bkt_conv_forward(_dev(x, "x"), _dev(wt, "wt", (cin * k * k, COUT)), bp, _dev(y, "y"), B, cin, k,
                                    _stream(x)), "bkt_conv_forward")
     return y
 
 
-def conv_dgrad(dy, w):
+def conv_dgrad(dy, w, precision="fp32"):
     """dL/dx of the 3x3 128->128 convolution with weights w, from dy = dL/dy."""
+    bf16 = _precision(precision)
     cin, k = _conv_shape(w)
     if (cin, k) != (COUT, 3):
         raise ValueError("the input gradient is built for the 3x3 128->128 convolution only")
     B = _batch(dy, COUT)
     lib, s = load(), _stream(dy)
+    dx = torch.empty_like(dy)
+    if bf16:
+        wd = _packed_bf16(COUT, 3, dy.device)
+        _check(lib.bkt_conv_pack_dgrad_bf16(_dev(w, "w"), _dev(wd, "wt_dgrad", dtype=torch.int16), s),
+               "bkt_conv_pack_dgrad_bf16")
+        _check(lib.bkt_conv_dgrad_bf16(_dev(dy, "dy"), _dev(wd, "wt_dgrad", dtype=torch.int16), _dev(dx, "dx"), B, s),
+               "bkt_conv_dgrad_bf16")
+        return dx
     wd = torch.empty((COUT * 9, COUT), dtype=torch.float32, device=dy.device)
     _check(lib.bkt_conv_pack_dgrad(_dev(w, "w"), _dev(wd, "wt_dgrad"), s), "bkt_conv_pack_dgrad")
-    dx = torch.empty_like(dy)
     _check(lib.bkt_conv_dgrad(_dev(dy, "dy"), _dev(wd, "wt_dgrad"), _dev(dx, "dx"), B, s), "bkt_conv_dgrad")
     return dx
 
 
-def conv_wgrad(x, dy, w_shape, need_bias=True):
+def conv_wgrad(x, dy, w_shape, need_bias=True, precision="fp32"):
     """(dL/dw [128, Cin, k, k], dL/dbias [128] or None) from the layer input x and dy = dL/dy."""
+    bf16 = _precision(precision)
     cin, k = int(w_shape[1]), int(w_shape[2])
     B = _batch(x, cin)
     _batch(dy, COUT)
     if dy.shape[0] != B:
         raise ValueError("x and dy have different batches")
     lib = load()
-    nbytes = lib.bkt_conv_wgrad_workspace(B, cin, k)
+    workspace, wgrad = ((lib.bkt_conv_wgrad_workspace_bf16, lib.bkt_conv_wgrad_bf16) if bf16 else
+                        (lib.bkt_conv_wgrad_workspace, lib.bkt_conv_wgrad))
+    nbytes = workspace(B, cin, k)
     if nbytes == 0:
         raise ValueError(f"unsupported convolution: B={B} Cin={cin} k={k}")
     ws = torch.empty((nbytes // 8,), dtype=torch.float64, device=x.device)  # 8-byte aligned: it holds double partials
     dw = torch.empty((COUT, cin, k, k), dtype=torch.float32, device=x.device)
     db = torch.empty((COUT,), dtype=torch.float32, device=x.device) if need_bias else None
-    _check(lib.bkt_conv_wgrad(_dev(x, "x"), _dev(dy, "dy"), _dev(dw, "dw"), None if db is None else _dev(db, "db"), B,
-                              cin, k, _dev(ws, "workspace", dtype=torch.float64), nbytes, _stream(x)), "bkt_conv_wgrad")
+    _check(wgrad(_dev(x, "x"), _dev(dy, "dy"), _dev(dw, "dw"), None if db is None else _dev(db, "db"), B, cin, k,
+                 _dev(ws, "workspace", dtype=torch.float64), nbytes, _stream(x)),
+           "bkt_conv_wgrad_bf16" if bf16 else "bkt_conv_wgrad")
     return dw, db
 
 

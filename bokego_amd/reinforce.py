@@ -1,7 +1,7 @@
 """REINFORCE on policy-vs-policy games against a pool of earlier policies (the reference's bin/selfplay.py:59-208).
 
     python -m bokego_amd.reinforce -w WEIGHTS_DIR [-e E] [-n N] [-b B] [--workers W] [-f STATS] [--lr 1e-5] [--seed S]
-                                   [--opponent ID|random] [--device D]
+                                   [--opponent ID|random] [--device D] [--precision fp32|bf16]
 
 The pool is the policy_<id>.pt / .bkw files of -w.  With n = (number of ids) - 1, policy_n is trained; each epoch it
 plays an opponent from the pool (policy_0 when it exists), writes policy_{n+1}.pt and three lines of statistics, and n
@@ -19,6 +19,10 @@ The update differentiates the network that sampled the moves: the eval-mode Trai
 running statistics frozen (train._TrunkBlockEval), which is the function the engine computes with the statistics
 folded in.  Randomness comes only from Philox4x32-10 keyed by --seed with counter (game, ply, iteration, epoch), so
 the same seed and pool give the same checkpoints bit for bit.  DESIGN 12 lists where this departs from the reference.
+
+--precision bf16 puts the update's trunk convolutions on bf16 operands (train._Trainable.precision).  The
+playouts keep sampling from the fp32 engine, so the update then differentiates a function whose logits differ slightly
+from the ones the moves were sampled from.
 """
 import argparse
 import ctypes
@@ -405,6 +409,9 @@ def _parse(argv):
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--opponent", default=None, help="pool id of the opponent, or 'random' (default: policy_0 if any)")
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--precision", choices=list(T.PRECISIONS), default="fp32",
+                    help="bf16: the update's trunk convolutions on bf16 operands with fp32 accumulation (the playouts "
+                         "stay on the fp32 engine)")
     args = ap.parse_args(argv)
     for flag, v in (("-e", args.e), ("-n", args.n), ("-b", args.b), ("--workers", args.workers)):
         if v < 1:
@@ -429,7 +436,7 @@ def main(argv=None):
     dev = torch.device("cuda", args.device)
     torch.cuda.set_device(dev)
     G = args.b * args.workers
-    net = TrainablePolicyNet.from_state_dict(load_weights(pool[n]), device=dev).eval()
+    net = TrainablePolicyNet.from_state_dict(load_weights(pool[n]), device=dev, precision=args.precision).eval()
     opt = torch.optim.AdamW(net.parameters(), lr=args.lr)
     if pool[n].endswith(".pt"):
         ck = torch.load(pool[n], map_location="cpu")

@@ -1,7 +1,7 @@
 """Training of the reference's PolicyNet / ValueNet on the MI355X from self-play records.
 
     python -m bokego_amd.train --records r/ --net policy|value|both [-c CKPT [CKPT]] [--init-trunk-from policy.pt]
-                               -e EPOCHS -b BATCH --lr LR --seed S --out DIR
+                               -e EPOCHS -b BATCH --lr LR --seed S --out DIR [--precision fp32|bf16]
     python -m bokego_amd.train --values values.csv [...] --net value [--records r/] ...
 
 closes the loop `selfplay --out r/` -> `train --records r/` -> `selfplay --policy out/policy_1.pt`, and
@@ -37,21 +37,24 @@ class _TrunkBlock(torch.autograd.Function):
     """conv (k = 5 or 3, pad k//2) -> train-mode BatchNorm2d -> ReLU; updates the BN running buffers in place."""
 
     @staticmethod
-    def forward(ctx, x, w, b, gamma, beta, running_mean, running_var, num_batches_tracked, momentum, eps):
+    def forward(ctx, x, w, b, gamma, beta, running_mean, running_var, num_batches_tracked, momentum, eps,
+                precision="fp32"):
         x = x.contiguous()
-        z = T.conv_forward(x, w.detach().contiguous(), b.detach().contiguous())
+        z = T.conv_forward(x, w.detach().contiguous(), b.detach().contiguous(), precision=precision)
         y, mean, invstd = T.bn_relu_train(z, gamma.detach().contiguous(), beta.detach().contiguous(), running_mean,
                                           running_var, num_batches_tracked, momentum, eps)
         ctx.save_for_backward(x, w, z, y, gamma, mean, invstd)
+        ctx.precision = precision
         return y
 
     @staticmethod
     def backward(ctx, dy):
         x, w, z, y, gamma, mean, invstd = ctx.saved_tensors
         dz, dgamma, dbeta = T.bn_relu_backward(dy.contiguous(), y, z, gamma.detach().contiguous(), mean, invstd)
-        dw, db = T.conv_wgrad(x, dz, w.shape)
-        dx = T.conv_dgrad(dz, w.detach().contiguous()) if ctx.needs_input_grad[0] else None
-        return dx, dw, db, dgamma, dbeta, None, None, None, None, None
+        dw, db = T.conv_wgrad(x, dz, w.shape, precision=ctx.precision)
+        dx = (T.conv_dgrad(dz, w.detach().contiguous(), precision=ctx.precision) if ctx.needs_input_grad[0]
+              else None)
+        return dx, dw, db, dgamma, dbeta, None, None, None, None, None, None
 
 
 class _TrunkBlockEval(torch.autograd.Function):
@@ -59,12 +62,13 @@ class _TrunkBlockEval(torch.autograd.Function):
     gradient of that function: the same kernels and bits forward as the no-grad eval path."""
 
     @staticmethod
-    def forward(ctx, x, w, b, gamma, beta, running_mean, running_var, eps):
+    def forward(ctx, x, w, b, gamma, beta, running_mean, running_var, eps, precision="fp32"):
         x = x.contiguous()
-        z = T.conv_forward(x, w.detach().contiguous(), b.detach().contiguous())
+        z = T.conv_forward(x, w.detach().contiguous(), b.detach().contiguous(), precision=precision)
         y = T.bn_relu_eval(z, gamma.detach().contiguous(), beta.detach().contiguous(), running_mean, running_var, eps)
         ctx.save_for_backward(x, w, z, y, gamma, running_mean, running_var)
         ctx.eps = eps
+        ctx.precision = precision
         return y
 
     @staticmethod
@@ -72,9 +76,10 @@ class _TrunkBlockEval(torch.autograd.Function):
         x, w, z, y, gamma, running_mean, running_var = ctx.saved_tensors
         dz, dgamma, dbeta = T.bn_relu_eval_backward(dy.contiguous(), y, z, gamma.detach().contiguous(), running_mean,
                                                     running_var, ctx.eps)
-        dw, db = T.conv_wgrad(x, dz, w.shape)
-        dx = T.conv_dgrad(dz, w.detach().contiguous()) if ctx.needs_input_grad[0] else None
-        return dx, dw, db, dgamma, dbeta, None, None, None
+        dw, db = T.conv_wgrad(x, dz, w.shape, precision=ctx.precision)
+        dx = (T.conv_dgrad(dz, w.detach().contiguous(), precision=ctx.precision) if ctx.needs_input_grad[0]
+              else None)
+        return dx, dw, db, dgamma, dbeta, None, None, None, None
 
 
 class _UntiedBias1x1(torch.nn.Module):
@@ -128,16 +133,27 @@ def load_weights(path):
     return _as_state_dict(torch.load(path, map_location="cpu"))
 
 
+def _check_precision(precision):
+    if precision not in T.PRECISIONS:
+        raise ValueError(f"precision must be one of {T.PRECISIONS}, got {precision!r}")
+    return precision
+
+
 class _Trainable(torch.nn.Module):
-    def __init__(self, device="cuda"):
+    """precision: "fp32", or "bf16" for the trunk convolutions on bf16 operands with fp32 accumulation (forward and
+    both gradients; weights, activations, BatchNorm, heads and the optimizer stay fp32).  A plain attribute of the
+    run: it may be changed on a live net and is not part of state_dict()."""
+
+    def __init__(self, device="cuda", precision="fp32"):
         super().__init__()
+        self.precision = _check_precision(precision)
         self.conv = _trunk_modules()
         self.to(device)
 
     @classmethod
-    def from_state_dict(cls, sd, device="cuda"):
+    def from_state_dict(cls, sd, device="cuda", precision="fp32"):
         """sd: a torch state_dict with the reference's names, BKW arrays, or a checkpoint dict."""
-        net = cls(device=device)
+        net = cls(device=device, precision=precision)
         net.load_state_dict(_as_state_dict(sd))
         return net
 
@@ -148,17 +164,19 @@ class _Trainable(torch.nn.Module):
         if not x.is_cuda:
             raise ValueError("the trainable nets run on the GPU: move the planes there first")
         h = x.float().contiguous()
+        prec = _check_precision(self.precision)
         grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.conv.parameters())
         for l in range(N_TRUNK):
             conv, bn = self.conv[3 * l], self.conv[3 * l + 1]
             if self.training:
                 h = _TrunkBlock.apply(h, conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var,
-                                      bn.num_batches_tracked, bn.momentum, bn.eps)
+                                      bn.num_batches_tracked, bn.momentum, bn.eps, prec)
             elif grad:  # eval mode with gradients (REINFORCE): frozen running statistics, differentiated
                 h = _TrunkBlockEval.apply(h, conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean,
-                                          bn.running_var, bn.eps)
+                                          bn.running_var, bn.eps, prec)
             else:  # eval mode under no_grad: running statistics, no autograd
-                z = T.conv_forward(h, conv.weight.detach().contiguous(), conv.bias.detach().contiguous())
+                z = T.conv_forward(h, conv.weight.detach().contiguous(), conv.bias.detach().contiguous(),
+                                   precision=prec)
                 h = T.bn_relu_eval(z, bn.weight.detach().contiguous(), bn.bias.detach().contiguous(), bn.running_mean,
                                    bn.running_var, bn.eps)
         return self.conv[21](h)
@@ -174,8 +192,9 @@ class TrainablePolicyNet(_Trainable):
 class TrainableValueNet(_Trainable):
     """(B,27,9,9) -> (B,1) in (-1,1); ValueNet (nnet.py:59-113) with gradients."""
 
-    def __init__(self, device="cuda"):
+    def __init__(self, device="cuda", precision="fp32"):
         torch.nn.Module.__init__(self)
+        self.precision = _check_precision(precision)
         self.conv = _trunk_modules()
         self.lin1 = torch.nn.Linear(81, 64)
         self.lin2 = torch.nn.Linear(64, 1)
@@ -401,6 +420,8 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--out", default=".")
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--precision", choices=list(T.PRECISIONS), default="fp32",
+                    help="bf16: the trunk convolutions on bf16 operands with fp32 accumulation; checkpoints stay fp32")
     args = ap.parse_args(argv)
     if args.batch < 2:
         ap.error("-b must be at least 2: BatchNorm in train mode needs a batch")
@@ -423,7 +444,8 @@ def main(argv=None):
     if len(data) < 2:
         raise SystemExit("fewer than 2 positions in the records")
     names = ["policy", "value"] if args.net == "both" else [args.net]
-    nets = {n: (TrainablePolicyNet if n == "policy" else TrainableValueNet)(device=dev) for n in names}
+    nets = {n: (TrainablePolicyNet if n == "policy" else TrainableValueNet)(device=dev, precision=args.precision)
+            for n in names}
     if args.init_trunk_from:
         trunk = load_weights(args.init_trunk_from)
         for n, net in nets.items():
@@ -469,7 +491,7 @@ def main(argv=None):
         torch.cuda.synchronize(dev)
         dt = time.perf_counter() - t0
         line = {"epoch": None, "steps": steps, "positions": positions, "positions_per_s": positions / dt,
-                "seconds": dt}
+                "seconds": dt, "precision": args.precision}
         for n in names:
             ep = start[n] + e + 1
             path = os.path.join(args.out, f"{n}_{ep}.pt")

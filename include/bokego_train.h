@@ -14,6 +14,8 @@
  *     5x5 27->128 and 3x3 128->128.  1 <= B <= BKT_MAX_BATCH.
  *   - Arithmetic: fp32 in, fp32 accumulate (v_mfma_f32_16x16x4_f32).  Every result is deterministic: sums run in
  *     an order fixed by the shapes alone (no float atomics), so equal inputs give equal bits.
+ *   - The bkt_*_bf16 entry points are an opt-in mixed-precision form of the six convolution calls: the same fp32
+ *     tensors, bf16 GEMM operands, fp32 accumulate (v_mfma_f32_16x16x32_bf16); see "bf16 mixed precision" below.
  */
 #ifndef BOKEGO_TRAIN_H
 #define BOKEGO_TRAIN_H
@@ -25,7 +27,7 @@
 extern "C" {
 #endif
 
-#define BKT_ABI_VERSION 3
+#define BKT_ABI_VERSION 4
 #define BKT_MAX_BATCH 65536
 #define BKT_COUT 128
 #define BKT_MAX_SAMPLE_ROWS (1 << 24)
@@ -69,6 +71,42 @@ size_t bkt_conv_wgrad_workspace(int batch, int cin, int ksize);
  * second kernel sums the chunks in chunk order.  Overwrites dw and db (no accumulation into them). */
 int bkt_conv_wgrad(const float *x, const float *dy, float *dw, float *db, int batch, int cin, int ksize,
                    void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---- bf16 mixed precision: the convolutions with bf16 operands (bk_train_bf16.hip) ---------------------------------- */
+
+/* The six calls above, argument for argument, except that packed weights are uint16_t (bf16 bit patterns).
+ *   - All tensors in memory stay fp32 with the shapes above: x, dy, w, bias, y, dx, dw, db.  Only the packed weights
+ *     are bf16.
+ *   - Each GEMM operand element is rounded ONCE to bf16, round to nearest even (a NaN stays a NaN), on its way into the
+ *     matrix unit -- the weights in the pack call.  With r() that rounding: products are exact in fp32, sums are the
+ *     MFMA's fp32 accumulation, without Kahan compensation.
+ *       forward          y  = sum r(w) r(x) + bias          bias added in fp32, unrounded
+ *       input gradient   dx = sum r(w rotated) r(dy)
+ *       weight gradient  dw = sum r(dy) r(x)                per slice of BKT_WGRAD_CHUNK boards, slices added in order
+ *       bias gradient    db = sum dy                        the UNROUNDED dy: double partials per slice, slices in order
+ *   - Deterministic as the fp32 calls: no float atomics, sums in an order fixed by the shapes.
+ *   - The same shapes: k = 5 or 3, any cin >= 1 (K is padded with zeros inside the packed operand), the input gradient
+ *     for 3x3 128->128 only, 1 <= B <= BKT_MAX_BATCH.  Anything else: BKT_ERR_ARG.
+ * The packed layout is private to the library: allocate bkt_conv_packed_elems_bf16 elements and pass them through. */
+
+/* Number of uint16_t a packed operand of a [128, cin, k, k] weight holds, padding included (0 for unsupported
+ * arguments).  bkt_conv_pack_dgrad_bf16 writes bkt_conv_packed_elems_bf16(128, 3). */
+size_t bkt_conv_packed_elems_bf16(int cin, int ksize);
+
+int bkt_conv_pack_bf16(const float *w, int cin, int ksize, uint16_t *wt, void *stream);
+
+int bkt_conv_forward_bf16(const float *x, const uint16_t *wt, const float *bias, float *y, int batch, int cin,
+                          int ksize, void *stream);
+
+int bkt_conv_pack_dgrad_bf16(const float *w, uint16_t *wt_dgrad, void *stream);
+
+int bkt_conv_dgrad_bf16(const float *dy, const uint16_t *wt_dgrad, float *dx, int batch, void *stream);
+
+/* Bytes of scratch bkt_conv_wgrad_bf16 needs (the same amount as bkt_conv_wgrad_workspace). */
+size_t bkt_conv_wgrad_workspace_bf16(int batch, int cin, int ksize);
+
+int bkt_conv_wgrad_bf16(const float *x, const float *dy, float *dw, float *db, int batch, int cin, int ksize,
+                        void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---- BatchNorm2d + ReLU over `channels` channels of B*81 values each ------------------------------------------------ */
 

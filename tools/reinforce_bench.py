@@ -2,6 +2,7 @@
 
     python tools/reinforce_bench.py [--games 256 4096] [--workers 16] [--reps 3] [--out profiles/reinforce_bench.json]
     python tools/reinforce_bench.py --one 4096     # warm-up, then ONE iteration at 4096 games (for rocprofv3)
+    python tools/reinforce_bench.py --precision bf16 [...]   # the update's trunk convolutions on bf16 operands
 
 An iteration is what reinforce.run_epoch does once: --workers batches of games/workers games each played in lock-step
 between two fp32 engines (policy_19 against itself), then one AdamW step per batch.  Times are wall clock between device
@@ -47,9 +48,9 @@ def _iteration(net, opt, eng, opp, W, b, seed, it, timing=None):
     return games, t1 - t0, t2 - t1
 
 
-def bench_config(sd, games, workers, reps, seed=1):
+def bench_config(sd, games, workers, reps, seed=1, precision="fp32"):
     b = games // workers
-    net = train.TrainablePolicyNet.from_state_dict(sd).eval()
+    net = train.TrainablePolicyNet.from_state_dict(sd, precision=precision).eval()
     opt = torch.optim.AdamW(net.parameters(), lr=1e-5)
     eng, opp = reinforce.policy_engine(sd, 0, games), reinforce.policy_engine(sd, 0, games)
     try:
@@ -101,11 +102,13 @@ def main():
     ap.add_argument("--yardstick-games", type=int, default=64)
     ap.add_argument("--one", type=int, default=None, help="warm up, then one iteration at this many games")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--precision", choices=["fp32", "bf16"], default="fp32",
+                    help="of the update's trunk convolutions (the playouts stay on the fp32 engines)")
     args = ap.parse_args()
     sd = train.load_weights(os.path.join(GOLDEN, "policy_19.bkw"))
     if args.one:
         b = args.one // args.workers
-        net = train.TrainablePolicyNet.from_state_dict(sd).eval()
+        net = train.TrainablePolicyNet.from_state_dict(sd, precision=args.precision).eval()
         opt = torch.optim.AdamW(net.parameters(), lr=1e-5)
         eng, opp = reinforce.policy_engine(sd, 0, args.one), reinforce.policy_engine(sd, 0, args.one)
         try:
@@ -116,8 +119,10 @@ def main():
             opp.close()
         print(json.dumps({"one": args.one, "playout_s": tp, "update_s": tu, "rows": len(g.row_game)}))
         return
-    out = {"device": torch.cuda.get_device_name(0), "configs": [bench_config(sd, n, args.workers, args.reps)
-                                                                for n in args.games]}
+    out = {"device": torch.cuda.get_device_name(0),
+           "configs": [bench_config(sd, n, args.workers, args.reps, precision=args.precision) for n in args.games]}
+    if args.precision != "fp32":
+        out["update_precision"] = args.precision
     out["yardstick"] = yardstick(sd, args.yardstick_games)
     for c in out["configs"]:
         c["playout_speedup_vs_yardstick"] = c["playout_games_per_s"] / out["yardstick"]["games_per_s"]
