@@ -41,6 +41,7 @@ SYMBOLS = {
     "bkt_bn_relu_eval_backward": (_I, [_P, _P, _P, _P, _P, _P, _F, _P, _P, _P, _P, _Z, _I, _I, _P]),
     "bkt_sample_moves": (_I, [_P, _P, _I, _U64, _P, _P, _P, _P]),
     "bkt_play_moves": (_I, [_P, _P, _I, _P, _P, _P]),
+    "bkt_area_score": (_I, [_P, _I, _F, _P, _P, _P]),
 }
 MAX_BATCH = 65536          # BKT_MAX_BATCH
 PRECISIONS = ("fp32", "bf16")
@@ -293,3 +294,17 @@ def play_moves(pos, moves, planes=None):
     _check(load().bkt_play_moves(_dev(pos, "pos", dtype=torch.uint8), _dev(moves, "moves", (B,), torch.int32), B,
                                  _dev(status, "status", dtype=torch.int32), pp, _stream(pos)), "bkt_play_moves")
     return status
+
+
+def area_score(pos, komi=5.5, owner=False):
+    """bk_pos_area_score of every record, on the device: pos uint8 [B,192] (read only) -> score f32 [B], the host's float
+    bit for bit; owner=True: (score, owner int8 [B,81]: +1 black stone or black-only empty region, -1 white, 0 neither)."""
+    if pos.dim() != 2 or pos.shape[1] != POS_BYTES:
+        raise ValueError(f"pos must be [B, {POS_BYTES}], got {tuple(pos.shape)}")
+    B = int(pos.shape[0])
+    score = torch.empty((B,), dtype=torch.float32, device=pos.device)
+    own = torch.empty((B, 81), dtype=torch.int8, device=pos.device) if owner else None
+    _check(load().bkt_area_score(_dev(pos, "pos", dtype=torch.uint8), B, float(komi), _dev(score, "score"),
+                                 None if own is None else _dev(own, "owner", dtype=torch.int8), _stream(pos)),
+           "bkt_area_score")
+    return (score, own) if owner else score

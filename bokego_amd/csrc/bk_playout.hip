@@ -1,6 +1,7 @@
 // bk_playout.hip -- the Go rules on the device: bkt_play_moves (include/bokego_train.h) plays one move on each of a batch
 // of 192-byte bk_pos records (include/bokego_go.h) in place and writes the 27 feature planes of the result, so that a
-// lock-step policy playout (bokego_amd/genvals.py) needs no host work per ply.
+// lock-step policy playout (bokego_amd/genvals.py, bokego_amd/reinforce.py) needs no host work per ply; bkt_area_score
+// scores the final records (area_score_kernel, at the end of the namespace).
 //
 // Contract: byte identity with the host rules.  After the call every record equals what bk_pos_play(p, m) followed by
 // bk_pos_liberties(p, tmp) leaves (bk_go.cpp), reserved bytes included, and the planes equal bk_features_batch_u8 of it.
@@ -216,11 +217,74 @@ __global__ void __launch_bounds__(256) play_moves_kernel(unsigned char* __restri
     }
 }
 
+// The area score (bk_pos_area_score): an empty point's thread grows its region through the empty points as a stone's thread
+// grows its chain; the region is a colour's if its neighbour set meets that colour and not the other.  The two area sets go
+// through a second round of ballots and thread 0 of a position adds the popcounts.  The records are only read.
+__device__ __forceinline__ void publish_ballots(unsigned (&bal)[2][8], int tid, bool a, bool b) {
+    const unsigned long long ba = __ballot(a), bb = __ballot(b);
+    if ((tid & 63) == 0) {
+        const int w = tid >> 6;
+        bal[0][2 * w] = (unsigned)ba; bal[0][2 * w + 1] = (unsigned)(ba >> 32);
+        bal[1][2 * w] = (unsigned)bb; bal[1][2 * w + 1] = (unsigned)(bb >> 32);
+    }
+}
+__device__ __forceinline__ BB position_set(const unsigned (&bal)[8], int p) {   // the 81 bits of position p < PPW
+    BB s;
+#pragma unroll
+    for (int kk = 0; kk < 3; ++kk) {
+        const int off = NN * p + 27 * kk, i = off >> 5, sh = off & 31;           // off + 27 <= 243: i + 1 <= 7
+        s.w[kk] = (unsigned)((((unsigned long long)bal[i + 1] << 32) | bal[i]) >> sh) & M27;
+    }
+    return s;
+}
+
+__global__ void __launch_bounds__(256) area_score_kernel(const unsigned char* __restrict__ pos, int B, float komi,
+                                                         float* __restrict__ score, signed char* __restrict__ owner) {
+    __shared__ unsigned stones[2][8], area[2][8];
+    const int tid = threadIdx.x;
+    const int b0 = blockIdx.x * PPW;
+    const int p = tid / NN, q = tid - NN * p;
+    const bool live = p < PPW && b0 + p < B;
+    const int k = q / 27;
+    const int me_board = live ? (signed char)pos[(size_t)(b0 + p) * BK_POS_BYTES + q] : 0;
+
+    publish_ballots(stones, tid, me_board == BK_BLACK, me_board == BK_WHITE);
+    __syncthreads();
+    const int pp = p < PPW ? p : 0;
+    const BB black = position_set(stones[0], pp), white = position_set(stones[1], pp);
+    const BB empty = ~(black | white);
+
+    BB x = single(k, 1u << (q - 27 * k));
+    bool changed = live && me_board == BK_EMPTY;
+    BB d = dilate(x);
+    for (;;) {                             // wave-uniform exit
+        const BB nx = (x | d) & empty;
+        changed = changed && (nx != x);
+        if (!__any(changed)) break;
+        if (changed) x = nx;
+        d = dilate(x);
+    }
+    int own = me_board == BK_BLACK ? 1 : me_board == BK_WHITE ? -1 : 0;
+    if (live && me_board == BK_EMPTY) own = (int)meets(d, black) - (int)meets(d, white);
+
+    publish_ballots(area, tid, live && own > 0, live && own < 0);
+    if (live && owner) owner[(size_t)(b0 + p) * NN + q] = (signed char)own;
+    __syncthreads();
+    if (live && q == 0) score[b0 + p] = (float)popc(position_set(area[0], p)) - ((float)popc(position_set(area[1], p)) + komi);
+}
+
 }  // namespace
 
 extern "C" int bkt_play_moves(void* pos, const int32_t* moves, int batch, int32_t* status, uint8_t* planes, void* stream) {
     if (!pos || !moves || !status || batch < 1 || batch > BKT_MAX_BATCH) return BKT_ERR_ARG;
     hipLaunchKernelGGL(play_moves_kernel, dim3((batch + PPW - 1) / PPW), dim3(256), 0, (hipStream_t)stream,
                        static_cast<unsigned char*>(pos), moves, batch, status, planes);
+    return hipGetLastError() == hipSuccess ? BKT_OK : BKT_ERR_HIP;
+}
+
+extern "C" int bkt_area_score(const void* pos, int batch, float komi, float* score, int8_t* owner, void* stream) {
+    if (!pos || !score || batch < 1 || batch > BKT_MAX_BATCH || !(komi - komi == 0.0f)) return BKT_ERR_ARG;   // komi finite
+    hipLaunchKernelGGL(area_score_kernel, dim3((batch + PPW - 1) / PPW), dim3(256), 0, (hipStream_t)stream,
+                       static_cast<const unsigned char*>(pos), batch, komi, score, reinterpret_cast<signed char*>(owner));
     return hipGetLastError() == hipSuccess ? BKT_OK : BKT_ERR_HIP;
 }

@@ -13,8 +13,8 @@ game with no legal point is scored as it stands.  With -w, SL is the lowest id o
 Playouts run in lock-step on the device, `--batch` games per pass.  The records are a uint8 [G, 192] tensor.  A pass
 sorts its games by r_g once, so at ply p the RL rows (r_g < p), the rows at their random ply (r_g == p) and the SL rows
 (r_g > p) are contiguous slices.  Each slice goes to its engine (or to the masked sampler) without a gather, and one
-bkt_play_moves call per ply plays the moves and writes the next ply's planes.  Per pass the host downloads the kept
-records, the final records and the moves; it does no work and no synchronisation per ply.
+bkt_play_moves call per ply plays the moves and writes the next ply's planes.  bkt_area_score scores the final records.
+Per pass the host downloads the kept records, the scores and the moves; it does no work and no synchronisation per ply.
 
 Randomness comes only from Philox4x32-10 keyed by --seed (reinforce.philox4x32_10 is the numpy mirror).  Counters
 depend on the game's global id g, never on its batch or row, so the output does not depend on --batch:
@@ -138,7 +138,7 @@ def _record_fields(recs):
 
 
 def _pass(sl, rl, ids, seed, dev, rules, timing):
-    """One lock-step pass over the games `ids`, sorted by r_g -> (r, moves, kept records, final records) in that order."""
+    """One lock-step pass over the games `ids`, sorted by r_g -> (r, moves, kept records, area scores) in that order."""
     n = len(ids)
     r = random_ply(ids, seed)
     key = int(seed) & (2 ** 64 - 1)
@@ -198,17 +198,24 @@ def _pass(sl, rl, ids, seed, dev, rules, timing):
             kept[rl_end:sl_start] = pos[rl_end:sl_start]
         t = lap("rules", t)
     if rules == "device":
-        pos, kept = pos.cpu().numpy(), kept.cpu().numpy()
-    out = r, hist.cpu().numpy(), kept, pos
+        score = T.area_score(pos, KOMI)
+        t = lap("score", t)
+        score, kept = score.cpu().numpy().astype(np.float64), kept.cpu().numpy()
+    else:
+        lib = go.golib()
+        score = np.array([lib.bk_pos_area_score(ctypes.cast(pos[i].ctypes.data, ctypes.POINTER(go.Pos)), KOMI)
+                          for i in range(n)], np.float64)
+    out = r, hist.cpu().numpy(), kept, score
     lap("download", t)
     return out
 
 
 def generate(sl, rl, games, batch, seed, device=None, rules="device", timing=None):
     """Play `games` games (ids 0 .. games-1) in passes of `batch`; sl, rl: fp32 LeafEngines (policy weights, max_batch >=
-    batch).  rules="device": bkt_play_moves; "host": the host rules of reinforce.play_games (the record download,
-    bk_features_batch_u8 and bk_pos_play), the reference the tests and the benchmark compare against.  timing: a dict
-    that receives seconds per phase ('engine', 'sampler', 'rules', 'download'); the phases are then separated by
+    batch).  rules="device": bkt_play_moves and bkt_area_score; "host": the host rules of reinforce.play_games(rules=
+    "host") (bk_features_batch_u8, the upload, bk_pos_play, bk_pos_area_score), the reference the tests and the benchmark
+    compare against.  timing: a dict that receives seconds per phase ('engine', 'sampler', 'rules', 'download', and
+    'score' with the device rules); the phases are then separated by
     synchronisations, so pass it only to measure.  -> Generated."""
     if rules not in ("device", "host"):
         raise ValueError(f"rules must be 'device' or 'host', got {rules!r}")
@@ -222,14 +229,11 @@ def generate(sl, rl, games, batch, seed, device=None, rules="device", timing=Non
     out.score = np.zeros(G, np.float64)
     out.kept = np.zeros(G, bool)
     rows, row_game = [], []
-    lib = go.golib()
     for s in range(0, G, batch):
         ids = np.arange(s, min(s + batch, G), dtype=np.int64)
         order = ids[np.argsort(random_ply(ids, seed), kind="stable")]
-        r, hist, kept, final = _pass(sl, rl, order, seed, dev, rules, timing)
+        r, hist, kept, score = _pass(sl, rl, order, seed, dev, rules, timing)
         out.r[order], out.moves[order] = r, hist
-        score = np.array([lib.bk_pos_area_score(ctypes.cast(final[i].ctypes.data, ctypes.POINTER(go.Pos)), KOMI)
-                          for i in range(len(order))], np.float64)
         out.score[order] = score
         ok = hist[np.arange(len(order)), r] >= 0       # a game stuck before or at r_g stays stuck: -1 at ply r_g
         out.kept[order] = ok

@@ -11,9 +11,15 @@ batch, in batch order, on
 
     loss_batch = (1/b) * sum_games r_g * sum_{learner's plies} -log pi(a|s),     r_g = +1 if the learner won, else -1.
 
-Playouts (play_games): per ply one bk_features_batch_u8 call on the live games' bk_pos records, one upload, one
-fp32 LeafEngine.eval_device per side, bkt_sample_moves on the logits, and 4 bytes per game back to the host, which
-plays the moves.  The learner's rows (planes and moves) stay on the device and are the update's batch.
+Playouts (play_games) are device-resident from the first ply to the scores.  The games are laid out once so that the
+learner-is-black and the learner-is-white games are two contiguous slices of the uint8 [G, 192] bk_pos record tensor
+and of the planes.  Per ply: one fp32 LeafEngine.eval_device per side on its slice, bkt_sample_moves on the logits, a
+copy of the learner's slice (planes, moves, logp) into preallocated row buffers, and one bkt_play_moves that plays the
+moves and writes the next ply's planes: no host work, no download and no synchronisation per ply.  bkt_area_score scores
+the final records, and one download brings back the move history and the scores.  The learner's rows stay on the
+device and are the update's batch.  play_games(rules="host") is the same loop with the rules on the host (per ply
+bk_features_batch_u8 on the live games' records, one upload, 4 bytes per game back, bk_pos_play per game, and
+bk_pos_area_score at the end): the reference the tests and the benchmark compare against, identical in every output.
 
 The update differentiates the network that sampled the moves: the eval-mode TrainablePolicyNet, BatchNorm with its
 running statistics frozen (train._TrunkBlockEval), which is the function the engine computes with the statistics
@@ -228,18 +234,122 @@ class Playouts:
         return torch.from_numpy(sel).to(dev), torch.from_numpy(self.row_game[sel] - w * b).to(dev)
 
 
-def play_games(learner, opponent, n_batches, batch_size, seed, iteration=0, epoch=0, device=None, timing=None,
-               max_turns=POLICY_MAX_TURNS):
-    """n_batches * batch_size games in lock-step between two fp32 LeafEngines (policy weights); the learner is black in
-    even batches.  timing: a dict that receives seconds spent in 'host' (features, staging, playing the moves),
-    'engine' (upload + both evaluations) and 'sampler' (bkt_sample_moves + the copy back); the phases are then
-    separated by synchronisations, so pass it only to measure."""
-    dev = torch.device("cuda", learner.device_id) if device is None else torch.device(device)
-    G = n_batches * batch_size
-    lib, play = go.golib(), _play_fn()
-    key = int(seed) & (2 ** 64 - 1)
+def _start_positions(start, G):
+    """The records play_games starts from, uint8 [G, 192] (a copy): empty boards, or `start` checked."""
+    if start is None:
+        return initial_positions(G)
+    if isinstance(start, torch.Tensor):
+        start = start.cpu().numpy()
+    start = np.array(start, order="C")
+    if start.dtype != np.uint8 or start.shape != (G, POS_BYTES):
+        raise ValueError(f"start must be uint8 [{G}, {POS_BYTES}], got {start.dtype} {start.shape}")
+    turn = np.ascontiguousarray(start[:, 172:176]).view(np.int32)[:, 0]
+    if (turn != 0).any():
+        raise ValueError(f"start: record {int(np.nonzero(turn)[0][0])} has turn {int(turn[turn != 0][0])}; every record "
+                         "must have turn 0 (black to move), so that the ply equals the turn")
+    return start
+
+
+def _play_games_device(learner, opponent, n_batches, batch_size, key, iteration, epoch, dev, timing, max_turns, pos0):
+    """play_games(rules="device"): see the module docstring."""
+    G, T_ = n_batches * batch_size, max_turns + 1
     learner_black = (np.arange(G) // batch_size) % 2 == 0
-    pos = initial_positions(G)
+    perm = np.concatenate([np.nonzero(learner_black)[0], np.nonzero(~learner_black)[0]])   # slot -> game
+    nb = int(learner_black.sum())
+    side = (slice(0, nb), slice(nb, G))                   # slots of the learner-is-black / learner-is-white games
+    clock = time.perf_counter
+
+    def lap(name, t0):
+        if timing is None:
+            return t0
+        torch.cuda.synchronize(dev)
+        t1 = clock()
+        timing[name] = timing.get(name, 0.0) + (t1 - t0)
+        return t1
+
+    t = clock()
+    pos = torch.from_numpy(pos0[perm]).to(dev)
+    ctr = torch.from_numpy(counters(perm, 0, iteration, epoch)).to(dev)
+    planes = torch.empty((G, 27, 9, 9), dtype=torch.uint8, device=dev)
+    hist = torch.full((G, T_), go.PASS, dtype=torch.int16, device=dev)
+    status = T.play_moves(pos, torch.full((G,), -1, dtype=torch.int32, device=dev), planes)    # ply 0's planes
+    # the learner's rows in ply order: ply p holds the games of side p % 2, ascending
+    n_side = (nb, G - nb)
+    row0 = np.concatenate([[0], np.cumsum([n_side[p % 2] for p in range(T_)])])
+    rows_planes = torch.empty((int(row0[-1]), 27, 9, 9), dtype=torch.uint8, device=dev)
+    rows_moves = torch.empty((int(row0[-1]),), dtype=torch.int32, device=dev)
+    rows_logp = torch.empty((int(row0[-1]),), dtype=torch.float32, device=dev)
+    t = lap("rules", t)
+    for ply in range(T_):
+        mine = side[ply % 2]
+        if ply:
+            ctr[:, 1].fill_(ply)
+        engines = (learner, opponent) if ply % 2 == 0 else (opponent, learner)      # black is to move on even plies
+        logits = [eng.eval_device(planes[sl], logits=True, probs=False, value=False)["logits"]
+                  for eng, sl in zip(engines, side) if sl.stop > sl.start]
+        logits = logits[0] if len(logits) == 1 else torch.cat(logits)
+        t = lap("engine", t)
+        moves, logp = T.sample_moves(logits, planes, key, ctr)
+        hist[:, ply] = moves
+        t = lap("sampler", t)
+        a, b = int(row0[ply]), int(row0[ply + 1])
+        if b > a:                                         # before bkt_play_moves overwrites the planes
+            rows_planes[a:b] = planes[mine]
+            rows_moves[a:b] = moves[mine]
+            rows_logp[a:b] = logp[mine]
+        status |= T.play_moves(pos, moves, planes)
+        t = lap("rules", t)
+    score = T.area_score(pos, KOMI)
+    t = lap("score", t)
+    back = torch.cat([hist, score.view(torch.int16).view(G, 2), status.view(torch.int16).view(G, 2)], 1).cpu().numpy()
+    t = lap("download", t)
+    st = np.ascontiguousarray(back[:, T_ + 2:]).view(np.int32)[:, 0]
+    if st.any():
+        s = int(np.nonzero(st)[0][0])
+        raise RuntimeError(f"game {perm[s]}: a sampled move is illegal (status {st[s]}); the legal plane and the rules "
+                           "disagree")
+    out = Playouts()
+    out.moves = np.empty((G, T_), np.int16)
+    out.moves[perm] = back[:, :T_]
+    scores = np.empty(G, np.float32)
+    scores[perm] = np.ascontiguousarray(back[:, T_:T_ + 2]).view(np.float32)[:, 0]
+    out.length = (out.moves >= 0).sum(1).astype(np.int64)        # a game without a move at a ply has none later
+    out.learner_black = learner_black
+    out.black_wins = scores > 0
+    out.reward = np.where(out.black_wins == learner_black, 1.0, -1.0).astype(np.float32)
+    row_game = np.concatenate([perm[side[p % 2]] for p in range(T_)]).astype(np.int64)
+    keep = out.moves[row_game, np.repeat(np.arange(T_), [n_side[p % 2] for p in range(T_)])] >= 0
+    if not keep.all():                                    # the plies of ended games
+        k = torch.from_numpy(np.nonzero(keep)[0]).to(dev)
+        rows_planes, rows_moves, rows_logp = (x.index_select(0, k) for x in (rows_planes, rows_moves, rows_logp))
+        row_game = row_game[keep]
+    out.planes, out.played, out.logp, out.row_game = rows_planes, rows_moves.long(), rows_logp, row_game
+    lap("download", t)
+    return out
+
+
+def play_games(learner, opponent, n_batches, batch_size, seed, iteration=0, epoch=0, device=None, timing=None,
+               max_turns=POLICY_MAX_TURNS, rules="device", start=None):
+    """n_batches * batch_size games in lock-step between two fp32 LeafEngines (policy weights); the learner is black in
+    even batches.  rules="device": bkt_play_moves and bkt_area_score, nothing on the host per ply; "host": the host
+    rules (bk_features_batch_u8, the upload, bk_pos_play, bk_pos_area_score), the reference the tests and the benchmark
+    compare against.  Both give the same Playouts, bit for bit.  start: uint8 [G, 192] bk_pos records to play from (game
+    g from start[g]), every one with turn 0; default: empty boards.  timing: a dict that receives seconds per phase;
+    the phases are then separated by synchronisations, so pass it only to measure.  Device rules: 'engine' (both
+    evaluations), 'sampler' (bkt_sample_moves + the move history), 'rules' (the copy of the learner's rows +
+    bkt_play_moves), 'score' (bkt_area_score), 'download'.  Host rules: 'host' (features, staging, playing the moves),
+    'engine' (upload + both evaluations) and 'sampler' (bkt_sample_moves + the copy back)."""
+    if rules not in ("device", "host"):
+        raise ValueError(f"rules must be 'device' or 'host', got {rules!r}")
+    G = n_batches * batch_size
+    pos = _start_positions(start, G)
+    dev = torch.device("cuda", learner.device_id) if device is None else torch.device(device)
+    key = int(seed) & (2 ** 64 - 1)
+    if rules == "device":
+        return _play_games_device(learner, opponent, n_batches, batch_size, key, iteration, epoch, dev, timing,
+                                  max_turns, pos)
+    lib, play = go.golib(), _play_fn()
+    learner_black = (np.arange(G) // batch_size) % 2 == 0
     hist = np.full((G, max_turns + 1), go.PASS, np.int16)
     length = np.zeros(G, np.int64)
     staging = torch.empty(G * (16 + PLANE_BYTES), dtype=torch.uint8).pin_memory()

@@ -1,7 +1,8 @@
 /*
  * bokego_train.h -- C ABI of the training kernels (libbktrain.so): the trunk of the reference's PolicyNet / ValueNet
  * (bokego/nnet.py:31-57, 73-113) with gradients, for bokego_amd/train.py, the move sampler of the REINFORCE
- * playouts (bokego_amd/reinforce.py), and the Go rules of the device-resident playouts (bokego_amd/genvals.py).
+ * playouts (bokego_amd/reinforce.py), and the Go rules and the area score of the device-resident playouts
+ * (bokego_amd/reinforce.py, bokego_amd/genvals.py).
  *
  * Conventions:
  *   - Stateless.  No entry point allocates device memory or keeps anything between calls: every buffer is a device
@@ -155,7 +156,7 @@ int bkt_bn_relu_eval_backward(const float *dy, const float *y, const float *x, c
 int bkt_sample_moves(const float *logits, const uint8_t *planes, int batch, uint64_t seed, const uint32_t *counters,
                      int32_t *moves, float *logp, void *stream);
 
-/* ---- the Go rules on the device (bokego_amd/genvals.py; bk_playout.hip) --------------------------------------------- */
+/* ---- the Go rules on the device (reinforce.py, genvals.py; bk_playout.hip) --------------------------------------------- */
 
 /* For each row b < batch: if moves[b] >= 0, play it on the 192-byte record pos[b] (bk_pos, include/bokego_go.h) and
  * refresh its liberty cache, in place; status[b] = 0 or the BK_ILLEGAL_* code (record untouched).  moves[b] < 0: the
@@ -165,6 +166,12 @@ int bkt_sample_moves(const float *logits, const uint8_t *planes, int batch, uint
  * Byte identity with the host: every record afterwards equals what bk_pos_play(p, m) followed by
  * bk_pos_liberties(p, tmp) leaves, all 192 bytes (board, libs, libs_valid, ko, last move, turn, hash, reserved). */
 int bkt_play_moves(void *pos, const int32_t *moves, int batch, int32_t *status, uint8_t *planes, void *stream);
+
+/* For each row b < batch: score[b] = bk_pos_area_score(&pos[b], komi) -- Tromp-Taylor area: stones, plus empty regions
+ * bordered by one colour only; black - (white + komi), computed as (float)black - ((float)white + komi).
+ * owner != NULL: owner[b*81 + s] = +1 black stone or black-only region, -1 white, 0 otherwise.
+ * The records are read only.  1 <= batch <= BKT_MAX_BATCH; komi must be finite; else BKT_ERR_ARG. */
+int bkt_area_score(const void *pos, int batch, float komi, float *score, int8_t *owner, void *stream);
 
 #ifdef __cplusplus
 }
