@@ -40,12 +40,15 @@ SYMBOLS = {
     "bkt_bn_relu_eval": (_I, [_P, _P, _P, _P, _P, _F, _P, _I, _I, _P]),
     "bkt_bn_relu_eval_backward": (_I, [_P, _P, _P, _P, _P, _P, _F, _P, _P, _P, _P, _Z, _I, _I, _P]),
     "bkt_sample_moves": (_I, [_P, _P, _I, _U64, _P, _P, _P, _P]),
+    "bkt_sample_moves_masked": (_I, [_P, _P, _Z, _I, _U64, _P, _P, _P, _P]),
     "bkt_play_moves": (_I, [_P, _P, _I, _P, _P, _P]),
+    "bkt_playout_step": (_I, [_P, _P, _I, _P, _P, _P, _P, _P]),
     "bkt_area_score": (_I, [_P, _I, _F, _P, _P, _P]),
 }
 MAX_BATCH = 65536          # BKT_MAX_BATCH
 PRECISIONS = ("fp32", "bf16")
 POS_BYTES = 192            # sizeof(bk_pos)
+MOVE_NONE = -2             # BKT_MOVE_NONE: bkt_playout_step leaves the row alone
 
 _lib = None
 
@@ -280,6 +283,23 @@ def sample_moves(logits, planes, seed, counters):
     return moves, logp
 
 
+def sample_moves_masked(logits, mask, seed, counters):
+    """sample_moves with the acceptable points given as mask uint8 [B,81] (non-zero: may be played) instead of the legal
+    plane: the same kernel, the same draw; -1 where a row's mask is empty."""
+    if logits.dim() != 2 or logits.shape[1] != 81:
+        raise ValueError(f"logits must be [B, 81], got {tuple(logits.shape)}")
+    B = int(logits.shape[0])
+    moves = torch.empty((B,), dtype=torch.int32, device=logits.device)
+    logp = torch.empty((B,), dtype=torch.float32, device=logits.device)
+    if B == 0:
+        return moves, logp
+    _check(load().bkt_sample_moves_masked(_dev(logits, "logits"), _dev(mask, "mask", (B, 81), torch.uint8), 81, B,
+                                          int(seed) & (2 ** 64 - 1), _dev(counters, "counters", (B, 4), torch.int32),
+                                          _dev(moves, "moves", dtype=torch.int32), _dev(logp, "logp"), _stream(logits)),
+           "bkt_sample_moves_masked")
+    return moves, logp
+
+
 def play_moves(pos, moves, planes=None):
     """The Go rules on the device, in place: pos uint8 [B,192] (bk_pos records), moves int32 [B] (< 0: leave the row
     alone) -> status int32 [B] (0 or BK_ILLEGAL_*; an illegal row is untouched).  planes: None, or uint8 [B,27,9,9]
@@ -293,6 +313,26 @@ def play_moves(pos, moves, planes=None):
     pp = None if planes is None else _dev(planes, "planes", (B, 27, 9, 9), torch.uint8)
     _check(load().bkt_play_moves(_dev(pos, "pos", dtype=torch.uint8), _dev(moves, "moves", (B,), torch.int32), B,
                                  _dev(status, "status", dtype=torch.int32), pp, _stream(pos)), "bkt_play_moves")
+    return status
+
+
+def playout_step(pos, moves, over=None, planes=None, playable=None):
+    """One ply of a playout to the end of the game, in place: play_moves that also passes (moves == -1: the second pass
+    in a row sets over), leaves rows alone whose move is <= MOVE_NONE or whose over flag is set, and writes playable uint8
+    [B,81]: the points the side to move may play in a playout (legal, and not its own one-point eye).  over: None or
+    uint8 [B]; planes: None or uint8 [B,27,9,9]; playable: None or uint8 [B,81].  -> status int32 [B]."""
+    if pos.dim() != 2 or pos.shape[1] != POS_BYTES:
+        raise ValueError(f"pos must be [B, {POS_BYTES}], got {tuple(pos.shape)}")
+    B = int(pos.shape[0])
+    if not 1 <= B <= MAX_BATCH:
+        raise ValueError(f"batch must be 1..{MAX_BATCH}, got {B}")
+    status = torch.empty((B,), dtype=torch.int32, device=pos.device)
+    _check(load().bkt_playout_step(_dev(pos, "pos", dtype=torch.uint8), _dev(moves, "moves", (B,), torch.int32), B,
+                                   None if over is None else _dev(over, "over", (B,), torch.uint8),
+                                   _dev(status, "status", dtype=torch.int32),
+                                   None if planes is None else _dev(planes, "planes", (B, 27, 9, 9), torch.uint8),
+                                   None if playable is None else _dev(playable, "playable", (B, 81), torch.uint8),
+                                   _stream(pos)), "bkt_playout_step")
     return status
 
 

@@ -1,7 +1,9 @@
 // bk_playout.hip -- the Go rules on the device: bkt_play_moves (include/bokego_train.h) plays one move on each of a batch
 // of 192-byte bk_pos records (include/bokego_go.h) in place and writes the 27 feature planes of the result, so that a
 // lock-step policy playout (bokego_amd/genvals.py, bokego_amd/reinforce.py) needs no host work per ply; bkt_area_score
-// scores the final records (area_score_kernel, at the end of the namespace).
+// scores the final records (area_score_kernel, at the end of the namespace).  bkt_playout_step is the same body (play_body
+// with STEP = true) for playouts that run to the end of the game (bokego_amd/rollout.py): it also passes, keeps the `over`
+// flag of a game that two passes have ended, and writes the points a playout may play (legal and not the mover's own eye).
 //
 // Contract: byte identity with the host rules.  After the call every record equals what bk_pos_play(p, m) followed by
 // bk_pos_liberties(p, tmp) leaves (bk_go.cpp), reserved bytes included, and the planes equal bk_features_batch_u8 of it.
@@ -21,6 +23,13 @@
 // from bk_enc::encode_points on an LDS copy of the updated record whose libs are the refreshed ones bk_features_batch_u8
 // would use (for an untouched record, the refresh pending on it; the record itself stays untouched).
 // The hash needs no table: bk_go.cpp's Zobrist entry i is splitmix64's mix of (i + 2) * 0x9E3779B97F4A7C15.
+// The step (STEP): a row whose `over` flag is set, or whose move is <= BKT_MOVE_NONE, is an untouched record.  A pass is
+// bk_pos_play(p, BK_PASS) + bk_pos_liberties: the header changes (ko out of the hash, side to move, turn, last move), and
+// the liberty cache is computed only when it was invalid -- last_move is BK_PASS by then, so a refresh that was pending on
+// the old last move does NOT happen.  `playable` is bk_pos_is_legal && bk_pos_possible_eye != the mover, on the record as
+// it stands after the call: legality is plane 5 of the encoder; the eye is mask algebra on the updated stone sets (every
+// on-board neighbour the mover's, and the reference's diagonal count, bk_go.cpp bk_pos_possible_eye: (r+1,c+1), (r+1,c-1)
+// and (r-1,c-1) TWICE, one fault more when any of them is off the board, an eye when at most one fault).
 // Integer work only; plain vector stores.
 #include "bk_encode_dev.h"
 
@@ -51,9 +60,10 @@ __device__ __forceinline__ int first_point(BB a) {
     return a.w[0] ? __ffs(a.w[0]) - 1 : a.w[1] ? 27 + __ffs(a.w[1]) - 1 : 54 + __ffs(a.w[2]) - 1;
 }
 
-__global__ void __launch_bounds__(256) play_moves_kernel(unsigned char* __restrict__ pos, const int32_t* __restrict__ moves,
-                                                         int B, int32_t* __restrict__ status,
-                                                         unsigned char* __restrict__ planes) {
+template <bool STEP>
+__device__ __forceinline__ void play_body(unsigned char* __restrict__ pos, const int32_t* __restrict__ moves, int B,
+                                          unsigned char* __restrict__ over, int32_t* __restrict__ status,
+                                          unsigned char* __restrict__ planes, unsigned char* __restrict__ playable) {
     __shared__ EncLds S;
     __shared__ __align__(16) unsigned char rec[PPW * BK_POS_BYTES];   // the updated records, as the encoder reads them
     const int tid = threadIdx.x;
@@ -75,6 +85,7 @@ __global__ void __launch_bounds__(256) play_moves_kernel(unsigned char* __restri
         lm = (short)(kl >> 16);
         turn = *reinterpret_cast<const int*>(dst + OFF_TURN);
         mv = moves[b0 + p];
+        if (STEP && over && over[b0 + p]) mv = BKT_MOVE_NONE;          // read before the first barrier, written after the last
         if (lm >= 0) libs_lm = dst[OFF_LIBS + lm];
         if (mv >= 0 && mv < NN) libs_mv = dst[OFF_LIBS + mv];
     }
@@ -157,6 +168,7 @@ __global__ void __launch_bounds__(256) play_moves_kernel(unsigned char* __restri
         }
     }
     const bool legal = live && mv >= 0 && st == 0;
+    const bool passed = STEP && live && mv == BK_PASS;
 
     // ---- 4. the liberty cache: refresh_libs before the move (libs1), and after it (libs2) ----
     int libs1 = my_libs;
@@ -190,19 +202,34 @@ __global__ void __launch_bounds__(256) play_moves_kernel(unsigned char* __restri
             *reinterpret_cast<uint64_t*>(dst + OFF_HASH) = h;
         }
     }
+    const int libs_pass = valid ? my_libs : (stone ? popc(lib) : 0);   // a pass: the cache only when it was invalid
+    if (passed) {
+        if (!valid) dst[OFF_LIBS + q] = (unsigned char)libs_pass;
+        if (q == 0) {
+            uint64_t h = *reinterpret_cast<const uint64_t*>(dst + OFF_HASH) ^ zobrist(Z_FLIP);
+            if (ko >= 0) h ^= zobrist(Z_KO + ko);
+            dst[OFF_VALID] = 1;
+            *reinterpret_cast<unsigned*>(dst + OFF_KO) = (unsigned)(unsigned short)BK_NO_KO | ((unsigned)BK_PASS << 16);
+            *reinterpret_cast<int*>(dst + OFF_TURN) = turn + 1;
+            *reinterpret_cast<uint64_t*>(dst + OFF_HASH) = h;
+            if (over && lm == BK_PASS) over[b0 + p] = 1;               // the second pass in a row ends the game
+        }
+    }
     if (live && q == 0) status[b0 + p] = st;
-    if (!planes) return;                    // uniform: a kernel argument
+    if (!planes && !(STEP && playable)) return;                        // uniform: kernel arguments
 
     // ---- 6. the planes of the record as it now stands, libs refreshed as bk_features_batch_u8 refreshes them (an
     //         untouched record: libs1, the refresh pending on it; after a legal move libs2 is already refreshed) ----
     if (live) {
         unsigned char* r = rec + p * BK_POS_BYTES;
         r[q] = (unsigned char)board2;
-        r[OFF_LIBS + q] = (unsigned char)(legal ? libs2 : libs1);
+        r[OFF_LIBS + q] = (unsigned char)(legal ? libs2 : passed ? libs_pass : libs1);
         if (q == 0) {
             *reinterpret_cast<unsigned*>(r + OFF_KO) =
-                legal ? ((unsigned)(unsigned short)new_ko | ((unsigned)mv << 16)) : ((unsigned)(unsigned short)ko | ((unsigned)lm << 16));
-            *reinterpret_cast<int*>(r + OFF_TURN) = legal ? turn + 1 : turn;
+                legal ? ((unsigned)(unsigned short)new_ko | ((unsigned)mv << 16))
+                : passed ? ((unsigned)(unsigned short)BK_NO_KO | ((unsigned)BK_PASS << 16))
+                         : ((unsigned)(unsigned short)ko | ((unsigned)lm << 16));
+            *reinterpret_cast<int*>(r + OFF_TURN) = legal || passed ? turn + 1 : turn;
         }
     }
     __syncthreads();
@@ -210,11 +237,42 @@ __global__ void __launch_bounds__(256) play_moves_kernel(unsigned char* __restri
     bool enc_live;
     int ep, eq;
     encode_points(rec, B - b0, tid, S, v, enc_live, ep, eq);
-    if (enc_live) {
+    if (enc_live && planes) {
         unsigned char* out = planes + (size_t)(b0 + ep) * 2187 + eq;
 #pragma unroll
         for (int i = 0; i < 27; ++i) out[i * NN] = v[i];
     }
+    if (!STEP || !playable || !live) return;
+
+    // ---- 7. the playable set of the record as it now stands: legal (plane 5) and not the mover's own one-point eye ----
+    BB mine = me == BK_BLACK ? black : white, theirs = me == BK_BLACK ? white : black;
+    if (legal) { mine = mine | point(mv); theirs = theirs & ~cap; }
+    const bool flipped = legal || passed;                              // the side to move is now the other one
+    const BB mover = flipped ? theirs : mine, other = flipped ? mine : theirs;
+    bool eye = !meets(dilate(single(k, bit)), ~mover);                 // every on-board neighbour is the mover's stone
+    if (eye) {
+        const int r = q / 9, c = q - 9 * r;
+        int on_board = 0, faults = 0;
+        if (r + 1 < 9 && c + 1 < 9) { on_board += 1; faults += (int)meets(other, point(q + 10)); }
+        if (r + 1 < 9 && c >= 1) { on_board += 1; faults += (int)meets(other, point(q + 8)); }
+        if (r >= 1 && c >= 1) { on_board += 2; faults += 2 * (int)meets(other, point(q - 10)); }   // the table lists it twice
+        if (on_board < 4) ++faults;
+        eye = faults <= 1;
+    }
+    playable[(size_t)(b0 + p) * NN + q] = (unsigned char)(v[5] && !eye);
+}
+
+__global__ void __launch_bounds__(256) play_moves_kernel(unsigned char* __restrict__ pos, const int32_t* __restrict__ moves,
+                                                         int B, int32_t* __restrict__ status,
+                                                         unsigned char* __restrict__ planes) {
+    play_body<false>(pos, moves, B, nullptr, status, planes, nullptr);
+}
+
+__global__ void __launch_bounds__(256) playout_step_kernel(unsigned char* __restrict__ pos, const int32_t* __restrict__ moves,
+                                                           int B, unsigned char* __restrict__ over,
+                                                           int32_t* __restrict__ status, unsigned char* __restrict__ planes,
+                                                           unsigned char* __restrict__ playable) {
+    play_body<true>(pos, moves, B, over, status, planes, playable);
 }
 
 // The area score (bk_pos_area_score): an empty point's thread grows its region through the empty points as a stone's thread
@@ -279,6 +337,14 @@ extern "C" int bkt_play_moves(void* pos, const int32_t* moves, int batch, int32_
     if (!pos || !moves || !status || batch < 1 || batch > BKT_MAX_BATCH) return BKT_ERR_ARG;
     hipLaunchKernelGGL(play_moves_kernel, dim3((batch + PPW - 1) / PPW), dim3(256), 0, (hipStream_t)stream,
                        static_cast<unsigned char*>(pos), moves, batch, status, planes);
+    return hipGetLastError() == hipSuccess ? BKT_OK : BKT_ERR_HIP;
+}
+
+extern "C" int bkt_playout_step(void* pos, const int32_t* moves, int batch, uint8_t* over, int32_t* status, uint8_t* planes,
+                                uint8_t* playable, void* stream) {
+    if (!pos || !moves || !status || batch < 1 || batch > BKT_MAX_BATCH) return BKT_ERR_ARG;
+    hipLaunchKernelGGL(playout_step_kernel, dim3((batch + PPW - 1) / PPW), dim3(256), 0, (hipStream_t)stream,
+                       static_cast<unsigned char*>(pos), moves, batch, over, status, planes, playable);
     return hipGetLastError() == hipSuccess ? BKT_OK : BKT_ERR_HIP;
 }
 

@@ -422,7 +422,7 @@ __global__ __launch_bounds__(256) void bn_eval_bwd_apply_kernel(const float *__r
 
 // ---- move sampling: Philox4x32-10 (Salmon et al., SC'11; the Random123 constants) and one wave64 per row ---------------
 constexpr int SAMPLE_WAVES = 4;       // rows per workgroup
-constexpr int LEGAL_PLANE = 5;        // nnet.features' "legal" plane
+constexpr int LEGAL_PLANE = 5;        // nnet.features' "legal" plane: bkt_sample_moves' mask, with a row stride of 27 planes
 
 __device__ __forceinline__ void philox4x32_10(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
 #pragma unroll
@@ -442,8 +442,10 @@ __device__ __forceinline__ void philox4x32_10(uint32_t (&c)[4], uint32_t k0, uin
 }
 
 // Lane l holds points l and 64 + l (the second only for l < 17).  Every branch below is uniform over the wave.
+// mask[row * mask_stride + i] != 0: point i may be played (bkt_sample_moves: the legal plane inside the feature planes).
 __global__ __launch_bounds__(64 * SAMPLE_WAVES) void sample_moves_kernel(const float *__restrict__ logits,
-                                                                         const uint8_t *__restrict__ planes, int batch,
+                                                                         const uint8_t *__restrict__ mask,
+                                                                         size_t mask_stride, int batch,
                                                                          uint32_t k0, uint32_t k1,
                                                                          const uint32_t *__restrict__ counters,
                                                                          int32_t *__restrict__ moves,
@@ -452,7 +454,7 @@ __global__ __launch_bounds__(64 * SAMPLE_WAVES) void sample_moves_kernel(const f
     const int row = blockIdx.x * SAMPLE_WAVES + (threadIdx.x >> 6);
     if (row >= batch) return;
     const float *x = logits + (size_t)row * P;
-    const uint8_t *legal = planes + ((size_t)row * 27 + LEGAL_PLANE) * P;
+    const uint8_t *legal = mask + (size_t)row * mask_stride;
     const bool has1 = lane < P - 64;
     const float xa = x[lane], xb = has1 ? x[64 + lane] : -INFINITY;
     float m = fmaxf(xa, xb);
@@ -667,8 +669,15 @@ int bkt_bn_relu_eval_backward(const float *dy, const float *y, const float *x, c
 int bkt_sample_moves(const float *logits, const uint8_t *planes, int batch, uint64_t seed, const uint32_t *counters,
                      int32_t *moves, float *logp, void *stream) {
     if (!logits || !planes || !counters || !moves || !logp || batch < 1 || batch > BKT_MAX_SAMPLE_ROWS) return BKT_ERR_ARG;
+    return bkt_sample_moves_masked(logits, planes + LEGAL_PLANE * P, (size_t)27 * P, batch, seed, counters, moves, logp,
+                                   stream);
+}
+
+int bkt_sample_moves_masked(const float *logits, const uint8_t *mask, size_t mask_stride, int batch, uint64_t seed,
+                            const uint32_t *counters, int32_t *moves, float *logp, void *stream) {
+    if (!logits || !mask || !counters || !moves || !logp || batch < 1 || batch > BKT_MAX_SAMPLE_ROWS) return BKT_ERR_ARG;
     hipLaunchKernelGGL(sample_moves_kernel, dim3(blocks(batch, SAMPLE_WAVES)), dim3(64 * SAMPLE_WAVES), 0, S(stream),
-                       logits, planes, batch, (uint32_t)seed, (uint32_t)(seed >> 32), counters, moves, logp);
+                       logits, mask, mask_stride, batch, (uint32_t)seed, (uint32_t)(seed >> 32), counters, moves, logp);
     return launched();
 }
 

@@ -2,7 +2,7 @@
 bin/genvals.py).
 
     python -m bokego_amd.genvals -o values.csv [-w POOL | --sl PATH --rl PATH] [-n THOUSANDS | --games G]
-                                 [--batch 4096] [--seed S] [--device D]
+                                 [--batch 4096] [--seed S] [--device D] [--finish]
 
 A game (gen_game): r_g is drawn uniformly from [70, 90).  The SL policy samples plies 0 .. r_g - 1, ply r_g is a uniformly
 random legal point, and the RL policy samples from then on while turn < 90.  The game is scored by area with komi 5.5.
@@ -22,6 +22,11 @@ depend on the game's global id g, never on its batch or row, so the output does 
     r_g:                               (g mod 2^32, 0, g >> 32, 1)  -> r_g = 70 + floor(20 * u), u = (x0 >> 8) * 2^-24
 The random move is bkt_sample_moves on masked logits (0 on the legal points of plane 5, -inf elsewhere): the first
 point whose prefix count of legal points exceeds u * (number of legal points), -1 when there is none.
+
+--finish (generate(finish=True)): after turn 90 the RL policy plays the game out, both colours, to two passes in a row
+(rollout.finish_games, counters (g mod 2^32, p, g >> 32, 0) running on with p = 90, 91, ...), and the label comes from
+the area score of the finished board, on which dead stones have been captured.  The stored rows are the same; only
+val can differ.
 
 The output is a CSV with the header `board,ko,last,turn,val`, appended to (`a+`).  DESIGN 13 lists where this departs
 from the reference.
@@ -137,7 +142,7 @@ def _record_fields(recs):
     return boards, ko, last, turn
 
 
-def _pass(sl, rl, ids, seed, dev, rules, timing):
+def _pass(sl, rl, ids, seed, dev, rules, timing, finish=False):
     """One lock-step pass over the games `ids`, sorted by r_g -> (r, moves, kept records, area scores) in that order."""
     n = len(ids)
     r = random_ply(ids, seed)
@@ -197,7 +202,14 @@ def _pass(sl, rl, ids, seed, dev, rules, timing):
                     raise RuntimeError(f"game {ids[i]} ply {ply}: sampled move {mv[i]} is illegal")
             kept[rl_end:sl_start] = pos[rl_end:sl_start]
         t = lap("rules", t)
-    if rules == "device":
+    if finish:
+        from . import rollout
+        fin = rollout.finish_games(pos, rl, seed, counters=move_counters(ids, MAX_TURNS), rules=rules, device=dev,
+                                   komi=KOMI)
+        score = fin.score.astype(np.float64)
+        kept = kept.cpu().numpy() if rules == "device" else kept
+        t = lap("finish", t)
+    elif rules == "device":
         score = T.area_score(pos, KOMI)
         t = lap("score", t)
         score, kept = score.cpu().numpy().astype(np.float64), kept.cpu().numpy()
@@ -210,13 +222,14 @@ def _pass(sl, rl, ids, seed, dev, rules, timing):
     return out
 
 
-def generate(sl, rl, games, batch, seed, device=None, rules="device", timing=None):
+def generate(sl, rl, games, batch, seed, device=None, rules="device", timing=None, finish=False):
     """Play `games` games (ids 0 .. games-1) in passes of `batch`; sl, rl: fp32 LeafEngines (policy weights, max_batch >=
     batch).  rules="device": bkt_play_moves and bkt_area_score; "host": the host rules of reinforce.play_games(rules=
     "host") (bk_features_batch_u8, the upload, bk_pos_play, bk_pos_area_score), the reference the tests and the benchmark
     compare against.  timing: a dict that receives seconds per phase ('engine', 'sampler', 'rules', 'download', and
     'score' with the device rules); the phases are then separated by
-    synchronisations, so pass it only to measure.  -> Generated."""
+    synchronisations, so pass it only to measure.  finish: the RL engine plays every game out after turn 90 and the
+    score is the finished board's (phase 'finish' instead of 'score').  -> Generated."""
     if rules not in ("device", "host"):
         raise ValueError(f"rules must be 'device' or 'host', got {rules!r}")
     if not 1 <= batch <= T.MAX_BATCH:
@@ -232,7 +245,7 @@ def generate(sl, rl, games, batch, seed, device=None, rules="device", timing=Non
     for s in range(0, G, batch):
         ids = np.arange(s, min(s + batch, G), dtype=np.int64)
         order = ids[np.argsort(random_ply(ids, seed), kind="stable")]
-        r, hist, kept, score = _pass(sl, rl, order, seed, dev, rules, timing)
+        r, hist, kept, score = _pass(sl, rl, order, seed, dev, rules, timing, finish)
         out.r[order], out.moves[order] = r, hist
         out.score[order] = score
         ok = hist[np.arange(len(order)), r] >= 0       # a game stuck before or at r_g stays stuck: -1 at ply r_g
@@ -263,6 +276,8 @@ def _parse(argv):
     ap.add_argument("--batch", type=int, default=4096, help="games per lock-step pass")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--finish", action="store_true",
+                    help="the RL policy plays every game out after turn 90; the label comes from the finished board")
     args = ap.parse_args(argv)
     if args.w is None and args.sl is None and args.rl is None:
         ap.error("no policies: give -w POOL or --sl PATH --rl PATH")
@@ -297,7 +312,7 @@ def main(argv=None):
     rl = R.policy_engine(load_weights(args.rl), args.device, args.batch)
     try:
         t0 = time.perf_counter()
-        out = generate(sl, rl, args.games, args.batch, args.seed, dev)
+        out = generate(sl, rl, args.games, args.batch, args.seed, dev, finish=args.finish)
         dt = time.perf_counter() - t0
     finally:
         sl.close()

@@ -9,6 +9,11 @@ it, boke.py:17 vs 40-44); `clear_cache` answers "= " instead of failing; ponderi
 asked for (`--ponder` / `pondering on`; the reference's default is on: it searches in a busy loop while a thread waits
 on stdin); an `analyze` reply ends with the empty line GTP requires once the next command has arrived.
 Replies are pinned against a transcript recorded from the reference (tests/golden/gtp_transcript.json).
+
+`--rollout-score N` (N > 0) scores by playouts: `final_score` answers with rollout.rollout_score's score of the current
+position (N policy playouts to the end of the game on the device: dead stones are captured before the count), and the
+standard command `final_status_list alive|dead|seki` is added.  Both need the HIP engine.  N = 0, the default, keeps the
+score of the board as it stands and the reference's command list.
 """
 import argparse
 import os
@@ -38,6 +43,12 @@ class _GTPProtocol:
         self.time_lim = kwargs.pop("time_lim", 20.0)
         self.n_rollouts = kwargs.pop("n_rollouts", None)
         self.pondering = kwargs.pop("pondering", False)
+        self.rollout_score_n = int(kwargs.pop("rollout_score", 0))
+        self.rollout_seed = int(kwargs.pop("rollout_seed", 0))
+        if self.rollout_score_n < 0:
+            raise ValueError("rollout_score must not be negative")
+        if self.rollout_score_n:
+            self.commands = type(self).commands + ("final_status_list",)
         kwargs.pop("connection", None)
         super().__init__(root, policy_net, value_net, **kwargs)
         self.running = False
@@ -265,8 +276,33 @@ class _GTPProtocol:
         self._undid = True
         return True, ""
 
+    NO_HIP = "rollout scoring needs the HIP backend"
+
+    def _rollout_result(self):
+        """rollout.rollout_score of the root with the policy net's HIP engine; None when the net has none."""
+        get = getattr(self.policy_net, "engine", None)
+        if not callable(get):
+            return None
+        from . import rollout
+        root = self.root
+        return rollout.rollout_score([root], get(), n=self.rollout_score_n, seed=self.rollout_seed, komi=root.komi)[0]
+
+    def _c_final_status_list(self, args, turn):
+        if len(args) != 1 or args[0] not in ("alive", "dead", "seki"):
+            return False, "usage: final_status_list <alive|dead|seki>"
+        r = self._rollout_result()
+        if r is None:
+            return False, self.NO_HIP
+        return True, " ".join(go.unsquash(r.stones(args[0])))
+
     def _c_final_score(self, args, turn):
-        score = self.root.score()
+        if self.rollout_score_n:
+            r = self._rollout_result()
+            if r is None:
+                return False, self.NO_HIP
+            score = r.score
+        else:
+            score = self.root.score()
         if abs(score) < 1e-4:
             return True, "0"
         return True, f"B+{score}" if score > 0 else f"W+{-score}"
@@ -412,18 +448,25 @@ def build_parser():
     ap.add_argument("--precision", choices=["f32", "f16x2"], default=None,
                     help="conv arithmetic: f32 (default, the reference's width) or the opt-in split-fp16 fast path")
     ap.add_argument("--ponder", action="store_true")
+    ap.add_argument("--rollout-score", type=int, default=0, metavar="N",
+                    help="N > 0: final_score and final_status_list from N policy playouts to the end of the game "
+                         "(default 0: the score of the board as it stands)")
     ap.add_argument("--python-tree", action="store_true", help="search with the Python tree instead of the native one")
     return ap
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    ap = build_parser()
+    args = ap.parse_args(argv)
+    if args.rollout_score < 0:
+        ap.error("--rollout-score must not be negative")
 
     from . import nnet
     pi = nnet.HipPolicyNet(load_state_dict(args.p), device_id=args.gpu, precision=args.precision)
     val = nnet.HipValueNet(load_state_dict(args.v), device_id=args.gpu, precision=args.precision)
     cls, root = (GTP, Go_MCTS()) if args.python_tree else (NativeGTP, Position())
-    gtp = cls(root, pi, val, no_sim=not args.simulate, time_lim=None if args.r else args.t, n_rollouts=args.r, pondering=args.ponder)
+    gtp = cls(root, pi, val, no_sim=not args.simulate, time_lim=None if args.r else args.t, n_rollouts=args.r, pondering=args.ponder,
+              rollout_score=args.rollout_score)
     gtp.start()
 
 

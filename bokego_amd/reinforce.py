@@ -1,7 +1,7 @@
 """REINFORCE on policy-vs-policy games against a pool of earlier policies (the reference's bin/selfplay.py:59-208).
 
     python -m bokego_amd.reinforce -w WEIGHTS_DIR [-e E] [-n N] [-b B] [--workers W] [-f STATS] [--lr 1e-5] [--seed S]
-                                   [--opponent ID|random] [--device D] [--precision fp32|bf16]
+                                   [--opponent ID|random] [--device D] [--precision fp32|bf16] [--finish]
 
 The pool is the policy_<id>.pt / .bkw files of -w.  With n = (number of ids) - 1, policy_n is trained; each epoch it
 plays an opponent from the pool (policy_0 when it exists), writes policy_{n+1}.pt and three lines of statistics, and n
@@ -25,6 +25,12 @@ The update differentiates the network that sampled the moves: the eval-mode Trai
 running statistics frozen (train._TrunkBlockEval), which is the function the engine computes with the statistics
 folded in.  Randomness comes only from Philox4x32-10 keyed by --seed with counter (game, ply, iteration, epoch), so
 the same seed and pool give the same checkpoints bit for bit.  DESIGN 12 lists where this departs from the reference.
+
+--finish (play_games(finish=True)): after the last sampled ply the games are played out to two passes in a row
+(rollout.finish_games, pair form: the learner and the opponent keep their colours, the counters run on with the ply),
+and black_wins / reward come from the area score of the finished boards, on which dead stones have been captured.
+The finishing plies contribute no rows to the update.  A game whose turn lags (a side had no legal point at some ply)
+is left out and scored as it stands.
 
 --precision bf16 puts the update's trunk convolutions on bf16 operands (train._Trainable.precision).  The
 playouts keep sampling from the fp32 engine, so the update then differentiates a function whose logits differ slightly
@@ -250,7 +256,25 @@ def _start_positions(start, G):
     return start
 
 
-def _play_games_device(learner, opponent, n_batches, batch_size, key, iteration, epoch, dev, timing, max_turns, pos0):
+def _finish(recs, perm, nb, plies, learner, opponent, key, iteration, epoch, dev, rules):
+    """play_games(finish=True): play out the records recs (slot order: perm[slot] = game, the learner black in slots
+    [0, nb)) whose turn is `plies` -> (the slots played out, rollout.Finished)."""
+    from . import rollout
+    if isinstance(recs, torch.Tensor):
+        turn = recs[:, 172:176].contiguous().view(torch.int32)[:, 0].cpu().numpy()
+    else:
+        turn = rollout.record_turns(recs)
+    sel = np.nonzero(turn == plies)[0]
+    if len(sel) == 0:
+        return sel, None
+    sub = recs.index_select(0, torch.from_numpy(sel).to(recs.device)) if isinstance(recs, torch.Tensor) else recs[sel]
+    fin = rollout.finish_games(sub, (learner, opponent), key, counters=counters(perm[sel], plies, iteration, epoch),
+                               sides=(int((sel < nb).sum()),), rules=rules, device=dev, komi=KOMI)
+    return sel, fin
+
+
+def _play_games_device(learner, opponent, n_batches, batch_size, key, iteration, epoch, dev, timing, max_turns, pos0,
+                       finish=False):
     """play_games(rules="device"): see the module docstring."""
     G, T_ = n_batches * batch_size, max_turns + 1
     learner_black = (np.arange(G) // batch_size) % 2 == 0
@@ -301,6 +325,13 @@ def _play_games_device(learner, opponent, n_batches, batch_size, key, iteration,
         t = lap("rules", t)
     score = T.area_score(pos, KOMI)
     t = lap("score", t)
+    finished = None
+    if finish:
+        sel, fin = _finish(pos, perm, nb, T_, learner, opponent, key, iteration, epoch, dev, "device")
+        if fin is not None:
+            score[torch.from_numpy(sel).to(dev)] = torch.from_numpy(fin.score).to(dev)
+        finished = (perm[sel], fin)
+        t = lap("finish", t)
     back = torch.cat([hist, score.view(torch.int16).view(G, 2), status.view(torch.int16).view(G, 2)], 1).cpu().numpy()
     t = lap("download", t)
     st = np.ascontiguousarray(back[:, T_ + 2:]).view(np.int32)[:, 0]
@@ -309,6 +340,8 @@ def _play_games_device(learner, opponent, n_batches, batch_size, key, iteration,
         raise RuntimeError(f"game {perm[s]}: a sampled move is illegal (status {st[s]}); the legal plane and the rules "
                            "disagree")
     out = Playouts()
+    if finish:
+        out.finished_games, out.finished = finished
     out.moves = np.empty((G, T_), np.int16)
     out.moves[perm] = back[:, :T_]
     scores = np.empty(G, np.float32)
@@ -329,7 +362,7 @@ def _play_games_device(learner, opponent, n_batches, batch_size, key, iteration,
 
 
 def play_games(learner, opponent, n_batches, batch_size, seed, iteration=0, epoch=0, device=None, timing=None,
-               max_turns=POLICY_MAX_TURNS, rules="device", start=None):
+               max_turns=POLICY_MAX_TURNS, rules="device", start=None, finish=False):
     """n_batches * batch_size games in lock-step between two fp32 LeafEngines (policy weights); the learner is black in
     even batches.  rules="device": bkt_play_moves and bkt_area_score, nothing on the host per ply; "host": the host
     rules (bk_features_batch_u8, the upload, bk_pos_play, bk_pos_area_score), the reference the tests and the benchmark
@@ -338,7 +371,11 @@ def play_games(learner, opponent, n_batches, batch_size, seed, iteration=0, epoc
     the phases are then separated by synchronisations, so pass it only to measure.  Device rules: 'engine' (both
     evaluations), 'sampler' (bkt_sample_moves + the move history), 'rules' (the copy of the learner's rows +
     bkt_play_moves), 'score' (bkt_area_score), 'download'.  Host rules: 'host' (features, staging, playing the moves),
-    'engine' (upload + both evaluations) and 'sampler' (bkt_sample_moves + the copy back)."""
+    'engine' (upload + both evaluations) and 'sampler' (bkt_sample_moves + the copy back).
+    finish=True: the games are then played out to the end (rollout.finish_games with the same rules, phase 'finish') and
+    black_wins / reward come from the finished boards; moves, length and the learner's rows are what they are without
+    it.  The Playouts then also has finished_games (the games played out: all but those whose turn lags) and finished
+    (their rollout.Finished, or None when there is none)."""
     if rules not in ("device", "host"):
         raise ValueError(f"rules must be 'device' or 'host', got {rules!r}")
     G = n_batches * batch_size
@@ -347,7 +384,7 @@ def play_games(learner, opponent, n_batches, batch_size, seed, iteration=0, epoc
     key = int(seed) & (2 ** 64 - 1)
     if rules == "device":
         return _play_games_device(learner, opponent, n_batches, batch_size, key, iteration, epoch, dev, timing,
-                                  max_turns, pos)
+                                  max_turns, pos, finish)
     lib, play = go.golib(), _play_fn()
     learner_black = (np.arange(G) // batch_size) % 2 == 0
     hist = np.full((G, max_turns + 1), go.PASS, np.int16)
@@ -418,6 +455,13 @@ def play_games(learner, opponent, n_batches, batch_size, seed, iteration=0, epoc
     out.moves, out.length, out.learner_black = hist, length, learner_black
     scores = np.array([lib.bk_pos_area_score(ctypes.cast(pos[g].ctypes.data, ctypes.POINTER(go.Pos)), KOMI)
                        for g in range(G)], np.float64)
+    if finish:
+        perm = np.concatenate([np.nonzero(learner_black)[0], np.nonzero(~learner_black)[0]])
+        sel, fin = _finish(np.ascontiguousarray(pos[perm]), perm, int(learner_black.sum()), max_turns + 1, learner,
+                           opponent, key, iteration, epoch, dev, "host")
+        if fin is not None:
+            scores[perm[sel]] = fin.score
+        out.finished_games, out.finished = perm[sel], fin
     out.black_wins = scores > 0
     out.reward = np.where(out.black_wins == learner_black, 1.0, -1.0).astype(np.float32)
     if rows_game:
@@ -481,12 +525,12 @@ def engine_weights(net):
     return {k: v.detach() for k, v in net.state_dict().items()}
 
 
-def run_epoch(net, opt, learner_eng, opp_eng, n_iters, n_batches, batch_size, seed, epoch, log=None):
+def run_epoch(net, opt, learner_eng, opp_eng, n_iters, n_batches, batch_size, seed, epoch, log=None, finish=False):
     """n_iters iterations: play, update, hand the new weights to the learner's engine.  -> wins per batch, in order."""
     wins = []
     for it in range(n_iters):
         t0 = time.perf_counter()
-        games = play_games(learner_eng, opp_eng, n_batches, batch_size, seed, iteration=it, epoch=epoch)
+        games = play_games(learner_eng, opp_eng, n_batches, batch_size, seed, iteration=it, epoch=epoch, finish=finish)
         losses = update(net, opt, games, n_batches, batch_size)
         learner_eng.set_weights(engine_weights(net))
         w = wins_per_batch(games, n_batches, batch_size)
@@ -522,6 +566,8 @@ def _parse(argv):
     ap.add_argument("--precision", choices=list(T.PRECISIONS), default="fp32",
                     help="bf16: the update's trunk convolutions on bf16 operands with fp32 accumulation (the playouts "
                          "stay on the fp32 engine)")
+    ap.add_argument("--finish", action="store_true",
+                    help="play every game out to the end after the last sampled ply; rewards from the finished boards")
     args = ap.parse_args(argv)
     for flag, v in (("-e", args.e), ("-n", args.n), ("-b", args.b), ("--workers", args.workers)):
         if v < 1:
@@ -564,7 +610,7 @@ def main(argv=None):
             t0 = time.perf_counter()
             try:
                 wins = run_epoch(net, opt, learner_eng, opp_eng, args.n, args.workers, args.b, args.seed, n,
-                                 log=lambda d: print(json.dumps(d), flush=True))
+                                 log=lambda d: print(json.dumps(d), flush=True), finish=args.finish)
             finally:
                 opp_eng.close()
             dt = time.perf_counter() - t0

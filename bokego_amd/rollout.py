@@ -1,0 +1,434 @@
+"""Play positions out to the end of the game on the device and score the settled boards.
+
+    python -m bokego_amd.rollout --sgf FILE [--move K] -p POLICY [-n 256] [--seed S] [--komi 5.5] [--device D]
+
+finish_games plays every record on, both colours, until two passes in a row end the game: the side to move samples from
+the policy (or uniformly, engine=None) among its *playable* points -- legal, and not its own one-point eye as the
+reference's go.possible_eye defines one -- and passes when it has none.  Neither side can then destroy its own living
+groups, so dead stones get captured, open regions get filled, and the raw Tromp-Taylor area of the final board
+(bkt_area_score) is the result of the game.  rollout_score averages n such playouts per position into a score, an
+ownership map and the status (alive / dead / seki) of every stone, which is what the reference asks GNU Go for.
+
+Lock-step on the device.  One bkt_playout_step with every move BKT_MOVE_NONE gives the planes and the playable sets of
+the start records; then per ply LeafEngine.eval_device (logits), bkt_sample_moves_masked on the playable set, one write
+into the device move history, and bkt_playout_step, which plays the move or the pass, keeps the `over` flag of a game
+that has ended and writes the next planes and playable set.  No host work, download or synchronisation per ply: the
+host looks at `over` once every CHECK_EVERY plies and stops when every game is over, or at max_plies.  Simple ko only:
+a game can cycle, and the cap is what ends it; it is then scored as it stands and counted in `unfinished`.
+
+Randomness is Philox4x32-10 keyed by the seed with a counter per game and ply, never per row: by default
+(g mod 2^32, the record's turn + plies played here, g >> 32, 2) -- tag 2 keeps the draws apart from genvals' tags 0
+and 1 -- or the caller's own layout (counters=) whose second word runs on with the ply.
+
+rules="host" is the same loop on the host rules with the same draws (bk_pos_play, bk_pos_liberties, bk_pos_is_legal,
+bk_pos_possible_eye, bk_features_batch_u8, bk_pos_area_score, reinforce.sample_host in float64): the reference the
+tests compare the device with.  With engine=None it needs no GPU.
+"""
+import argparse
+import ctypes
+import json
+
+import numpy as np
+
+from . import go
+from . import reinforce as R
+
+MAX_PLIES = 400            # default cap of finish_games: 2.8x the longest playout measured (142 plies)
+CHECK_EVERY = 16           # plies between two looks at `over`
+STREAM_ROLLOUT = 2         # counter word 3 (genvals uses 0 and 1)
+MOVE_NONE = -2             # BKT_MOVE_NONE; in the history: the game was over before this ply
+SEKI_THRESHOLD = 0.5       # |mean ownership| of a stone's point below this: the stone is in seki (rollout_score)
+POS_BYTES = R.POS_BYTES
+_PP = ctypes.POINTER(go.Pos)
+
+
+class Finished:
+    """What finish_games returns, rows in the order of `pos`.
+
+    records     uint8 [G,192]   the final bk_pos records (a device tensor with rules="device", numpy with "host")
+    moves       int16 [G,L]     (numpy) the move at each ply played here: a point, -1 = pass, -2 = the game was over;
+                                L = the longest game
+    over        bool [G]        two passes in a row ended the game
+    plies       int64 [G]       plies played here, the two passes included
+    score       float32 [G]     area score of the final record (black - (white + komi))
+    owner       int8 [G,81]     +1 black stone or black-only region, -1 white, 0 neither
+    unfinished  int             rows not over at the cap
+    min_margin  float64 [G]     rules="host" only: the smallest reinforce.cdf_margin among the game's draws
+    """
+
+
+def default_counters(n, turns):
+    """(g mod 2^32, turn, g >> 32, 2) for the games g = 0 .. n-1, int32 [n, 4]."""
+    g = np.arange(n, dtype=np.uint64)
+    c = np.empty((n, 4), np.uint32)
+    c[:, 0] = g & np.uint64(0xFFFFFFFF)
+    c[:, 1] = np.asarray(turns, np.int64).astype(np.uint32)
+    c[:, 2] = g >> np.uint64(32)
+    c[:, 3] = STREAM_ROLLOUT
+    return c.view(np.int32)
+
+
+def record_turns(recs):
+    """The `turn` field of bk_pos records uint8 [n, 192] (numpy)."""
+    return np.ascontiguousarray(recs[:, 172:176]).view(np.int32)[:, 0].copy()
+
+
+def playable_host(recs):
+    """bool [n,81]: bk_pos_is_legal(p, s) and bk_pos_possible_eye(p, s) != the colour to move (black on an even turn)."""
+    lib = go.golib()
+    out = np.zeros((len(recs), 81), bool)
+    buf = (ctypes.c_uint8 * 81)()
+    for i in range(len(recs)):
+        p = ctypes.cast(recs[i].ctypes.data, _PP)
+        lib.bk_pos_legal_moves(p, buf)
+        mover = 2 if p.contents.turn & 1 else 1
+        for s in range(81):
+            if buf[s] and lib.bk_pos_possible_eye(p, s) != mover:
+                out[i, s] = True
+    return out
+
+
+def _engines(engine, sides, G):
+    """-> (None | one engine | (a, b), n0)."""
+    if isinstance(engine, (tuple, list)):
+        if len(engine) != 2 or sides is None or len(sides) != 1:
+            raise ValueError("the pair form is engine=(engine_black, engine_white) with sides=(n0,)")
+        n0 = int(sides[0])
+        if not 0 <= n0 <= G:
+            raise ValueError(f"sides[0] must be 0..{G}, got {n0}")
+        return tuple(engine), n0
+    if sides is not None:
+        raise ValueError("sides goes with the pair form engine=(engine_black, engine_white)")
+    return engine, G
+
+
+def _check_records(pos, is_tensor):
+    if tuple(pos.shape[1:]) != (POS_BYTES,) or pos.ndim != 2 or (str(pos.dtype) not in ("uint8", "torch.uint8")):
+        raise ValueError(f"pos must be uint8 [G, {POS_BYTES}], got {pos.dtype} {tuple(pos.shape)}")
+    if len(pos) < 1:
+        raise ValueError("pos holds no record")
+
+
+def _logits(eng, planes, black_to_move, n0):
+    """The logits of every row: one engine for all rows, or the pair -- rows [0, n0) by the first engine when black is
+    to move, by the second when white is; rows [n0, G) the other way round."""
+    import torch
+
+    def run(e, x):
+        parts = [e.eval_device(x[s:s + e.max_batch], logits=True, probs=False, value=False)["logits"]
+                 for s in range(0, len(x), e.max_batch)]
+        return parts[0] if len(parts) == 1 else torch.cat(parts)
+
+    if not isinstance(eng, tuple):
+        return run(eng, planes)
+    first, second = eng if black_to_move else eng[::-1]
+    G = len(planes)
+    parts = [run(e, planes[a:b]) for e, a, b in ((first, 0, n0), (second, n0, G)) if b > a]
+    return parts[0] if len(parts) == 1 else torch.cat(parts)
+
+
+def finish_games(pos, engine, seed, counters=None, max_plies=MAX_PLIES, rules="device", device=None, sides=None,
+                 komi=R.KOMI):
+    """Play the records pos (uint8 [G,192], numpy or a tensor; not modified) to the end of the game -> Finished.
+
+    engine: one fp32 LeafEngine with policy weights that plays both colours; None: uniform logits (random eye-safe
+    playouts, no network); or the pair form (engine_black, engine_white) with sides=(n0,): in rows [0, n0) the first
+    engine plays black and the second white, in rows [n0, G) the second plays black and the first white (the two
+    slices of reinforce.play_games) -- every record must then have the same parity of turn (ValueError otherwise).
+    counters: int32 [G,4] Philox counter words of the first ply; word 1 runs on with the ply.  Default: default_counters.
+    """
+    if rules not in ("device", "host"):
+        raise ValueError(f"rules must be 'device' or 'host', got {rules!r}")
+    max_plies = int(max_plies)
+    if max_plies < 1:
+        raise ValueError("max_plies must be at least 1")
+    is_tensor = not isinstance(pos, np.ndarray)
+    _check_records(pos, is_tensor)
+    G = len(pos)
+    eng, n0 = _engines(engine, sides, G)
+    turns = None
+    if counters is None or isinstance(eng, tuple):
+        turns = record_turns(pos.cpu().numpy() if is_tensor else pos)
+    black_first = True
+    if isinstance(eng, tuple):
+        if len(set((turns & 1).tolist())) != 1:
+            raise ValueError("the pair form needs every record at the same parity of turn")
+        black_first = int(turns[0]) % 2 == 0
+    if counters is None:
+        counters = default_counters(G, turns)
+    key = int(seed) & (2 ** 64 - 1)
+    if rules == "host":
+        ctr = np.array(counters.cpu().numpy() if hasattr(counters, "cpu") else counters, np.int32)
+        if ctr.shape != (G, 4):
+            raise ValueError(f"counters must be int32 [{G}, 4]")
+        recs = np.array(pos.cpu().numpy() if is_tensor else pos, np.uint8, order="C")
+        return _finish_host(recs, eng, n0, black_first, key, ctr, max_plies, device, komi)
+    return _finish_device(pos, eng, n0, black_first, key, counters, max_plies, device, komi)
+
+
+def _finish_device(pos, eng, n0, black_first, key, counters, max_plies, device, komi):
+    import torch
+
+    from . import _trainlib as T
+
+    any_eng = eng[0] if isinstance(eng, tuple) else eng
+    if device is not None:
+        dev = torch.device(device)
+    elif any_eng is not None:
+        dev = torch.device("cuda", any_eng.device_id)
+    elif isinstance(pos, torch.Tensor) and pos.is_cuda:
+        dev = pos.device
+    else:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    G = len(pos)
+    if G > T.MAX_BATCH:
+        raise ValueError(f"at most {T.MAX_BATCH} games per call, got {G}")
+    pos = (pos.to(dev) if isinstance(pos, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(pos)).to(dev))
+    pos = pos.contiguous().clone()
+    ctr = (counters.to(dev) if isinstance(counters, torch.Tensor) else
+           torch.from_numpy(np.ascontiguousarray(counters, np.int32)).to(dev)).contiguous().clone()
+    if tuple(ctr.shape) != (G, 4) or ctr.dtype != torch.int32:
+        raise ValueError(f"counters must be int32 [{G}, 4]")
+    planes = torch.empty((G, 27, 9, 9), dtype=torch.uint8, device=dev) if eng is not None else None
+    playable = torch.empty((G, 81), dtype=torch.uint8, device=dev)
+    over = torch.zeros((G,), dtype=torch.uint8, device=dev)
+    none = torch.full((G,), MOVE_NONE, dtype=torch.int32, device=dev)
+    hist = torch.full((G, max_plies), MOVE_NONE, dtype=torch.int16, device=dev)
+    uniform = torch.zeros((G, 81), dtype=torch.float32, device=dev) if eng is None else None
+    status = T.playout_step(pos, none, over, planes, playable)            # the start planes and playable sets
+    for k in range(max_plies):
+        if k:
+            ctr[:, 1] += 1
+            if k % CHECK_EVERY == 0 and bool(over.all()):                 # the only look at the device inside the loop
+                break
+        logits = uniform if eng is None else _logits(eng, planes, black_first == (k % 2 == 0), n0)
+        moves, _ = T.sample_moves_masked(logits, playable, key, ctr)
+        moves = torch.where(over != 0, none, moves)
+        hist[:, k] = moves
+        status |= T.playout_step(pos, moves, over, planes, playable)
+    score, owner = T.area_score(pos, komi, owner=True)
+    out = Finished()
+    out.records = pos
+    moves = hist.cpu().numpy()
+    if status.any().item():
+        s = int(torch.nonzero(status)[0, 0])
+        raise RuntimeError(f"row {s}: a sampled move is illegal (status {int(status[s])}); the playable set and the rules "
+                           "disagree")
+    out.plies = (moves > MOVE_NONE).sum(1).astype(np.int64)
+    out.moves = np.ascontiguousarray(moves[:, :max(int(out.plies.max()), 1)])
+    out.over = over.cpu().numpy() != 0
+    out.score, out.owner = score.cpu().numpy(), owner.cpu().numpy()
+    out.unfinished = int((~out.over).sum())
+    return out
+
+
+def _finish_host(recs, eng, n0, black_first, key, ctr, max_plies, device, komi):
+    lib, play = go.golib(), R._play_fn()
+    G = len(recs)
+    over = np.zeros(G, bool)
+    hist = np.full((G, max_plies), MOVE_NONE, np.int16)
+    margin = np.full(G, np.inf)
+    kw = R.seed_key(key)
+    tmp = (ctypes.c_uint8 * 81)()
+    if eng is not None:
+        import torch
+
+        any_eng = eng[0] if isinstance(eng, tuple) else eng
+        dev = torch.device("cuda", any_eng.device_id) if device is None else torch.device(device)
+        feats = np.empty((G, 27, 9, 9), np.uint8)
+    for k in range(max_plies):
+        if over.all():
+            break
+        if k:
+            ctr[:, 1] += 1
+        live = np.nonzero(~over)[0]
+        if eng is None:
+            logits = np.zeros((G, 81))
+        else:                                                             # every row, so that the pair's slices stay put
+            R.features_batch(recs, feats.ctypes.data)
+            logits = _logits(eng, torch.from_numpy(feats).to(dev), black_first == (k % 2 == 0), n0)
+            logits = logits.cpu().numpy().astype(np.float64)
+        ok = playable_host(recs[live])
+        u = R.uniform(R.philox4x32_10(ctr[live].view(np.uint32), kw)[:, 0])
+        mv, _ = R.sample_host(logits[live], ok, u)
+        margin[live] = np.minimum(margin[live], R.cdf_margin(logits[live], u))
+        hist[live, k] = mv
+        for g, m in zip(live.tolist(), mv.tolist()):
+            p = ctypes.cast(recs[g].ctypes.data, _PP)
+            if m < 0 and p.contents.last_move == go.PASS:
+                over[g] = True
+            if play(recs[g].ctypes.data, m):
+                raise RuntimeError(f"row {g}: sampled move {m} is illegal; the playable set and the rules disagree")
+            lib.bk_pos_liberties(p, tmp)
+    out = Finished()
+    out.records = recs
+    out.plies = (hist > MOVE_NONE).sum(1).astype(np.int64)
+    out.moves = np.ascontiguousarray(hist[:, :max(int(out.plies.max()), 1)])
+    out.over = over
+    out.score = np.array([lib.bk_pos_area_score(ctypes.cast(recs[g].ctypes.data, _PP), komi) for g in range(G)],
+                         np.float32)
+    out.owner = owner_host(recs)
+    out.unfinished = int((~over).sum())
+    out.min_margin = margin
+    return out
+
+
+def owner_host(recs):
+    """bkt_area_score's owner on the host: int8 [n,81], +1 black stone or black-only empty region, -1 white, 0 neither."""
+    out = np.zeros((len(recs), 81), np.int8)
+    for i in range(len(recs)):
+        b = recs[i, :81].view(np.int8)
+        out[i] = np.where(b == 1, 1, np.where(b == 2, -1, 0))
+        seen = np.zeros(81, bool)
+        for s in range(81):
+            if b[s] != 0 or seen[s]:
+                continue
+            region, stack, touch = [], [s], set()
+            seen[s] = True
+            while stack:
+                q = stack.pop()
+                region.append(q)
+                for t in go.NEIGHBORS[q]:
+                    if b[t] != 0:
+                        touch.add(int(b[t]))
+                    elif not seen[t]:
+                        seen[t] = True
+                        stack.append(t)
+            if touch == {1}:
+                out[i, region] = 1
+            elif touch == {2}:
+                out[i, region] = -1
+    return out
+
+
+# ---- the Monte-Carlo score ------------------------------------------------------------------------------------------------
+class RolloutScore:
+    """rollout_score's result for one position.
+
+    mean_owner  float64 [81]   mean of the final owner over the n playouts (+1 black ... -1 white)
+    black_win   float          share of playouts black won (final area score > 0)
+    mean_score  float          mean final area score
+    score       float          area by majority ownership: (points with mean > 0) - ((points with mean < 0) + komi)
+    status      list [81]      None for an empty point, else "alive", "dead" or "seki"
+    """
+
+    def stones(self, status):
+        return [s for s in range(81) if self.status[s] == status]
+
+
+def _as_records(positions):
+    if isinstance(positions, np.ndarray) and positions.dtype == np.uint8:
+        recs = positions.reshape(-1, POS_BYTES)
+    else:
+        if isinstance(positions, go.Game):
+            positions = [positions]
+        recs = np.stack([np.frombuffer(bytes(g._pos), np.uint8) for g in positions])
+    return np.ascontiguousarray(recs)
+
+
+def rollout_score(positions, engine, n=256, seed=0, komi=R.KOMI, rules="device", max_plies=MAX_PLIES, device=None):
+    """n playouts (finish_games) of every position -> a list of RolloutScore.  positions: go.Game objects or uint8
+    [P,192] records.  Playout j of position i is game i * n + j of one finish_games call: deterministic per seed."""
+    recs = _as_records(positions)
+    n = int(n)
+    if n < 1:
+        raise ValueError("n must be at least 1")
+    P = len(recs)
+    fin = finish_games(np.repeat(recs, n, 0), engine, seed, max_plies=max_plies, rules=rules, device=device, komi=komi)
+    owner = fin.owner.reshape(P, n, 81).astype(np.float64).mean(1)
+    score = fin.score.reshape(P, n).astype(np.float64)
+    out = []
+    for i in range(P):
+        r = RolloutScore()
+        r.mean_owner = owner[i]
+        r.black_win = float((score[i] > 0).mean())
+        r.mean_score = float(score[i].mean())
+        r.score = float((owner[i] > 0).sum()) - (float((owner[i] < 0).sum()) + float(komi))
+        board = recs[i, :81].view(np.int8)
+        r.status = [None] * 81
+        for s in np.nonzero(board)[0].tolist():
+            sign = 1.0 if board[s] == 1 else -1.0
+            m = owner[i, s]
+            r.status[s] = "seki" if abs(m) < SEKI_THRESHOLD else ("alive" if m * sign > 0 else "dead")
+        r.unfinished = int((~fin.over.reshape(P, n)[i]).sum())
+        out.append(r)
+    return out
+
+
+def format_score(score):
+    """GTP's final_score answer: B+3.5, W+2.5 or 0."""
+    return "0" if score == 0 else f"{'B' if score > 0 else 'W'}+{abs(score):g}"
+
+
+def owner_board(mean_owner):
+    """Nine lines: X / O where the mean ownership is beyond +-SEKI_THRESHOLD, x / o for a weaker lean, . for none."""
+    rows = []
+    for r in range(9):
+        cells = []
+        for c in range(9):
+            m = mean_owner[9 * r + c]
+            cells.append("X" if m >= SEKI_THRESHOLD else "O" if m <= -SEKI_THRESHOLD else "x" if m > 0 else
+                         "o" if m < 0 else ".")
+        rows.append(" ".join(cells))
+    return "\n".join(rows)
+
+
+# ---- the command line --------------------------------------------------------------------------------------------------------
+def _parse(argv):
+    ap = argparse.ArgumentParser(description="Score a position of an SGF by policy playouts to the end of the game")
+    ap.add_argument("--sgf", required=True, help="the game record")
+    ap.add_argument("--move", type=int, default=None, help="score the position after K moves (default: the last)")
+    ap.add_argument("-p", dest="p", metavar="POLICY", default=None,
+                    help="policy weights (.pt or .bkw); without it the playouts are uniformly random")
+    ap.add_argument("-n", dest="n", type=int, default=256, help="playouts")
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--komi", type=float, default=R.KOMI)
+    ap.add_argument("--device", type=int, default=0)
+    args = ap.parse_args(argv)
+    if args.n < 1:
+        ap.error("-n must be at least 1")
+    if args.move is not None and args.move < 0:
+        ap.error("--move must not be negative")
+    if not (0 <= args.seed < 2 ** 64):
+        ap.error("--seed must be an unsigned 64-bit integer")
+    return args
+
+
+def sgf_position(path, move=None):
+    """The position after `move` moves of the SGF (all of them by default)."""
+    moves = go.get_moves(path)
+    g = go.Game()
+    for mv in moves[:len(moves) if move is None else move]:
+        if mv == go.PASS:
+            g.play_pass()
+        else:
+            g.play_move(mv)
+    return g
+
+
+def main(argv=None):
+    import torch
+
+    args = _parse(argv)
+    game = sgf_position(args.sgf, args.move)
+    torch.cuda.set_device(args.device)
+    eng = None
+    if args.p is not None:
+        from .train import load_weights
+
+        eng = R.policy_engine(load_weights(args.p), args.device, min(args.n, 4096))
+    try:
+        r = rollout_score([game], eng, n=args.n, seed=args.seed, komi=args.komi,
+                          device=torch.device("cuda", args.device))[0]
+    finally:
+        if eng is not None:
+            eng.close()
+    print(json.dumps({"score": format_score(r.score), "black_win": r.black_win, "mean_score": r.mean_score,
+                      "dead": [go.unsquash(s) for s in r.stones("dead")],
+                      "seki": [go.unsquash(s) for s in r.stones("seki")], "playouts": args.n,
+                      "unfinished": r.unfinished}))
+    print(owner_board(r.mean_owner))
+
+
+if __name__ == "__main__":
+    main()

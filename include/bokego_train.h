@@ -156,6 +156,12 @@ int bkt_bn_relu_eval_backward(const float *dy, const float *y, const float *x, c
 int bkt_sample_moves(const float *logits, const uint8_t *planes, int batch, uint64_t seed, const uint32_t *counters,
                      int32_t *moves, float *logp, void *stream);
 
+/* bkt_sample_moves with the acceptable set read from mask[b * mask_stride + i] != 0 (i < 81) instead of plane 5: the same
+ * softmax, the same draw, the same replacement of a sample outside the set, -1 when the set is empty (a playout passes).
+ * bkt_sample_moves(logits, planes, ...) IS bkt_sample_moves_masked(logits, planes + 5 * 81, 27 * 81, ...): one kernel. */
+int bkt_sample_moves_masked(const float *logits, const uint8_t *mask, size_t mask_stride, int batch, uint64_t seed,
+                            const uint32_t *counters, int32_t *moves, float *logp, void *stream);
+
 /* ---- the Go rules on the device (reinforce.py, genvals.py; bk_playout.hip) --------------------------------------------- */
 
 /* For each row b < batch: if moves[b] >= 0, play it on the 192-byte record pos[b] (bk_pos, include/bokego_go.h) and
@@ -166,6 +172,20 @@ int bkt_sample_moves(const float *logits, const uint8_t *planes, int batch, uint
  * Byte identity with the host: every record afterwards equals what bk_pos_play(p, m) followed by
  * bk_pos_liberties(p, tmp) leaves, all 192 bytes (board, libs, libs_valid, ko, last move, turn, hash, reserved). */
 int bkt_play_moves(void *pos, const int32_t *moves, int batch, int32_t *status, uint8_t *planes, void *stream);
+
+/* One ply of a playout that runs to the end of the game (bokego_amd/rollout.py).  Per row b < batch:
+ *   over != NULL && over[b] != 0      the record is untouched, status[b] = 0 (the game has ended);
+ *   moves[b] >= 0                     exactly bkt_play_moves;
+ *   moves[b] == BK_PASS (-1)          the record becomes what bk_pos_play(p, BK_PASS) + bk_pos_liberties(p, tmp) leaves, all
+ *                                     192 bytes; if its last move was already BK_PASS and over != NULL, over[b] = 1;
+ *   moves[b] <= BKT_MOVE_NONE         the record is untouched, status[b] = 0.
+ * planes (may be NULL): as bkt_play_moves.  playable (may be NULL) [batch, 81]: for the record as it stands after the call,
+ * 1 where the side to move may play in a playout: bk_pos_is_legal(p, s) && bk_pos_possible_eye(p, s) != the mover's colour
+ * (black on an even turn) -- it never fills its own one-point eye, by the reference's definition of one.
+ * 1 <= batch <= BKT_MAX_BATCH, else BKT_ERR_ARG. */
+#define BKT_MOVE_NONE (-2)
+int bkt_playout_step(void *pos, const int32_t *moves, int batch, uint8_t *over, int32_t *status, uint8_t *planes,
+                     uint8_t *playable, void *stream);
 
 /* For each row b < batch: score[b] = bk_pos_area_score(&pos[b], komi) -- Tromp-Taylor area: stones, plus empty regions
  * bordered by one colour only; black - (white + komi), computed as (float)black - ((float)white + komi).
