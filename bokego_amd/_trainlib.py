@@ -44,11 +44,13 @@ SYMBOLS = {
     "bkt_play_moves": (_I, [_P, _P, _I, _P, _P, _P]),
     "bkt_playout_step": (_I, [_P, _P, _I, _P, _P, _P, _P, _P]),
     "bkt_area_score": (_I, [_P, _I, _F, _P, _P, _P]),
+    "bkt_random_playouts": (_I, [_P, _I, _U64, _P, _I, _P, _P, _P, _P, _P]),
 }
 MAX_BATCH = 65536          # BKT_MAX_BATCH
 PRECISIONS = ("fp32", "bf16")
 POS_BYTES = 192            # sizeof(bk_pos)
 MOVE_NONE = -2             # BKT_MOVE_NONE: bkt_playout_step leaves the row alone
+MAX_PLAYOUT_PLIES = 1024   # BKT_MAX_PLAYOUT_PLIES
 
 _lib = None
 
@@ -348,3 +350,28 @@ def area_score(pos, komi=5.5, owner=False):
                                  None if own is None else _dev(own, "owner", dtype=torch.int8), _stream(pos)),
            "bkt_area_score")
     return (score, own) if owner else score
+
+
+def random_playouts(pos, seed, counters, max_plies, over=None, history=True):
+    """Whole uniformly random playouts in one launch, in place (bkt_random_playouts): pos uint8 [B,192], counters int32
+    [B,4] (the Philox counter words of ply 0; word 1 runs on with the ply), 1 <= max_plies <= MAX_PLAYOUT_PLIES.  over: None
+    (no game has ended) or uint8 [B], updated in place; rows whose flag is set are left alone.
+    -> (over uint8 [B], plies int32 [B], moves int16 [B,max_plies] or None with history=False, status int32 [B])."""
+    if pos.dim() != 2 or pos.shape[1] != POS_BYTES:
+        raise ValueError(f"pos must be [B, {POS_BYTES}], got {tuple(pos.shape)}")
+    B, max_plies = int(pos.shape[0]), int(max_plies)
+    if not 1 <= B <= MAX_BATCH:
+        raise ValueError(f"batch must be 1..{MAX_BATCH}, got {B}")
+    if not 1 <= max_plies <= MAX_PLAYOUT_PLIES:
+        raise ValueError(f"max_plies must be 1..{MAX_PLAYOUT_PLIES}, got {max_plies}")
+    if over is None:
+        over = torch.zeros((B,), dtype=torch.uint8, device=pos.device)
+    plies = torch.empty((B,), dtype=torch.int32, device=pos.device)
+    status = torch.empty((B,), dtype=torch.int32, device=pos.device)
+    moves = torch.empty((B, max_plies), dtype=torch.int16, device=pos.device) if history else None
+    _check(load().bkt_random_playouts(_dev(pos, "pos", dtype=torch.uint8), B, int(seed) & (2 ** 64 - 1),
+                                      _dev(counters, "counters", (B, 4), torch.int32), max_plies,
+                                      _dev(over, "over", (B,), torch.uint8), _dev(plies, "plies", dtype=torch.int32),
+                                      None if moves is None else _dev(moves, "moves", dtype=torch.int16),
+                                      _dev(status, "status", dtype=torch.int32), _stream(pos)), "bkt_random_playouts")
+    return over, plies, moves, status

@@ -14,6 +14,10 @@ Replies are pinned against a transcript recorded from the reference (tests/golde
 position (N policy playouts to the end of the game on the device: dead stones are captured before the count), and the
 standard command `final_status_list alive|dead|seki` is added.  Both need the HIP engine.  N = 0, the default, keeps the
 score of the board as it stands and the reference's command list.
+
+`--playout-value N` (N > 0) searches without a value net: the value of a leaf is the share of N uniformly random playouts
+its side to move wins (rollout.PlayoutEvaluator).  Not together with `-v`, `--simulate` or `--python-tree`; it
+needs the HIP engine as `--rollout-score` does.
 """
 import argparse
 import os
@@ -440,7 +444,8 @@ def build_parser():
     ap.add_argument("-t", metavar="SEC", type=float, default=10.0, help="time limit in seconds for each move")
     ap.add_argument("-r", type=int, default=None, help="number of rollouts per move (overrides -t)")
     ap.add_argument("-p", metavar="PATH", default=os.path.join(golden, "policy_19.bkw"), help="policy weights (.pt/.bkw)")
-    ap.add_argument("-v", metavar="PATH", default=os.path.join(golden, "value_synth.bkw"), help="value weights (.pt/.bkw)")
+    ap.add_argument("-v", metavar="PATH", default=os.path.join(golden, "value_synth.bkw"), action=_Given,
+                    help="value weights (.pt/.bkw)")
     ap.add_argument("-g", "--gpu", type=int, nargs="?", const=0, default=0, metavar="INDEX",
                     help="GPU index (default 0; the networks always run on the GPU -- a bare -g is accepted as in the reference)")
     ap.add_argument("--simulate", action="store_true",
@@ -451,22 +456,49 @@ def build_parser():
     ap.add_argument("--rollout-score", type=int, default=0, metavar="N",
                     help="N > 0: final_score and final_status_list from N policy playouts to the end of the game "
                          "(default 0: the score of the board as it stands)")
+    ap.add_argument("--playout-value", type=int, default=0, metavar="N",
+                    help="N > 0: no value net -- a leaf's value is the share of N uniformly random playouts its side to move "
+                         "wins (not with -v, --simulate or --python-tree)")
     ap.add_argument("--python-tree", action="store_true", help="search with the Python tree instead of the native one")
+    ap.set_defaults(v_given=False)
     return ap
 
 
-def main(argv=None):
+class _Given(argparse.Action):
+    """store, and note that the flag was on the command line (its default does not count as a choice)"""
+
+    def __call__(self, parser, namespace, values, option_string=None):
+        setattr(namespace, self.dest, values)
+        setattr(namespace, self.dest + "_given", True)
+
+
+def parse_args(argv=None):
+    """build_parser's result, with the combinations of flags that make no sense refused (SystemExit, as argparse does)."""
     ap = build_parser()
     args = ap.parse_args(argv)
     if args.rollout_score < 0:
         ap.error("--rollout-score must not be negative")
+    if args.playout_value < 0:
+        ap.error("--playout-value must not be negative")
+    if args.playout_value:
+        for flag, on in (("-v", args.v_given), ("--simulate", args.simulate), ("--python-tree", args.python_tree)):
+            if on:
+                ap.error(f"--playout-value takes the place of a value net: not allowed with {flag}")
+    return args
+
+
+def main(argv=None):
+    args = parse_args(argv)
 
     from . import nnet
     pi = nnet.HipPolicyNet(load_state_dict(args.p), device_id=args.gpu, precision=args.precision)
-    val = nnet.HipValueNet(load_state_dict(args.v), device_id=args.gpu, precision=args.precision)
+    val = None
+    if not args.playout_value:
+        val = nnet.HipValueNet(load_state_dict(args.v), device_id=args.gpu, precision=args.precision)
     cls, root = (GTP, Go_MCTS()) if args.python_tree else (NativeGTP, Position())
+    more = {"playout_value": args.playout_value} if args.playout_value else {}
     gtp = cls(root, pi, val, no_sim=not args.simulate, time_lim=None if args.r else args.t, n_rollouts=args.r, pondering=args.ponder,
-              rollout_score=args.rollout_score)
+              rollout_score=args.rollout_score, **more)
     gtp.start()
 
 

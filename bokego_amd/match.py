@@ -220,7 +220,7 @@ def play_match(a, b, n_games=10, komi=5.5, out_sgf=None, opening_plies=0, seed=0
             "ms_per_move": {a.name: float(np.mean(ms[0])), b.name: float(np.mean(ms[1]))}, "records": games}
 
 
-def main(argv=None):
+def parse_args(argv=None):
     import os
     golden = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden")
     ap = argparse.ArgumentParser(description="GTP match: the HIP MCTS engine vs an opponent")
@@ -228,6 +228,9 @@ def main(argv=None):
     ap.add_argument("-r", type=int, default=400, help="rollouts per move of the HIP engine")
     ap.add_argument("-p", default=os.path.join(golden, "policy_19.bkw"))
     ap.add_argument("-v", default=os.path.join(golden, "value_synth.bkw"))
+    ap.add_argument("--playout-value", type=int, default=0, metavar="N",
+                    help="N > 0: the in-process engine searches without a value net, on the Monte-Carlo value of N random "
+                         "playouts (-v is then not loaded; not with --engine)")
     ap.add_argument("--opponent", default="policy", help='"policy" (raw policy, no search) or a GTP command line')
     ap.add_argument("--komi", type=float, default=5.5)
     ap.add_argument("--sgf", default=None, help="prefix for SGF records")
@@ -240,13 +243,26 @@ def main(argv=None):
     ap.add_argument("--opponent-name", default=None)
     ap.add_argument("--json-out", default=None, help="also write the result (without the move records) to this file")
     args = ap.parse_args(argv)
+    if args.playout_value < 0:
+        ap.error("--playout-value must not be negative")
+    if args.playout_value and args.engine is not None:
+        ap.error("--playout-value configures the in-process engine: it does not go with --engine")
+    return args
+
+
+def main(argv=None):
+    args = parse_args(argv)
     pi = None
     if args.engine is None or args.opponent == "policy":
         from . import nnet
         from .gtp import NativeGTP, load_state_dict
         from .mcts_native import Position
         pi = nnet.HipPolicyNet(load_state_dict(args.p), precision=args.precision)
-    if args.engine is None:
+    if args.engine is None and args.playout_value > 0:
+        a = InProcessEngine(NativeGTP(Position(), pi, None, no_sim=True, time_lim=None, n_rollouts=args.r,
+                                      playout_value=args.playout_value),
+                            name=args.engine_name or f"boke-hip-r{args.r}-mc{args.playout_value}")
+    elif args.engine is None:
         val = nnet.HipValueNet(load_state_dict(args.v), precision=args.precision)
         a = InProcessEngine(NativeGTP(Position(), pi, val, no_sim=True, time_lim=None, n_rollouts=args.r),
                             name=args.engine_name or f"boke-hip-r{args.r}")

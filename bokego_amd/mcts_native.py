@@ -131,12 +131,24 @@ class _ChildrenView(Mapping):
 
 class NativeMCTS:
     """kwargs as the reference's MCTS: expand_thresh, exploration_weight, noise_weight, device; plus
-    `evaluator` (anything with __call__(feats_u8, n_policy) -> (probs, values)) and `max_batch`."""
+    `evaluator` (anything with __call__(feats_u8, n_policy) -> (probs, values)) and `max_batch`; `playout_value=N` (with
+    `playout_seed`, and `playout_rules="host"` for the host mirror where there is no GPU): rollout.PlayoutEvaluator."""
 
     def __init__(self, root=None, policy_net=None, value_net=None, **kwargs):
         if policy_net is None and kwargs.get("evaluator") is None:
             raise TypeError("Missing required keywork argument: 'policy_net'")
         self.no_sim = kwargs.get("no_sim", True)
+        # OPT-IN, not the reference's search: playout_value=N > 0 -- no value net; a leaf's value is the share of N uniformly
+        # random playouts its side to move wins (rollout.PlayoutEvaluator on the policy net's engine; DESIGN 16).
+        self.playout_value = int(kwargs.get("playout_value") or 0)
+        self.playout_seed = int(kwargs.get("playout_seed", 0))
+        self.playout_rules = kwargs.get("playout_rules", "device")     # "host": the playouts on the host rules, the same bits
+        if self.playout_value:
+            if self.playout_value < 0:
+                raise ValueError("playout_value must not be negative")
+            if value_net is not None or not self.no_sim or kwargs.get("evaluator") is not None:
+                raise TypeError("playout_value=N goes with policy_net alone: no value_net, no evaluator, no_sim=True")
+            kwargs = dict(kwargs, evaluator=self._playout_evaluator(policy_net))
         if value_net is None and self.no_sim and kwargs.get("evaluator") is None:
             raise TypeError("Keyword argument 'value_net' is required for no simulation mode")
         # no_sim=False (boke.py --simulate; mcts.py:58,147-148): rollouts end in a policy playout, bk_search_params.simulate.
@@ -197,8 +209,31 @@ class NativeMCTS:
         self._pump()
 
     # ---- plumbing ------------------------------------------------------------------------------------
+    NO_HIP = "rollout scoring needs the HIP backend"
+
+    @property
+    def komi(self):
+        return self._tree_komi
+
+    @komi.setter
+    def komi(self, komi):
+        """The tree's komi (the root's, or what GTP's `komi` set): playout_value=N scores its playouts with it.  An
+        `evaluator=` of the caller's keeps the komi it was built with."""
+        self._tree_komi = komi
+        if self.playout_value:
+            self.evaluator.komi = komi
+
+    def _playout_evaluator(self, policy_net):
+        get = getattr(policy_net, "engine", None)
+        if not callable(get):
+            raise RuntimeError(self.NO_HIP)
+        from . import rollout
+        return rollout.PlayoutEvaluator(get(), self.playout_value, seed=self.playout_seed, rules=self.playout_rules)
+
     def _evaluator_from_nets(self):
         policy_net, value_net = self.policy_net, self.value_net
+        if getattr(self, "playout_value", 0):
+            return self._playout_evaluator(policy_net)
         if isinstance(policy_net, nnet.HipPolicyNet) and isinstance(value_net, nnet.HipValueNet):
             return selfplay.EngineEvaluator(nnet.fuse(policy_net, value_net, self._max_batch))
         if isinstance(policy_net, nnet.HipPolicyNet) and value_net is None:

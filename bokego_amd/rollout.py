@@ -20,6 +20,15 @@ Randomness is Philox4x32-10 keyed by the seed with a counter per game and ply, n
 (g mod 2^32, the record's turn + plies played here, g >> 32, 2) -- tag 2 keeps the draws apart from genvals' tags 0
 and 1 -- or the caller's own layout (counters=) whose second word runs on with the ply.
 
+random_playouts is the engine=None case without the lock-step: no network sits between two plies, so ONE launch
+(bkt_random_playouts) plays every game to its end, each workgroup looping over the plies of its three records (DESIGN
+16).  Its choice among the n playable points is integer arithmetic on the Philox word -- the ((x0 >> 8) * n) >> 24-th
+point in ascending order -- so the host mirror (rules="host") equals the device bit for bit, with no margin to excuse.
+playout_value turns it into the classical Monte-Carlo value of a position, the share of n such playouts the side to
+move wins, and PlayoutEvaluator hands that value to the tree search in place of a value net (priors from the policy).
+
+    python -m bokego_amd.rollout --sgf FILE [--move K] --random [-n 256] [--seed S]      # the one-launch playouts
+
 rules="host" is the same loop on the host rules with the same draws (bk_pos_play, bk_pos_liberties, bk_pos_is_legal,
 bk_pos_possible_eye, bk_features_batch_u8, bk_pos_area_score, reinforce.sample_host in float64): the reference the
 tests compare the device with.  With engine=None it needs no GPU.
@@ -36,10 +45,15 @@ from . import reinforce as R
 MAX_PLIES = 400            # default cap of finish_games: 2.8x the longest playout measured (142 plies)
 CHECK_EVERY = 16           # plies between two looks at `over`
 STREAM_ROLLOUT = 2         # counter word 3 (genvals uses 0 and 1)
+STREAM_VALUE = 3           # playout_value: word 3 of playout j is 4 * j + STREAM_VALUE (0..2 stay with the above)
 MOVE_NONE = -2             # BKT_MOVE_NONE; in the history: the game was over before this ply
 SEKI_THRESHOLD = 0.5       # |mean ownership| of a stone's point below this: the stone is in seki (rollout_score)
 POS_BYTES = R.POS_BYTES
 _PP = ctypes.POINTER(go.Pos)
+
+__all__ = ["MAX_PLIES", "MOVE_NONE", "Finished", "PlayoutEvaluator", "RolloutScore", "default_counters", "finish_games",
+           "format_score", "owner_board", "owner_host", "playable_host", "playout_value", "random_playouts", "record_turns",
+           "rollout_score", "sgf_position"]
 
 
 class Finished:
@@ -301,6 +315,262 @@ def owner_host(recs):
     return out
 
 
+# ---- whole random playouts in one launch, and the Monte-Carlo value ----------------------------------------------------------
+def select_index(x0, n):
+    """The rank, among n playable points in ascending order, that the Philox word x0 selects: ((x0 >> 8) * n) >> 24, in
+    [0, n) for n >= 1 (and 0 for n = 0: the row passes).  24 x 7 bits: exact in 32-bit unsigned arithmetic on the device."""
+    return ((np.asarray(x0, np.uint64) >> np.uint64(8)) * np.asarray(n, np.uint64)) >> np.uint64(24)
+
+
+def _counters_array(counters, G):
+    ctr = np.array(counters.cpu().numpy() if hasattr(counters, "cpu") else counters, np.int32)
+    if ctr.shape != (G, 4):
+        raise ValueError(f"counters must be int32 [{G}, 4]")
+    return ctr
+
+
+def random_playouts(pos, seed, counters=None, max_plies=MAX_PLIES, rules="device", komi=R.KOMI, history=True, device=None):
+    """Play the records pos (uint8 [G,192], numpy or a tensor; not modified) to the end of the game with uniformly random
+    eye-safe moves -> Finished, the fields finish_games returns (moves is None with history=False; no min_margin: nothing
+    is rounded).  rules="device": one bkt_random_playouts launch per T.MAX_BATCH rows, then bkt_area_score.  rules="host":
+    the mirror on bk_pos_play / bk_pos_is_legal / bk_pos_possible_eye and reinforce.philox4x32_10; it needs no GPU and
+    gives the same bits.  counters: int32 [G,4], the Philox counter words of ply 0 (word 1 runs on with the ply); default:
+    default_counters, as finish_games.  A row's game depends on its record, the seed and its counters only.
+    These are not finish_games(engine=None)'s games: that sampler goes through a float CDF."""
+    if rules not in ("device", "host"):
+        raise ValueError(f"rules must be 'device' or 'host', got {rules!r}")
+    max_plies = int(max_plies)
+    if not 1 <= max_plies <= 1024:
+        raise ValueError("max_plies must be 1..1024 (BKT_MAX_PLAYOUT_PLIES)")
+    is_tensor = not isinstance(pos, np.ndarray)
+    _check_records(pos, is_tensor)
+    G = len(pos)
+    if counters is None:
+        counters = default_counters(G, record_turns(pos.cpu().numpy() if is_tensor else pos))
+    key = int(seed) & (2 ** 64 - 1)
+    if rules == "host":
+        recs = np.array(pos.cpu().numpy() if is_tensor else pos, np.uint8, order="C")
+        return _random_host(recs, key, _counters_array(counters, G), max_plies, komi, history)
+    return _random_device(pos, key, counters, max_plies, komi, history, device)
+
+
+def _device_of(pos, device):
+    import torch
+
+    if device is not None:
+        return torch.device(device)
+    if isinstance(pos, torch.Tensor) and pos.is_cuda:
+        return pos.device
+    return torch.device("cuda", torch.cuda.current_device())
+
+
+def _play_random_device(pos, key, ctr, max_plies, history):
+    """pos uint8 [G,192] and ctr int32 [G,4] on the device; pos is played on in place.
+    -> (over uint8 [G], plies int32 [G], moves int16 [G,max_plies] or None, status int32 [G]), T.MAX_BATCH rows per launch."""
+    import torch
+
+    from . import _trainlib as T
+
+    parts = [T.random_playouts(pos[s:s + T.MAX_BATCH], key, ctr[s:s + T.MAX_BATCH], max_plies, history=history)
+             for s in range(0, len(pos), T.MAX_BATCH)]
+    if len(parts) == 1:
+        return parts[0]
+    return tuple(None if col[0] is None else torch.cat(col) for col in zip(*parts))
+
+
+def _area_score_device(pos, komi, owner):
+    import torch
+
+    from . import _trainlib as T
+
+    parts = [T.area_score(pos[s:s + T.MAX_BATCH], komi, owner=owner) for s in range(0, len(pos), T.MAX_BATCH)]
+    if len(parts) == 1:
+        return parts[0]
+    return tuple(torch.cat(col) for col in zip(*parts)) if owner else torch.cat(parts)
+
+
+def _random_device(pos, key, counters, max_plies, komi, history, device):
+    import torch
+
+    dev = _device_of(pos, device)
+    G = len(pos)
+    pos = (pos.to(dev) if isinstance(pos, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(pos)).to(dev))
+    pos = pos.contiguous().clone()
+    ctr = (counters.to(dev) if isinstance(counters, torch.Tensor) else
+           torch.from_numpy(np.ascontiguousarray(counters, np.int32)).to(dev)).contiguous()
+    if tuple(ctr.shape) != (G, 4) or ctr.dtype != torch.int32:
+        raise ValueError(f"counters must be int32 [{G}, 4]")
+    over, plies, moves, status = _play_random_device(pos, key, ctr, max_plies, history)
+    score, owner = _area_score_device(pos, komi, True)
+    if status.any().item():
+        s = int(torch.nonzero(status)[0, 0])
+        raise RuntimeError(f"row {s}: a selected move is illegal (status {int(status[s])}); the playable set and the rules "
+                           "disagree")
+    out = Finished()
+    out.records = pos
+    out.plies = plies.cpu().numpy().astype(np.int64)
+    out.moves = None
+    if history:
+        out.moves = np.ascontiguousarray(moves[:, :max(int(out.plies.max()), 1)].cpu().numpy())
+    out.over = over.cpu().numpy() != 0
+    out.score, out.owner = score.cpu().numpy(), owner.cpu().numpy()
+    out.unfinished = int((~out.over).sum())
+    return out
+
+
+def _random_host(recs, key, ctr, max_plies, komi, history):
+    lib, play = go.golib(), R._play_fn()
+    G = len(recs)
+    over = np.zeros(G, bool)
+    plies = np.zeros(G, np.int64)
+    hist = np.full((G, max_plies), MOVE_NONE, np.int16)
+    kw = R.seed_key(key)
+    ctr = ctr.view(np.uint32).copy()
+    tmp = (ctypes.c_uint8 * 81)()
+    for k in range(max_plies):
+        if over.all():
+            break
+        if k:
+            ctr[:, 1] += np.uint32(1)                                      # wraps at 2^32, as the kernel's c1 + k
+        live = np.nonzero(~over)[0]
+        ok = playable_host(recs[live])
+        idx = select_index(R.philox4x32_10(ctr[live], kw)[:, 0], ok.sum(1))
+        for g, row, i in zip(live.tolist(), ok, idx.tolist()):
+            points = np.nonzero(row)[0]
+            m = int(points[i]) if len(points) else go.PASS
+            hist[g, k] = m
+            plies[g] += 1
+            p = ctypes.cast(recs[g].ctypes.data, _PP)
+            if m < 0 and p.contents.last_move == go.PASS:
+                over[g] = True
+            if play(recs[g].ctypes.data, m):
+                raise RuntimeError(f"row {g}: selected move {m} is illegal; the playable set and the rules disagree")
+            lib.bk_pos_liberties(p, tmp)
+    out = Finished()
+    out.records = recs
+    out.plies = plies
+    out.moves = np.ascontiguousarray(hist[:, :max(int(plies.max()), 1)]) if history else None
+    out.over = over
+    out.score = np.array([lib.bk_pos_area_score(ctypes.cast(recs[g].ctypes.data, _PP), komi) for g in range(G)],
+                         np.float32)
+    out.owner = owner_host(recs)
+    out.unfinished = int((~over).sum())
+    return out
+
+
+def value_counters(recs, n):
+    """The Philox counters of playout_value, int32 [R * n, 4] (numpy): playout j of a record whose Zobrist field is h uses
+    (h & 0xFFFFFFFF, 0, h >> 32, 4 * j + STREAM_VALUE) -- the record names its own draws, never its row."""
+    h = np.ascontiguousarray(recs[:, 184:192]).view(np.uint32)            # [R, 2]: the low and the high word
+    c = np.zeros((len(recs), n, 4), np.uint32)
+    c[:, :, 0] = h[:, :1]
+    c[:, :, 2] = h[:, 1:]
+    c[:, :, 3] = 4 * np.arange(n, dtype=np.uint32) + STREAM_VALUE
+    return c.reshape(-1, 4).view(np.int32)
+
+
+def _check_playouts(n):
+    n = int(n)
+    if not 1 <= n < 2 ** 30:
+        raise ValueError("the number of playouts must be at least 1 (and below 2^30)")
+    return n
+
+
+def _playout_value_device(recs, n, key, komi, max_plies=MAX_PLIES):
+    """recs: a uint8 [R,192] tensor on the device -> float32 [R] on the device; nothing here waits for the device."""
+    import torch
+
+    R_ = len(recs)
+    pos = recs.repeat_interleave(n, 0)                                     # a copy: the caller's records stay
+    ctr = torch.zeros((R_, n, 4), dtype=torch.int32, device=recs.device)
+    h = recs[:, 184:192].contiguous().view(torch.int32)                    # [R, 2]: the low and the high word of the hash
+    ctr[:, :, 0] = h[:, :1]
+    ctr[:, :, 2] = h[:, 1:]
+    ctr[:, :, 3] = 4 * torch.arange(n, dtype=torch.int32, device=recs.device) + STREAM_VALUE
+    _play_random_device(pos, key, ctr.view(-1, 4), max_plies, False)
+    black_wins = _area_score_device(pos, komi, False).view(R_, n) > 0
+    black_to_move = (recs[:, 172] & 1) == 0                                # the low byte of `turn`
+    w = (black_wins == black_to_move[:, None]).sum(1)
+    return (2 * w - n).to(torch.float32) / n
+
+
+def playout_value(recs, n, seed, rules="device", komi=R.KOMI, device=None):
+    """The Monte-Carlo value of each record, float32 [R] (numpy): (2 w - n) / n, w = the number of n uniformly random
+    eye-safe playouts (random_playouts, capped at MAX_PLIES and then scored as they stand) that the side to move wins --
+    black wins iff the area score is > 0.  A pure function of the record, `seed` and `n` (value_counters): the row index
+    and the rest of the batch do not enter.  recs: uint8 [R,192], numpy or a tensor."""
+    if rules not in ("device", "host"):
+        raise ValueError(f"rules must be 'device' or 'host', got {rules!r}")
+    n = _check_playouts(n)
+    is_tensor = not isinstance(recs, np.ndarray)
+    _check_records(recs, is_tensor)
+    key = int(seed) & (2 ** 64 - 1)
+    if rules == "device":
+        import torch
+
+        dev = _device_of(recs, device)
+        t = recs.to(dev) if is_tensor else torch.from_numpy(np.ascontiguousarray(recs)).to(dev)
+        return _playout_value_device(t.contiguous(), n, key, komi).cpu().numpy()
+    recs = np.array(recs.cpu().numpy() if is_tensor else recs, np.uint8, order="C")
+    fin = _random_host(np.repeat(recs, n, 0), key, value_counters(recs, n), MAX_PLIES, komi, False)
+    black_wins = fin.score.reshape(len(recs), n) > 0
+    black_to_move = (record_turns(recs) & 1) == 0
+    w = (black_wins == black_to_move[:, None]).sum(1)
+    return ((2 * w - n).astype(np.float32) / np.float32(n)).astype(np.float32)
+
+
+class PlayoutEvaluator:
+    """A tree-search evaluator (NativeMCTS(evaluator=), selfplay.self_play, the GTP front-end) without a value net: the
+    priors of a request's first n_policy rows come from `engine` (a LeafEngine with policy weights, asked as
+    selfplay.EngineEvaluator(value=False) asks), the values of all its rows from playout_value(playouts, seed).  The
+    engine's request and the playout launch do not depend on each other and are in flight together between submit and
+    finish.  rules="host": the values from the host mirror (the same bits; for tests).
+    The engine is kept as `policy_engine`, not `engine`: selfplay.run_pools_native hands an evaluator's `engine` to the C
+    step loop as its own bk_evaluator, which would compute no playouts -- this class goes through callback_evaluator."""
+    wants_positions = True
+
+    def __init__(self, engine, playouts=64, seed=0, rules="device", komi=R.KOMI):
+        if rules not in ("device", "host"):
+            raise ValueError(f"rules must be 'device' or 'host', got {rules!r}")
+        self.policy_engine = engine
+        self.playouts = _check_playouts(playouts)
+        self.seed = int(seed) & (2 ** 64 - 1)
+        self.rules, self.komi = rules, komi
+        self.positions = self.batches = 0
+
+    def submit(self, recs, n_policy):
+        recs = np.ascontiguousarray(recs, np.uint8)
+        if recs.ndim != 2 or recs.shape[1] != POS_BYTES:
+            raise ValueError(f"a PlayoutEvaluator takes position records uint8 [B, {POS_BYTES}], got {recs.shape}")
+        self.positions += len(recs)
+        self.batches += 1
+        ticket = None
+        if n_policy:
+            ticket = self.policy_engine.submit_positions(recs[:n_policy], logits=False, probs=True, value=False,
+                                                         n_policy=n_policy)
+        if self.rules == "host":
+            values = playout_value(recs, self.playouts, self.seed, rules="host", komi=self.komi)
+        else:
+            import torch
+
+            dev = torch.device("cuda", self.policy_engine.device_id)
+            values = _playout_value_device(torch.from_numpy(recs).to(dev), self.playouts, self.seed, self.komi)
+        return ticket, values
+
+    def finish(self, handle, normalise=None):
+        ticket, values = handle
+        if ticket is None:
+            probs = np.zeros((0, 81), np.float32)
+        else:
+            if normalise is None:
+                from .selfplay import normalise_like_categorical as normalise
+            probs = normalise(self.policy_engine.wait(ticket)["probs"])
+        return probs, (values if isinstance(values, np.ndarray) else values.cpu().numpy())
+
+    def __call__(self, recs, n_policy):
+        return self.finish(self.submit(recs, n_policy))
+
+
 # ---- the Monte-Carlo score ------------------------------------------------------------------------------------------------
 class RolloutScore:
     """rollout_score's result for one position.
@@ -326,15 +596,23 @@ def _as_records(positions):
     return np.ascontiguousarray(recs)
 
 
-def rollout_score(positions, engine, n=256, seed=0, komi=R.KOMI, rules="device", max_plies=MAX_PLIES, device=None):
+def rollout_score(positions, engine, n=256, seed=0, komi=R.KOMI, rules="device", max_plies=MAX_PLIES, device=None,
+                  one_launch=False):
     """n playouts (finish_games) of every position -> a list of RolloutScore.  positions: go.Game objects or uint8
-    [P,192] records.  Playout j of position i is game i * n + j of one finish_games call: deterministic per seed."""
+    [P,192] records.  Playout j of position i is game i * n + j of one finish_games call: deterministic per seed.
+    one_launch=True (engine must be None): the uniformly random playouts of random_playouts instead, any number of rows."""
     recs = _as_records(positions)
     n = int(n)
     if n < 1:
         raise ValueError("n must be at least 1")
     P = len(recs)
-    fin = finish_games(np.repeat(recs, n, 0), engine, seed, max_plies=max_plies, rules=rules, device=device, komi=komi)
+    if one_launch:
+        if engine is not None:
+            raise ValueError("one_launch=True plays uniformly random playouts: engine must be None")
+        fin = random_playouts(np.repeat(recs, n, 0), seed, max_plies=max_plies, rules=rules, komi=komi, history=False,
+                              device=device)
+    else:
+        fin = finish_games(np.repeat(recs, n, 0), engine, seed, max_plies=max_plies, rules=rules, device=device, komi=komi)
     owner = fin.owner.reshape(P, n, 81).astype(np.float64).mean(1)
     score = fin.score.reshape(P, n).astype(np.float64)
     out = []
@@ -380,6 +658,8 @@ def _parse(argv):
     ap.add_argument("--move", type=int, default=None, help="score the position after K moves (default: the last)")
     ap.add_argument("-p", dest="p", metavar="POLICY", default=None,
                     help="policy weights (.pt or .bkw); without it the playouts are uniformly random")
+    ap.add_argument("--random", action="store_true",
+                    help="uniformly random playouts, each played to its end inside one kernel launch (not with -p)")
     ap.add_argument("-n", dest="n", type=int, default=256, help="playouts")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--komi", type=float, default=R.KOMI)
@@ -387,6 +667,8 @@ def _parse(argv):
     args = ap.parse_args(argv)
     if args.n < 1:
         ap.error("-n must be at least 1")
+    if args.random and args.p is not None:
+        ap.error("--random plays without a network: not with -p")
     if args.move is not None and args.move < 0:
         ap.error("--move must not be negative")
     if not (0 <= args.seed < 2 ** 64):
@@ -419,7 +701,7 @@ def main(argv=None):
         eng = R.policy_engine(load_weights(args.p), args.device, min(args.n, 4096))
     try:
         r = rollout_score([game], eng, n=args.n, seed=args.seed, komi=args.komi,
-                          device=torch.device("cuda", args.device))[0]
+                          device=torch.device("cuda", args.device), one_launch=args.random)[0]
     finally:
         if eng is not None:
             eng.close()

@@ -193,6 +193,28 @@ int bkt_playout_step(void *pos, const int32_t *moves, int batch, uint8_t *over, 
  * The records are read only.  1 <= batch <= BKT_MAX_BATCH; komi must be finite; else BKT_ERR_ARG. */
 int bkt_area_score(const void *pos, int batch, float komi, float *score, int8_t *owner, void *stream);
 
+/* Whole uniformly random playouts in ONE launch (bokego_amd/rollout.py random_playouts, playout_value): every
+ * row b < batch plays on, in place, until two passes in a row end its game or max_plies moves have been played here.
+ * Ply k = 0, 1, ... of a row that is not over:
+ *   P = the playable set of the record as it stands (bkt_playout_step's `playable`: bk_pos_is_legal and not the mover's
+ *       own eye by bk_pos_possible_eye), n = |P|;
+ *   x0 = the first word of Philox4x32-10 with key (seed low word, seed high word) and counter (c0, c1 + k, c2, c3), where
+ *       (c0, c1, c2, c3) = counters[b] and c1 + k wraps at 2^32;
+ *   the move is BK_PASS when n == 0, else the (((x0 >> 8) * n) >> 24)-th point of P in ascending point order (integer
+ *       arithmetic, uniform up to n * 2^-24; no float, no fallback rule);
+ *   it is played exactly as bkt_playout_step plays it, all 192 bytes; a pass after a pass sets over[b] = 1.
+ * A record whose last move is BK_PASS on entry ends with its first pass.  A row whose over[b] != 0 on entry is untouched
+ * and gets plies[b] = 0.
+ * plies[b] = the moves played here, passes included.  moves (may be NULL) [batch, max_plies] int16: the move of each ply,
+ * BKT_MOVE_NONE from the ply at which the row was over (every entry is written).  status[b] = the bitwise or of the
+ * BK_ILLEGAL_* codes of the row's plies (0: the playable set and the rules agree).  No feature planes are written; score
+ * the final records with bkt_area_score.
+ * 1 <= batch <= BKT_MAX_BATCH and 1 <= max_plies <= BKT_MAX_PLAYOUT_PLIES; pos, counters, over, plies and status must not
+ * be NULL; else BKT_ERR_ARG and nothing is launched. */
+#define BKT_MAX_PLAYOUT_PLIES 1024
+int bkt_random_playouts(void *pos, int batch, uint64_t seed, const uint32_t *counters, int max_plies, uint8_t *over,
+                        int32_t *plies, int16_t *moves, int32_t *status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
