@@ -268,9 +268,13 @@ def bn_relu_eval_backward(dy, y, x, gamma, running_mean, running_var, eps=BN_EPS
     return dx, dg, db
 
 
-def sample_moves(logits, planes, seed, counters):
-    """One move per row: logits [B,81] f32, planes uint8 [B,27,9,9] (plane 5: legal points), counters int32 [B,4]
-    (the Philox counter words, read as uint32) -> (moves int32 [B], -1 where no point is legal; logp f32 [B])."""
+def seed_u64(seed):
+    """A seed as the unsigned 64-bit integer the kernels take (the Philox key)."""
+    return int(seed) & (2 ** 64 - 1)
+
+
+def _sample(name, logits, mask_args, seed, counters):
+    """sample_moves / sample_moves_masked: mask_args(B) checks the second tensor and gives its arguments of the C call."""
     if logits.dim() != 2 or logits.shape[1] != 81:
         raise ValueError(f"logits must be [B, 81], got {tuple(logits.shape)}")
     B = int(logits.shape[0])
@@ -278,39 +282,41 @@ def sample_moves(logits, planes, seed, counters):
     logp = torch.empty((B,), dtype=torch.float32, device=logits.device)
     if B == 0:
         return moves, logp
-    _check(load().bkt_sample_moves(_dev(logits, "logits"), _dev(planes, "planes", (B, 27, 9, 9), torch.uint8), B,
-                                   int(seed) & (2 ** 64 - 1), _dev(counters, "counters", (B, 4), torch.int32),
-                                   _dev(moves, "moves", dtype=torch.int32), _dev(logp, "logp"), _stream(logits)),
-           "bkt_sample_moves")
+    _check(getattr(load(), name)(_dev(logits, "logits"), *mask_args(B), B, seed_u64(seed),
+                                 _dev(counters, "counters", (B, 4), torch.int32),
+                                 _dev(moves, "moves", dtype=torch.int32), _dev(logp, "logp"), _stream(logits)), name)
     return moves, logp
+
+
+def sample_moves(logits, planes, seed, counters):
+    """One move per row: logits [B,81] f32, planes uint8 [B,27,9,9] (plane 5: legal points), counters int32 [B,4]
+    (the Philox counter words, read as uint32) -> (moves int32 [B], -1 where no point is legal; logp f32 [B])."""
+    return _sample("bkt_sample_moves", logits, lambda B: (_dev(planes, "planes", (B, 27, 9, 9), torch.uint8),), seed,
+                   counters)
 
 
 def sample_moves_masked(logits, mask, seed, counters):
     """sample_moves with the acceptable points given as mask uint8 [B,81] (non-zero: may be played) instead of the legal
     plane: the same kernel, the same draw; -1 where a row's mask is empty."""
-    if logits.dim() != 2 or logits.shape[1] != 81:
-        raise ValueError(f"logits must be [B, 81], got {tuple(logits.shape)}")
-    B = int(logits.shape[0])
-    moves = torch.empty((B,), dtype=torch.int32, device=logits.device)
-    logp = torch.empty((B,), dtype=torch.float32, device=logits.device)
-    if B == 0:
-        return moves, logp
-    _check(load().bkt_sample_moves_masked(_dev(logits, "logits"), _dev(mask, "mask", (B, 81), torch.uint8), 81, B,
-                                          int(seed) & (2 ** 64 - 1), _dev(counters, "counters", (B, 4), torch.int32),
-                                          _dev(moves, "moves", dtype=torch.int32), _dev(logp, "logp"), _stream(logits)),
-           "bkt_sample_moves_masked")
-    return moves, logp
+    return _sample("bkt_sample_moves_masked", logits, lambda B: (_dev(mask, "mask", (B, 81), torch.uint8), 81), seed,
+                   counters)
+
+
+def _pos_batch(pos, ranged=True):
+    """B of the records pos [B,192]; ranged: ValueError unless 1 <= B <= MAX_BATCH (else the C side refuses it)."""
+    if pos.dim() != 2 or pos.shape[1] != POS_BYTES:
+        raise ValueError(f"pos must be [B, {POS_BYTES}], got {tuple(pos.shape)}")
+    B = int(pos.shape[0])
+    if ranged and not 1 <= B <= MAX_BATCH:
+        raise ValueError(f"batch must be 1..{MAX_BATCH}, got {B}")
+    return B
 
 
 def play_moves(pos, moves, planes=None):
     """The Go rules on the device, in place: pos uint8 [B,192] (bk_pos records), moves int32 [B] (< 0: leave the row
     alone) -> status int32 [B] (0 or BK_ILLEGAL_*; an illegal row is untouched).  planes: None, or uint8 [B,27,9,9]
     that receives the features of every record as it stands afterwards (bk_features_batch_u8's)."""
-    if pos.dim() != 2 or pos.shape[1] != POS_BYTES:
-        raise ValueError(f"pos must be [B, {POS_BYTES}], got {tuple(pos.shape)}")
-    B = int(pos.shape[0])
-    if not 1 <= B <= MAX_BATCH:
-        raise ValueError(f"batch must be 1..{MAX_BATCH}, got {B}")
+    B = _pos_batch(pos)
     status = torch.empty((B,), dtype=torch.int32, device=pos.device)
     pp = None if planes is None else _dev(planes, "planes", (B, 27, 9, 9), torch.uint8)
     _check(load().bkt_play_moves(_dev(pos, "pos", dtype=torch.uint8), _dev(moves, "moves", (B,), torch.int32), B,
@@ -323,11 +329,7 @@ def playout_step(pos, moves, over=None, planes=None, playable=None):
     in a row sets over), leaves rows alone whose move is <= MOVE_NONE or whose over flag is set, and writes playable uint8
     [B,81]: the points the side to move may play in a playout (legal, and not its own one-point eye).  over: None or
     uint8 [B]; planes: None or uint8 [B,27,9,9]; playable: None or uint8 [B,81].  -> status int32 [B]."""
-    if pos.dim() != 2 or pos.shape[1] != POS_BYTES:
-        raise ValueError(f"pos must be [B, {POS_BYTES}], got {tuple(pos.shape)}")
-    B = int(pos.shape[0])
-    if not 1 <= B <= MAX_BATCH:
-        raise ValueError(f"batch must be 1..{MAX_BATCH}, got {B}")
+    B = _pos_batch(pos)
     status = torch.empty((B,), dtype=torch.int32, device=pos.device)
     _check(load().bkt_playout_step(_dev(pos, "pos", dtype=torch.uint8), _dev(moves, "moves", (B,), torch.int32), B,
                                    None if over is None else _dev(over, "over", (B,), torch.uint8),
@@ -341,9 +343,7 @@ def playout_step(pos, moves, over=None, planes=None, playable=None):
 def area_score(pos, komi=5.5, owner=False):
     """bk_pos_area_score of every record, on the device: pos uint8 [B,192] (read only) -> score f32 [B], the host's float
     bit for bit; owner=True: (score, owner int8 [B,81]: +1 black stone or black-only empty region, -1 white, 0 neither)."""
-    if pos.dim() != 2 or pos.shape[1] != POS_BYTES:
-        raise ValueError(f"pos must be [B, {POS_BYTES}], got {tuple(pos.shape)}")
-    B = int(pos.shape[0])
+    B = _pos_batch(pos, ranged=False)
     score = torch.empty((B,), dtype=torch.float32, device=pos.device)
     own = torch.empty((B, 81), dtype=torch.int8, device=pos.device) if owner else None
     _check(load().bkt_area_score(_dev(pos, "pos", dtype=torch.uint8), B, float(komi), _dev(score, "score"),
@@ -357,11 +357,7 @@ def random_playouts(pos, seed, counters, max_plies, over=None, history=True):
     [B,4] (the Philox counter words of ply 0; word 1 runs on with the ply), 1 <= max_plies <= MAX_PLAYOUT_PLIES.  over: None
     (no game has ended) or uint8 [B], updated in place; rows whose flag is set are left alone.
     -> (over uint8 [B], plies int32 [B], moves int16 [B,max_plies] or None with history=False, status int32 [B])."""
-    if pos.dim() != 2 or pos.shape[1] != POS_BYTES:
-        raise ValueError(f"pos must be [B, {POS_BYTES}], got {tuple(pos.shape)}")
-    B, max_plies = int(pos.shape[0]), int(max_plies)
-    if not 1 <= B <= MAX_BATCH:
-        raise ValueError(f"batch must be 1..{MAX_BATCH}, got {B}")
+    B, max_plies = _pos_batch(pos), int(max_plies)
     if not 1 <= max_plies <= MAX_PLAYOUT_PLIES:
         raise ValueError(f"max_plies must be 1..{MAX_PLAYOUT_PLIES}, got {max_plies}")
     if over is None:
@@ -369,7 +365,7 @@ def random_playouts(pos, seed, counters, max_plies, over=None, history=True):
     plies = torch.empty((B,), dtype=torch.int32, device=pos.device)
     status = torch.empty((B,), dtype=torch.int32, device=pos.device)
     moves = torch.empty((B, max_plies), dtype=torch.int16, device=pos.device) if history else None
-    _check(load().bkt_random_playouts(_dev(pos, "pos", dtype=torch.uint8), B, int(seed) & (2 ** 64 - 1),
+    _check(load().bkt_random_playouts(_dev(pos, "pos", dtype=torch.uint8), B, seed_u64(seed),
                                       _dev(counters, "counters", (B, 4), torch.int32), max_plies,
                                       _dev(over, "over", (B,), torch.uint8), _dev(plies, "plies", dtype=torch.int32),
                                       None if moves is None else _dev(moves, "moves", dtype=torch.int16),

@@ -16,15 +16,16 @@ sorts its games by r_g once, so at ply p the RL rows (r_g < p), the rows at thei
 bkt_play_moves call per ply plays the moves and writes the next ply's planes.  bkt_area_score scores the final records.
 Per pass the host downloads the kept records, the scores and the moves; it does no work and no synchronisation per ply.
 
-Randomness comes only from Philox4x32-10 keyed by --seed (reinforce.philox4x32_10 is the numpy mirror).  Counters
-depend on the game's global id g, never on its batch or row, so the output does not depend on --batch:
-    move at ply p (SL, random or RL):  (g mod 2^32, p, g >> 32, 0)  -> bkt_sample_moves
-    r_g:                               (g mod 2^32, 0, g >> 32, 1)  -> r_g = 70 + floor(20 * u), u = (x0 >> 8) * 2^-24
+Randomness comes only from Philox4x32-10 keyed by --seed (lockstep.philox4x32_10 is the numpy mirror).  Counters
+depend on the game's global id g, never on its batch or row, so the output does not depend on --batch
+(lockstep.game_counters, whose table names the streams):
+    move at ply p (SL, random or RL):  (g mod 2^32, p, g >> 32, STREAM_MOVE)  -> bkt_sample_moves
+    r_g:                               (g mod 2^32, 0, g >> 32, STREAM_R)     -> r_g = 70 + floor(20 * u), u = (x0 >> 8) * 2^-24
 The random move is bkt_sample_moves on masked logits (0 on the legal points of plane 5, -inf elsewhere): the first
 point whose prefix count of legal points exceeds u * (number of legal points), -1 when there is none.
 
 --finish (generate(finish=True)): after turn 90 the RL policy plays the game out, both colours, to two passes in a row
-(rollout.finish_games, counters (g mod 2^32, p, g >> 32, 0) running on with p = 90, 91, ...), and the label comes from
+(rollout.finish_games, the move counters running on with p = 90, 91, ...), and the label comes from
 the area score of the finished board, on which dead stones have been captured.  The stored rows are the same; only
 val can differ.
 
@@ -42,42 +43,31 @@ import torch
 
 from . import _trainlib as T
 from . import go
+from . import lockstep as L
 from . import reinforce as R
 
 MAX_TURNS = 90
 R_LOW, R_HIGH = 70, 90           # r_g in [R_LOW, R_HIGH)
-KOMI = R.KOMI
+KOMI = L.KOMI
 HEADER = "board,ko,last,turn,val"
-STREAM_MOVE, STREAM_R = 0, 1     # counter word 3
 
 
-# ---- counters (documented in the module docstring; the numpy side of every draw) ---------------------------------------
+# ---- counters (the numpy side of every draw) ------------------------------------------------------------------------------
 def move_counters(game_ids, ply):
     """Counter words of the move at `ply` of each game, int32 [n, 4] (the bits bkt_sample_moves reads)."""
-    g = np.asarray(game_ids, np.uint64)
-    c = np.empty((len(g), 4), np.uint32)
-    c[:, 0] = g & np.uint64(0xFFFFFFFF)
-    c[:, 1] = int(ply)
-    c[:, 2] = g >> np.uint64(32)
-    c[:, 3] = STREAM_MOVE
-    return c.view(np.int32)
+    return L.game_counters(game_ids, int(ply), L.STREAM_MOVE)
 
 
 def random_ply(game_ids, seed):
-    """r_g of each game: 70 + floor(20 u), u from the Philox draw with counter (g mod 2^32, 0, g >> 32, 1)."""
-    g = np.asarray(game_ids, np.uint64)
-    c = np.empty((len(g), 4), np.uint32)
-    c[:, 0] = g & np.uint64(0xFFFFFFFF)
-    c[:, 1] = 0
-    c[:, 2] = g >> np.uint64(32)
-    c[:, 3] = STREAM_R
-    u = R.uniform(R.philox4x32_10(c, R.seed_key(seed))[:, 0])
+    """r_g of each game: 70 + floor(20 u), u from the Philox draw of stream STREAM_R."""
+    c = L.game_counters(game_ids, 0, L.STREAM_R).view(np.uint32)
+    u = L.uniform(L.philox4x32_10(c, L.seed_key(seed))[:, 0])
     return (R_LOW + np.floor(u * (R_HIGH - R_LOW))).astype(np.int64)
 
 
 def masked_logits(planes):
     """0 on the legal points (plane 5), -inf elsewhere: bkt_sample_moves then draws a uniformly random legal point."""
-    legal = planes[:, R.LEGAL_PLANE].reshape(-1, 81) != 0
+    legal = planes[:, L.LEGAL_PLANE].reshape(-1, 81) != 0
     return torch.zeros(legal.shape, dtype=torch.float32, device=planes.device).masked_fill_(~legal, float("-inf"))
 
 
@@ -133,56 +123,43 @@ def _record_fields(recs):
     lib, buf = go.golib(), ctypes.create_string_buffer(82)
     boards = []
     for i in range(len(recs)):
-        lib.bk_pos_board_string(ctypes.cast(recs[i].ctypes.data, ctypes.POINTER(go.Pos)), buf)
+        lib.bk_pos_board_string(L.pos_ptr(recs[i]), buf)
         boards.append(buf.value.decode("ascii"))
-    hdr = np.ascontiguousarray(recs[:, 164:176])
-    ko = hdr[:, 0:2].copy().view(np.int16)[:, 0].astype(np.int64)
-    last = hdr[:, 2:4].copy().view(np.int16)[:, 0].astype(np.int64)
-    turn = hdr[:, 8:12].copy().view(np.int32)[:, 0].astype(np.int64)
-    return boards, ko, last, turn
+    return boards, *(f(recs).astype(np.int64) for f in (L.record_ko, L.record_last_move, L.record_turns))
 
 
 def _pass(sl, rl, ids, seed, dev, rules, timing, finish=False):
     """One lock-step pass over the games `ids`, sorted by r_g -> (r, moves, kept records, area scores) in that order."""
     n = len(ids)
     r = random_ply(ids, seed)
-    key = int(seed) & (2 ** 64 - 1)
+    key = L.seed_u64(seed)
     empty_planes = torch.from_numpy(go.Game().features_u8()).to(dev)
     planes = empty_planes.unsqueeze(0).repeat(n, 1, 1, 1)
     ctr = torch.from_numpy(move_counters(ids, 0)).to(dev)
     moves = torch.empty((n,), dtype=torch.int32, device=dev)
     hist = torch.full((n, MAX_TURNS), -1, dtype=torch.int16, device=dev)
-    init = R.initial_positions(n)
+    init = L.initial_positions(n)
     if rules == "device":
         pos = torch.from_numpy(init).to(dev)
         kept = torch.empty_like(pos)
     else:
         pos, kept = init, np.empty_like(init)
-        play, staging = R._play_fn(), torch.empty((n, 27, 9, 9), dtype=torch.uint8).pin_memory()
-    clock = time.perf_counter
-
-    def lap(name, t0):
-        if timing is None:
-            return t0
-        torch.cuda.synchronize(dev)
-        t1 = clock()
-        timing[name] = timing.get(name, 0.0) + (t1 - t0)
-        return t1
-
-    t = clock()
+        staging = torch.empty((n, 27, 9, 9), dtype=torch.uint8).pin_memory()
+    lap = L.phase_clock(dev, timing)
+    t = time.perf_counter()
     for ply in range(MAX_TURNS):
         rl_end = int(np.searchsorted(r, ply, "left"))     # rows [0, rl_end): RL; [rl_end, sl_start): random; rest: SL
         sl_start = int(np.searchsorted(r, ply, "right"))
         if ply:
             ctr[:, 1].fill_(ply)
         if rules == "host":
-            R.features_batch(pos, staging.numpy().ctypes.data)
+            L.features_batch(pos, staging.numpy().ctypes.data)
             planes.copy_(staging, non_blocking=True)
             t = lap("rules", t)
         logits = {}
         for name, eng, a, b in (("rl", rl, 0, rl_end), ("sl", sl, sl_start, n)):
             if b > a:
-                logits[name] = eng.eval_device(planes[a:b], logits=True, probs=False, value=False)["logits"]
+                logits[name] = L.engine_logits([(eng, planes[a:b])])
         t = lap("engine", t)
         for name, a, b in (("rl", 0, rl_end), ("rand", rl_end, sl_start), ("sl", sl_start, n)):
             if b > a:
@@ -196,10 +173,8 @@ def _pass(sl, rl, ids, seed, dev, rules, timing, finish=False):
                 kept[rl_end:sl_start] = pos[rl_end:sl_start]
         else:
             mv = moves.cpu().numpy()
-            base = pos.ctypes.data
-            for i in np.nonzero(mv >= 0)[0].tolist():
-                if play(base + R.POS_BYTES * i, int(mv[i])):
-                    raise RuntimeError(f"game {ids[i]} ply {ply}: sampled move {mv[i]} is illegal")
+            L.play_host(pos, np.nonzero(mv >= 0)[0], mv[mv >= 0],
+                        lambda i, m: f"game {ids[i]} ply {ply}: sampled move {m} is illegal")
             kept[rl_end:sl_start] = pos[rl_end:sl_start]
         t = lap("rules", t)
     if finish:
@@ -214,9 +189,7 @@ def _pass(sl, rl, ids, seed, dev, rules, timing, finish=False):
         t = lap("score", t)
         score, kept = score.cpu().numpy().astype(np.float64), kept.cpu().numpy()
     else:
-        lib = go.golib()
-        score = np.array([lib.bk_pos_area_score(ctypes.cast(pos[i].ctypes.data, ctypes.POINTER(go.Pos)), KOMI)
-                          for i in range(n)], np.float64)
+        score = L.area_score_host(pos, KOMI)
     out = r, hist.cpu().numpy(), kept, score
     lap("download", t)
     return out
@@ -225,13 +198,12 @@ def _pass(sl, rl, ids, seed, dev, rules, timing, finish=False):
 def generate(sl, rl, games, batch, seed, device=None, rules="device", timing=None, finish=False):
     """Play `games` games (ids 0 .. games-1) in passes of `batch`; sl, rl: fp32 LeafEngines (policy weights, max_batch >=
     batch).  rules="device": bkt_play_moves and bkt_area_score; "host": the host rules of reinforce.play_games(rules=
-    "host") (bk_features_batch_u8, the upload, bk_pos_play, bk_pos_area_score), the reference the tests and the benchmark
+    "host") (lockstep: features_batch, the upload, play_host, area_score_host), the reference the tests and the benchmark
     compare against.  timing: a dict that receives seconds per phase ('engine', 'sampler', 'rules', 'download', and
     'score' with the device rules); the phases are then separated by
     synchronisations, so pass it only to measure.  finish: the RL engine plays every game out after turn 90 and the
     score is the finished board's (phase 'finish' instead of 'score').  -> Generated."""
-    if rules not in ("device", "host"):
-        raise ValueError(f"rules must be 'device' or 'host', got {rules!r}")
+    L.check_rules(rules)
     if not 1 <= batch <= T.MAX_BATCH:
         raise ValueError(f"batch must be 1..{T.MAX_BATCH}, got {batch}")
     dev = torch.device("cuda", sl.device_id) if device is None else torch.device(device)

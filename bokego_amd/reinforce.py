@@ -18,8 +18,9 @@ copy of the learner's slice (planes, moves, logp) into preallocated row buffers,
 moves and writes the next ply's planes: no host work, no download and no synchronisation per ply.  bkt_area_score scores
 the final records, and one download brings back the move history and the scores.  The learner's rows stay on the
 device and are the update's batch.  play_games(rules="host") is the same loop with the rules on the host (per ply
-bk_features_batch_u8 on the live games' records, one upload, 4 bytes per game back, bk_pos_play per game, and
-bk_pos_area_score at the end): the reference the tests and the benchmark compare against, identical in every output.
+lockstep.features_batch on the live games' records, one upload, 4 bytes per game back, lockstep.play_host, and
+lockstep.area_score_host at the end): the reference the tests and the benchmark compare against, identical in every
+output.  The host mirrors of the sampler and the host rules live in lockstep.py, shared with genvals and rollout.
 
 The update differentiates the network that sampled the moves: the eval-mode TrainablePolicyNet, BatchNorm with its
 running statistics frozen (train._TrunkBlockEval), which is the function the engine computes with the statistics
@@ -37,7 +38,6 @@ playouts keep sampling from the fp32 engine, so the update then differentiates a
 from the ones the moves were sampled from.
 """
 import argparse
-import ctypes
 import json
 import os
 import re
@@ -49,44 +49,13 @@ import torch.nn.functional as F
 
 from . import _trainlib as T
 from . import go
+from . import lockstep as L
+from .lockstep import (KOMI, LEGAL_PLANE, PLANE_BYTES, POS_BYTES, _play_fn, cdf_margin,  # noqa: F401  (the shared
+                       features_batch, initial_positions, philox4x32_10, sample_host,    # pieces, under the names the
+                       seed_key, uniform)                                                # tests and tools know)
 from .selfplay import POLICY_MAX_TURNS
 
-KOMI = 5.5
-LEGAL_PLANE = 5            # nnet.features' "legal" plane (reference nnet.py:198)
-POS_BYTES = 192            # sizeof(bk_pos)
-PLANE_BYTES = 27 * 81
 UPDATE_CHUNK = 32768       # rows per forward/backward of the update (libbktrain's trunk takes up to 65536)
-
-# ---- Philox4x32-10 and the sampler, host mirrors of bk_train.hip (float64) ----------------------------------------------
-PHILOX_M = (0xD2511F53, 0xCD9E8D57)
-PHILOX_W = (0x9E3779B9, 0xBB67AE85)
-_MASK32 = np.uint64(0xFFFFFFFF)
-
-
-def philox4x32_10(ctr, key):
-    """ctr uint32 [..., 4], key uint32 [..., 2] (broadcast) -> uint32 [..., 4] (Random123's philox4x32 with 10 rounds)."""
-    c = [np.asarray(ctr, np.uint64)[..., i] & _MASK32 for i in range(4)]
-    k = np.asarray(key, np.uint64)
-    k0, k1 = k[..., 0] & _MASK32, k[..., 1] & _MASK32
-    for r in range(10):
-        if r:
-            k0 = (k0 + np.uint64(PHILOX_W[0])) & _MASK32
-            k1 = (k1 + np.uint64(PHILOX_W[1])) & _MASK32
-        p0 = np.uint64(PHILOX_M[0]) * c[0]
-        p1 = np.uint64(PHILOX_M[1]) * c[2]
-        c = [(p1 >> np.uint64(32)) ^ c[1] ^ k0, p1 & _MASK32, (p0 >> np.uint64(32)) ^ c[3] ^ k1, p0 & _MASK32]
-    return np.stack(c, -1).astype(np.uint32)
-
-
-def seed_key(seed):
-    """--seed (an unsigned 64-bit integer) -> the Philox key words (low, high)."""
-    s = int(seed) & (2 ** 64 - 1)
-    return np.array([s & 0xFFFFFFFF, s >> 32], np.uint32)
-
-
-def uniform(x0):
-    """The first Philox output word -> u = (x0 >> 8) * 2^-24 in [0, 1), exact in float32 and float64."""
-    return (np.asarray(x0, np.uint32) >> np.uint32(8)).astype(np.float64) * 2.0 ** -24
 
 
 def counters(game_ids, ply, iteration, epoch):
@@ -98,34 +67,6 @@ def counters(game_ids, ply, iteration, epoch):
     c[:, 2] = int(iteration)
     c[:, 3] = int(epoch)
     return c.view(np.int32)
-
-
-def sample_host(logits, legal, u):
-    """bkt_sample_moves in float64: logits [B,81], legal bool [B,81], u [B] -> (moves int32 [B], logp float64 [B]).
-    The move is the first point whose inclusive prefix of p = exp(x - max) exceeds u * sum p; an illegal sample becomes
-    the legal point of the largest logit (lowest index on ties); -1 when no point is legal."""
-    x = np.asarray(logits, np.float64)
-    legal = np.asarray(legal, bool)
-    m = x.max(1, keepdims=True)
-    c = np.cumsum(np.exp(x - m), 1)
-    S = c[:, -1]
-    mv = np.argmax(c > (np.asarray(u, np.float64) * S)[:, None], 1)
-    rows = np.arange(len(x))
-    bad = ~legal[rows, mv]
-    fix = np.argmax(np.where(legal, x, -np.inf), 1)
-    mv = np.where(bad, fix, mv)
-    none = ~legal.any(1)
-    mv[none] = -1
-    logp = np.where(none, 0.0, x[rows, np.maximum(mv, 0)] - m[:, 0] - np.log(S))
-    return mv.astype(np.int32), logp
-
-
-def cdf_margin(logits, u):
-    """min_i |u - CDF_i| over the float64 CDF of each row: how close u lies to a boundary between two points."""
-    x = np.asarray(logits, np.float64)
-    c = np.cumsum(np.exp(x - x.max(1, keepdims=True)), 1)
-    c /= c[:, -1:]
-    return np.abs(c - np.asarray(u, np.float64)[:, None]).min(1)
 
 
 # ---- the loss ----------------------------------------------------------------------------------------------------------
@@ -169,7 +110,7 @@ def choose_opponent(pool, n, seed, epoch, opponent=None):
         return int(opponent)
     if opponent is None and 0 in pool:
         return 0
-    rng = np.random.default_rng([int(seed) & (2 ** 64 - 1), int(epoch)])
+    rng = np.random.default_rng([L.seed_u64(seed), int(epoch)])
     return ids[int(rng.integers(len(ids)))]
 
 
@@ -180,45 +121,6 @@ def stats_lines(n, opp, batch_size, iterations, wins):
 
 
 # ---- lock-step playouts ------------------------------------------------------------------------------------------------
-_PLAY = None
-
-
-def _play_fn():
-    """bk_pos_play taking a plain address (the records live in numpy arrays)."""
-    global _PLAY
-    if _PLAY is None:
-        _PLAY = ctypes.cast(go.golib().bk_pos_play, ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int))
-    return _PLAY
-
-
-FEATURE_THREADS = 8        # bk_features_batch_u8 calls in flight per ply (ctypes releases the GIL during each)
-FEATURE_CHUNK = 512        # positions per call
-_POOL = None
-
-
-def features_batch(recs, out_ptr):
-    """bk_features_batch_u8 over the contiguous bk_pos records recs [n, 192] into out_ptr ([n,27,9,9] uint8), split
-    into chunks encoded on FEATURE_THREADS threads: the records are independent, and so are the calls."""
-    global _POOL
-    lib, n, base = go.golib(), len(recs), recs.ctypes.data
-    if n <= FEATURE_CHUNK:
-        lib.bk_features_batch_u8(base, n, POS_BYTES, out_ptr, 0)
-        return
-    if _POOL is None:
-        from concurrent.futures import ThreadPoolExecutor
-        _POOL = ThreadPoolExecutor(FEATURE_THREADS, thread_name_prefix="bk-features")
-    jobs = [_POOL.submit(lib.bk_features_batch_u8, base + POS_BYTES * s, min(FEATURE_CHUNK, n - s), POS_BYTES,
-                         out_ptr + PLANE_BYTES * s, 0) for s in range(0, n, FEATURE_CHUNK)]
-    for j in jobs:
-        j.result()
-
-
-def initial_positions(n):
-    """n empty-board bk_pos records, uint8 [n, 192]."""
-    one = np.frombuffer(bytes(go.Game()._pos), np.uint8)
-    return np.tile(one, (n, 1))
-
-
 class Playouts:
     """What play_games returns.
 
@@ -243,13 +145,13 @@ class Playouts:
 def _start_positions(start, G):
     """The records play_games starts from, uint8 [G, 192] (a copy): empty boards, or `start` checked."""
     if start is None:
-        return initial_positions(G)
+        return L.initial_positions(G)
     if isinstance(start, torch.Tensor):
         start = start.cpu().numpy()
     start = np.array(start, order="C")
     if start.dtype != np.uint8 or start.shape != (G, POS_BYTES):
         raise ValueError(f"start must be uint8 [{G}, {POS_BYTES}], got {start.dtype} {start.shape}")
-    turn = np.ascontiguousarray(start[:, 172:176]).view(np.int32)[:, 0]
+    turn = L.record_turns(start)
     if (turn != 0).any():
         raise ValueError(f"start: record {int(np.nonzero(turn)[0][0])} has turn {int(turn[turn != 0][0])}; every record "
                          "must have turn 0 (black to move), so that the ply equals the turn")
@@ -260,10 +162,9 @@ def _finish(recs, perm, nb, plies, learner, opponent, key, iteration, epoch, dev
     """play_games(finish=True): play out the records recs (slot order: perm[slot] = game, the learner black in slots
     [0, nb)) whose turn is `plies` -> (the slots played out, rollout.Finished)."""
     from . import rollout
-    if isinstance(recs, torch.Tensor):
-        turn = recs[:, 172:176].contiguous().view(torch.int32)[:, 0].cpu().numpy()
-    else:
-        turn = rollout.record_turns(recs)
+    turn = L.record_turns(recs)
+    if isinstance(turn, torch.Tensor):
+        turn = turn.cpu().numpy()
     sel = np.nonzero(turn == plies)[0]
     if len(sel) == 0:
         return sel, None
@@ -281,17 +182,8 @@ def _play_games_device(learner, opponent, n_batches, batch_size, key, iteration,
     perm = np.concatenate([np.nonzero(learner_black)[0], np.nonzero(~learner_black)[0]])   # slot -> game
     nb = int(learner_black.sum())
     side = (slice(0, nb), slice(nb, G))                   # slots of the learner-is-black / learner-is-white games
-    clock = time.perf_counter
-
-    def lap(name, t0):
-        if timing is None:
-            return t0
-        torch.cuda.synchronize(dev)
-        t1 = clock()
-        timing[name] = timing.get(name, 0.0) + (t1 - t0)
-        return t1
-
-    t = clock()
+    lap = L.phase_clock(dev, timing)
+    t = time.perf_counter()
     pos = torch.from_numpy(pos0[perm]).to(dev)
     ctr = torch.from_numpy(counters(perm, 0, iteration, epoch)).to(dev)
     planes = torch.empty((G, 27, 9, 9), dtype=torch.uint8, device=dev)
@@ -309,9 +201,7 @@ def _play_games_device(learner, opponent, n_batches, batch_size, key, iteration,
         if ply:
             ctr[:, 1].fill_(ply)
         engines = (learner, opponent) if ply % 2 == 0 else (opponent, learner)      # black is to move on even plies
-        logits = [eng.eval_device(planes[sl], logits=True, probs=False, value=False)["logits"]
-                  for eng, sl in zip(engines, side) if sl.stop > sl.start]
-        logits = logits[0] if len(logits) == 1 else torch.cat(logits)
+        logits = L.engine_logits([(eng, planes[sl]) for eng, sl in zip(engines, side)])
         t = lap("engine", t)
         moves, logp = T.sample_moves(logits, planes, key, ctr)
         hist[:, ply] = moves
@@ -335,10 +225,8 @@ def _play_games_device(learner, opponent, n_batches, batch_size, key, iteration,
     back = torch.cat([hist, score.view(torch.int16).view(G, 2), status.view(torch.int16).view(G, 2)], 1).cpu().numpy()
     t = lap("download", t)
     st = np.ascontiguousarray(back[:, T_ + 2:]).view(np.int32)[:, 0]
-    if st.any():
-        s = int(np.nonzero(st)[0][0])
-        raise RuntimeError(f"game {perm[s]}: a sampled move is illegal (status {st[s]}); the legal plane and the rules "
-                           "disagree")
+    L.check_status(st, lambda s, v: f"game {perm[s]}: a sampled move is illegal (status {v}); the legal plane and the "
+                   "rules disagree")
     out = Playouts()
     if finish:
         out.finished_games, out.finished = finished
@@ -365,7 +253,7 @@ def play_games(learner, opponent, n_batches, batch_size, seed, iteration=0, epoc
                max_turns=POLICY_MAX_TURNS, rules="device", start=None, finish=False):
     """n_batches * batch_size games in lock-step between two fp32 LeafEngines (policy weights); the learner is black in
     even batches.  rules="device": bkt_play_moves and bkt_area_score, nothing on the host per ply; "host": the host
-    rules (bk_features_batch_u8, the upload, bk_pos_play, bk_pos_area_score), the reference the tests and the benchmark
+    rules (lockstep: features_batch, the upload, play_host, area_score_host), the reference the tests and the benchmark
     compare against.  Both give the same Playouts, bit for bit.  start: uint8 [G, 192] bk_pos records to play from (game
     g from start[g]), every one with turn 0; default: empty boards.  timing: a dict that receives seconds per phase;
     the phases are then separated by synchronisations, so pass it only to measure.  Device rules: 'engine' (both
@@ -376,16 +264,14 @@ def play_games(learner, opponent, n_batches, batch_size, seed, iteration=0, epoc
     black_wins / reward come from the finished boards; moves, length and the learner's rows are what they are without
     it.  The Playouts then also has finished_games (the games played out: all but those whose turn lags) and finished
     (their rollout.Finished, or None when there is none)."""
-    if rules not in ("device", "host"):
-        raise ValueError(f"rules must be 'device' or 'host', got {rules!r}")
+    L.check_rules(rules)
     G = n_batches * batch_size
     pos = _start_positions(start, G)
     dev = torch.device("cuda", learner.device_id) if device is None else torch.device(device)
-    key = int(seed) & (2 ** 64 - 1)
+    key = L.seed_u64(seed)
     if rules == "device":
         return _play_games_device(learner, opponent, n_batches, batch_size, key, iteration, epoch, dev, timing,
                                   max_turns, pos, finish)
-    lib, play = go.golib(), _play_fn()
     learner_black = (np.arange(G) // batch_size) % 2 == 0
     hist = np.full((G, max_turns + 1), go.PASS, np.int16)
     length = np.zeros(G, np.int64)
@@ -393,17 +279,8 @@ def play_games(learner, opponent, n_batches, batch_size, seed, iteration=0, epoc
     stage = staging.numpy()
     rows_planes, rows_moves, rows_logp, rows_game = [], [], [], []
     live = np.arange(G)
-    clock = time.perf_counter
-
-    def lap(name, t0):
-        if timing is None:
-            return t0
-        torch.cuda.synchronize(dev)
-        t1 = clock()
-        timing[name] = timing.get(name, 0.0) + (t1 - t0)
-        return t1
-
-    t = clock()
+    lap = L.phase_clock(dev, timing)
+    t = time.perf_counter()
     for ply in range(max_turns + 1):
         if len(live) == 0:
             break
@@ -412,28 +289,20 @@ def play_games(learner, opponent, n_batches, batch_size, seed, iteration=0, epoc
         nl, n = int(mine.sum()), len(order)
         recs = np.ascontiguousarray(pos[order])
         stage[:16 * n].view(np.int32)[:] = counters(order, ply, iteration, epoch).reshape(-1)
-        features_batch(recs, stage[16 * n:].ctypes.data)
+        L.features_batch(recs, stage[16 * n:].ctypes.data)
         t = lap("host", t)
         d = staging[:(16 + PLANE_BYTES) * n].to(dev, non_blocking=True)
         ctr = d[:16 * n].view(torch.int32).view(n, 4)
         planes = d[16 * n:].view(n, 27, 9, 9)
-        logits = []
-        if nl:
-            logits.append(learner.eval_device(planes[:nl], logits=True, probs=False, value=False)["logits"])
-        if n > nl:
-            logits.append(opponent.eval_device(planes[nl:], logits=True, probs=False, value=False)["logits"])
-        logits = logits[0] if len(logits) == 1 else torch.cat(logits)
+        logits = L.engine_logits([(learner, planes[:nl]), (opponent, planes[nl:])])
         t = lap("engine", t)
         d_moves, d_logp = T.sample_moves(logits, planes, key, ctr)
         moves = d_moves.cpu().numpy()
         t = lap("sampler", t)
-        base = recs.ctypes.data
-        for r, (addr, mv) in enumerate(zip(range(base, base + POS_BYTES * n, POS_BYTES), moves.tolist())):
-            if mv >= 0 and play(addr, mv):
-                raise RuntimeError(f"game {order[r]} ply {ply}: sampled move {mv} is illegal; the legal plane and "
-                                   "the rules disagree")
-        pos[order] = recs
         ok = moves >= 0
+        L.play_host(recs, np.nonzero(ok)[0], moves[ok], lambda r, mv: f"game {order[r]} ply {ply}: sampled move {mv} is "
+                    "illegal; the legal plane and the rules disagree")
+        pos[order] = recs
         hist[order[ok], ply] = moves[ok]
         length[order[ok]] += 1
         if nl:
@@ -453,8 +322,7 @@ def play_games(learner, opponent, n_batches, batch_size, seed, iteration=0, epoc
 
     out = Playouts()
     out.moves, out.length, out.learner_black = hist, length, learner_black
-    scores = np.array([lib.bk_pos_area_score(ctypes.cast(pos[g].ctypes.data, ctypes.POINTER(go.Pos)), KOMI)
-                       for g in range(G)], np.float64)
+    scores = L.area_score_host(pos, KOMI)
     if finish:
         perm = np.concatenate([np.nonzero(learner_black)[0], np.nonzero(~learner_black)[0]])
         sel, fin = _finish(np.ascontiguousarray(pos[perm]), perm, int(learner_black.sum()), max_turns + 1, learner,

@@ -17,8 +17,9 @@ host looks at `over` once every CHECK_EVERY plies and stops when every game is o
 a game can cycle, and the cap is what ends it; it is then scored as it stands and counted in `unfinished`.
 
 Randomness is Philox4x32-10 keyed by the seed with a counter per game and ply, never per row: by default
-(g mod 2^32, the record's turn + plies played here, g >> 32, 2) -- tag 2 keeps the draws apart from genvals' tags 0
-and 1 -- or the caller's own layout (counters=) whose second word runs on with the ply.
+(g mod 2^32, the record's turn + plies played here, g >> 32, STREAM_ROLLOUT) -- lockstep.py has the table of streams,
+which keeps these draws apart from genvals' -- or the caller's own layout (counters=) whose second word runs on with
+the ply.
 
 random_playouts is the engine=None case without the lock-step: no network sits between two plies, so ONE launch
 (bkt_random_playouts) plays every game to its end, each workgroup looping over the plies of its three records (DESIGN
@@ -29,27 +30,27 @@ move wins, and PlayoutEvaluator hands that value to the tree search in place of 
 
     python -m bokego_amd.rollout --sgf FILE [--move K] --random [-n 256] [--seed S]      # the one-launch playouts
 
-rules="host" is the same loop on the host rules with the same draws (bk_pos_play, bk_pos_liberties, bk_pos_is_legal,
-bk_pos_possible_eye, bk_features_batch_u8, bk_pos_area_score, reinforce.sample_host in float64): the reference the
-tests compare the device with.  With engine=None it needs no GPU.
+rules="host" is one loop (_playout_host) on the host rules with the same draws (lockstep's play_host, features_batch
+and area_score_host, bk_pos_is_legal, bk_pos_possible_eye, lockstep.sample_host in float64): the reference the tests
+compare the device with.  With engine=None it needs no GPU.
 """
 import argparse
 import ctypes
 import json
 
 import numpy as np
+import torch
 
+from . import _trainlib as T
 from . import go
-from . import reinforce as R
+from . import lockstep as L
+from .lockstep import record_turns  # noqa: F401  (public here: see __all__)
 
 MAX_PLIES = 400            # default cap of finish_games: 2.8x the longest playout measured (142 plies, DESIGN 15)
 CHECK_EVERY = 16           # plies between two looks at `over`
-STREAM_ROLLOUT = 2         # counter word 3 (genvals uses 0 and 1)
-STREAM_VALUE = 3           # playout_value: word 3 of playout j is 4 * j + STREAM_VALUE (0..2 stay with the above)
 MOVE_NONE = -2             # BKT_MOVE_NONE; in the history: the game was over before this ply
 SEKI_THRESHOLD = 0.5       # |mean ownership| of a stone's point below this: the stone is in seki (rollout_score)
-POS_BYTES = R.POS_BYTES
-_PP = ctypes.POINTER(go.Pos)
+POS_BYTES = L.POS_BYTES
 
 __all__ = ["MAX_PLIES", "MOVE_NONE", "Finished", "PlayoutEvaluator", "RolloutScore", "default_counters", "finish_games",
            "format_score", "owner_board", "owner_host", "playable_host", "playout_value", "random_playouts", "record_turns",
@@ -67,24 +68,13 @@ class Finished:
     score       float32 [G]     area score of the final record (black - (white + komi))
     owner       int8 [G,81]     +1 black stone or black-only region, -1 white, 0 neither
     unfinished  int             rows not over at the cap
-    min_margin  float64 [G]     rules="host" only: the smallest reinforce.cdf_margin among the game's draws
+    min_margin  float64 [G]     rules="host" only: the smallest lockstep.cdf_margin among the game's draws
     """
 
 
 def default_counters(n, turns):
     """(g mod 2^32, turn, g >> 32, 2) for the games g = 0 .. n-1, int32 [n, 4]."""
-    g = np.arange(n, dtype=np.uint64)
-    c = np.empty((n, 4), np.uint32)
-    c[:, 0] = g & np.uint64(0xFFFFFFFF)
-    c[:, 1] = np.asarray(turns, np.int64).astype(np.uint32)
-    c[:, 2] = g >> np.uint64(32)
-    c[:, 3] = STREAM_ROLLOUT
-    return c.view(np.int32)
-
-
-def record_turns(recs):
-    """The `turn` field of bk_pos records uint8 [n, 192] (numpy)."""
-    return np.ascontiguousarray(recs[:, 172:176]).view(np.int32)[:, 0].copy()
+    return L.game_counters(np.arange(n, dtype=np.uint64), turns, L.STREAM_ROLLOUT)
 
 
 def playable_host(recs):
@@ -93,7 +83,7 @@ def playable_host(recs):
     out = np.zeros((len(recs), 81), bool)
     buf = (ctypes.c_uint8 * 81)()
     for i in range(len(recs)):
-        p = ctypes.cast(recs[i].ctypes.data, _PP)
+        p = L.pos_ptr(recs[i])
         lib.bk_pos_legal_moves(p, buf)
         mover = 2 if p.contents.turn & 1 else 1
         for s in range(81):
@@ -116,33 +106,53 @@ def _engines(engine, sides, G):
     return engine, G
 
 
-def _check_records(pos, is_tensor):
+def _check_records(pos):
     if tuple(pos.shape[1:]) != (POS_BYTES,) or pos.ndim != 2 or (str(pos.dtype) not in ("uint8", "torch.uint8")):
         raise ValueError(f"pos must be uint8 [G, {POS_BYTES}], got {pos.dtype} {tuple(pos.shape)}")
     if len(pos) < 1:
         raise ValueError("pos holds no record")
 
 
-def _logits(eng, planes, black_to_move, n0):
-    """The logits of every row: one engine for all rows, or the pair -- rows [0, n0) by the first engine when black is
-    to move, by the second when white is; rows [n0, G) the other way round."""
-    import torch
+def _numpy(x):
+    return x.cpu().numpy() if isinstance(x, torch.Tensor) else x
 
-    def run(e, x):
-        parts = [e.eval_device(x[s:s + e.max_batch], logits=True, probs=False, value=False)["logits"]
-                 for s in range(0, len(x), e.max_batch)]
-        return parts[0] if len(parts) == 1 else torch.cat(parts)
 
+def _device(device, eng=None, pos=None):
+    """The device of a call: `device` when given, else the engine's, else that of the records, else the current one."""
+    if device is not None:
+        return torch.device(device)
+    if eng is not None:
+        return torch.device("cuda", (eng[0] if isinstance(eng, tuple) else eng).device_id)
+    if isinstance(pos, torch.Tensor) and pos.is_cuda:
+        return pos.device
+    return torch.device("cuda", torch.cuda.current_device())
+
+
+def _pairs(eng, planes, black_to_move, n0):
+    """The (engine, rows) L.engine_logits takes: one engine for all rows, or the pair -- rows [0, n0) by the first engine
+    when black is to move, by the second when white is; rows [n0, G) the other way round."""
     if not isinstance(eng, tuple):
-        return run(eng, planes)
+        return [(eng, planes)]
     first, second = eng if black_to_move else eng[::-1]
-    G = len(planes)
-    parts = [run(e, planes[a:b]) for e, a, b in ((first, 0, n0), (second, n0, G)) if b > a]
-    return parts[0] if len(parts) == 1 else torch.cat(parts)
+    return [(first, planes[:n0]), (second, planes[n0:])]
+
+
+def _finished(records, moves, plies, over, score, owner):
+    """A Finished; moves: the whole history [G, max_plies] (numpy or a tensor), cut here to the longest game, or None."""
+    out = Finished()
+    out.records, out.plies, out.over, out.score, out.owner = records, plies, over, score, owner
+    out.moves = None if moves is None else np.ascontiguousarray(_numpy(moves[:, :max(int(plies.max()), 1)]))
+    out.unfinished = int((~over).sum())
+    return out
+
+
+def _check_status(status, verb):
+    L.check_status(status, lambda s, st: f"row {s}: a {verb} move is illegal (status {st}); the playable set and the rules "
+                   "disagree")
 
 
 def finish_games(pos, engine, seed, counters=None, max_plies=MAX_PLIES, rules="device", device=None, sides=None,
-                 komi=R.KOMI):
+                 komi=L.KOMI):
     """Play the records pos (uint8 [G,192], numpy or a tensor; not modified) to the end of the game -> Finished.
 
     engine: one fp32 LeafEngine with policy weights that plays both colours; None: uniform logits (random eye-safe
@@ -151,18 +161,16 @@ def finish_games(pos, engine, seed, counters=None, max_plies=MAX_PLIES, rules="d
     slices of reinforce.play_games) -- every record must then have the same parity of turn (ValueError otherwise).
     counters: int32 [G,4] Philox counter words of the first ply; word 1 runs on with the ply.  Default: default_counters.
     """
-    if rules not in ("device", "host"):
-        raise ValueError(f"rules must be 'device' or 'host', got {rules!r}")
+    L.check_rules(rules)
     max_plies = int(max_plies)
     if max_plies < 1:
         raise ValueError("max_plies must be at least 1")
-    is_tensor = not isinstance(pos, np.ndarray)
-    _check_records(pos, is_tensor)
+    _check_records(pos)
     G = len(pos)
     eng, n0 = _engines(engine, sides, G)
     turns = None
     if counters is None or isinstance(eng, tuple):
-        turns = record_turns(pos.cpu().numpy() if is_tensor else pos)
+        turns = record_turns(_numpy(pos))
     black_first = True
     if isinstance(eng, tuple):
         if len(set((turns & 1).tolist())) != 1:
@@ -170,39 +178,19 @@ def finish_games(pos, engine, seed, counters=None, max_plies=MAX_PLIES, rules="d
         black_first = int(turns[0]) % 2 == 0
     if counters is None:
         counters = default_counters(G, turns)
-    key = int(seed) & (2 ** 64 - 1)
+    key = L.seed_u64(seed)
     if rules == "host":
-        ctr = np.array(counters.cpu().numpy() if hasattr(counters, "cpu") else counters, np.int32)
-        if ctr.shape != (G, 4):
-            raise ValueError(f"counters must be int32 [{G}, 4]")
-        recs = np.array(pos.cpu().numpy() if is_tensor else pos, np.uint8, order="C")
-        return _finish_host(recs, eng, n0, black_first, key, ctr, max_plies, device, komi)
+        return _finish_host(pos, eng, n0, black_first, key, L.counters_to_host(counters, G), max_plies, device, komi)
     return _finish_device(pos, eng, n0, black_first, key, counters, max_plies, device, komi)
 
 
 def _finish_device(pos, eng, n0, black_first, key, counters, max_plies, device, komi):
-    import torch
-
-    from . import _trainlib as T
-
-    any_eng = eng[0] if isinstance(eng, tuple) else eng
-    if device is not None:
-        dev = torch.device(device)
-    elif any_eng is not None:
-        dev = torch.device("cuda", any_eng.device_id)
-    elif isinstance(pos, torch.Tensor) and pos.is_cuda:
-        dev = pos.device
-    else:
-        dev = torch.device("cuda", torch.cuda.current_device())
+    dev = _device(device, eng, pos)
     G = len(pos)
     if G > T.MAX_BATCH:
         raise ValueError(f"at most {T.MAX_BATCH} games per call, got {G}")
-    pos = (pos.to(dev) if isinstance(pos, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(pos)).to(dev))
-    pos = pos.contiguous().clone()
-    ctr = (counters.to(dev) if isinstance(counters, torch.Tensor) else
-           torch.from_numpy(np.ascontiguousarray(counters, np.int32)).to(dev)).contiguous().clone()
-    if tuple(ctr.shape) != (G, 4) or ctr.dtype != torch.int32:
-        raise ValueError(f"counters must be int32 [{G}, 4]")
+    pos = L.records_to_device(pos, dev)
+    ctr = L.counters_to_device(counters, G, dev)
     planes = torch.empty((G, 27, 9, 9), dtype=torch.uint8, device=dev) if eng is not None else None
     playable = torch.empty((G, 81), dtype=torch.uint8, device=dev)
     over = torch.zeros((G,), dtype=torch.uint8, device=dev)
@@ -215,74 +203,62 @@ def _finish_device(pos, eng, n0, black_first, key, counters, max_plies, device, 
             ctr[:, 1] += 1
             if k % CHECK_EVERY == 0 and bool(over.all()):                 # the only look at the device inside the loop
                 break
-        logits = uniform if eng is None else _logits(eng, planes, black_first == (k % 2 == 0), n0)
+        logits = uniform if eng is None else L.engine_logits(_pairs(eng, planes, black_first == (k % 2 == 0), n0))
         moves, _ = T.sample_moves_masked(logits, playable, key, ctr)
         moves = torch.where(over != 0, none, moves)
         hist[:, k] = moves
         status |= T.playout_step(pos, moves, over, planes, playable)
     score, owner = T.area_score(pos, komi, owner=True)
-    out = Finished()
-    out.records = pos
     moves = hist.cpu().numpy()
-    if status.any().item():
-        s = int(torch.nonzero(status)[0, 0])
-        raise RuntimeError(f"row {s}: a sampled move is illegal (status {int(status[s])}); the playable set and the rules "
-                           "disagree")
-    out.plies = (moves > MOVE_NONE).sum(1).astype(np.int64)
-    out.moves = np.ascontiguousarray(moves[:, :max(int(out.plies.max()), 1)])
-    out.over = over.cpu().numpy() != 0
-    out.score, out.owner = score.cpu().numpy(), owner.cpu().numpy()
-    out.unfinished = int((~out.over).sum())
-    return out
+    _check_status(status, "sampled")
+    return _finished(pos, moves, (moves > MOVE_NONE).sum(1).astype(np.int64), over.cpu().numpy() != 0,
+                     score.cpu().numpy(), owner.cpu().numpy())
 
 
-def _finish_host(recs, eng, n0, black_first, key, ctr, max_plies, device, komi):
-    lib, play = go.golib(), R._play_fn()
-    G = len(recs)
-    over = np.zeros(G, bool)
-    hist = np.full((G, max_plies), MOVE_NONE, np.int16)
-    margin = np.full(G, np.inf)
-    kw = R.seed_key(key)
-    tmp = (ctypes.c_uint8 * 81)()
-    if eng is not None:
-        import torch
-
-        any_eng = eng[0] if isinstance(eng, tuple) else eng
-        dev = torch.device("cuda", any_eng.device_id) if device is None else torch.device(device)
-        feats = np.empty((G, 27, 9, 9), np.uint8)
+def _playout_host(pos, key, ctr, max_plies, komi, choose, verb, history=True):
+    """The one host loop: play a copy of the records pos to two passes in a row (or max_plies) -> Finished.  Per ply, for
+    the rows still live: their playable sets and one Philox draw each (ctr, word 1 running on with the ply), then
+    choose(k, recs, live, playable, x0) -> the move of each live row (-1: pass)."""
+    recs = np.array(_numpy(pos), np.uint8, order="C")
+    over = np.zeros(len(recs), bool)
+    hist = np.full((len(recs), max_plies), MOVE_NONE, np.int16)
+    kw = L.seed_key(key)
+    ctr = ctr.view(np.uint32).copy()
     for k in range(max_plies):
         if over.all():
             break
         if k:
-            ctr[:, 1] += 1
+            ctr[:, 1] += np.uint32(1)                                      # wraps at 2^32, as the kernels' c1 + k
         live = np.nonzero(~over)[0]
+        mv = np.asarray(choose(k, recs, live, playable_host(recs[live]), L.philox4x32_10(ctr[live], kw)[:, 0]))
+        hist[live, k] = mv
+        over[live[(mv < 0) & (L.record_last_move(recs)[live] == go.PASS)]] = True
+        L.play_host(recs, live, mv, lambda g, m: f"row {g}: {verb} move {m} is illegal; the playable set and the rules "
+                    "disagree", liberties=True)
+    return _finished(recs, hist if history else None, (hist > MOVE_NONE).sum(1).astype(np.int64), over,
+                     L.area_score_host(recs, komi).astype(np.float32), owner_host(recs))
+
+
+def _finish_host(pos, eng, n0, black_first, key, ctr, max_plies, device, komi):
+    """finish_games on the host: the move is bkt_sample_moves_masked's, from the float64 CDF of the logits."""
+    G = len(pos)
+    margin = np.full(G, np.inf)
+    if eng is not None:
+        dev = _device(device, eng)
+        feats = np.empty((G, 27, 9, 9), np.uint8)
+
+    def choose(k, recs, live, ok, x0):
         if eng is None:
             logits = np.zeros((G, 81))
         else:                                                             # every row, so that the pair's slices stay put
-            R.features_batch(recs, feats.ctypes.data)
-            logits = _logits(eng, torch.from_numpy(feats).to(dev), black_first == (k % 2 == 0), n0)
+            L.features_batch(recs, feats.ctypes.data)
+            logits = L.engine_logits(_pairs(eng, torch.from_numpy(feats).to(dev), black_first == (k % 2 == 0), n0))
             logits = logits.cpu().numpy().astype(np.float64)
-        ok = playable_host(recs[live])
-        u = R.uniform(R.philox4x32_10(ctr[live].view(np.uint32), kw)[:, 0])
-        mv, _ = R.sample_host(logits[live], ok, u)
-        margin[live] = np.minimum(margin[live], R.cdf_margin(logits[live], u))
-        hist[live, k] = mv
-        for g, m in zip(live.tolist(), mv.tolist()):
-            p = ctypes.cast(recs[g].ctypes.data, _PP)
-            if m < 0 and p.contents.last_move == go.PASS:
-                over[g] = True
-            if play(recs[g].ctypes.data, m):
-                raise RuntimeError(f"row {g}: sampled move {m} is illegal; the playable set and the rules disagree")
-            lib.bk_pos_liberties(p, tmp)
-    out = Finished()
-    out.records = recs
-    out.plies = (hist > MOVE_NONE).sum(1).astype(np.int64)
-    out.moves = np.ascontiguousarray(hist[:, :max(int(out.plies.max()), 1)])
-    out.over = over
-    out.score = np.array([lib.bk_pos_area_score(ctypes.cast(recs[g].ctypes.data, _PP), komi) for g in range(G)],
-                         np.float32)
-    out.owner = owner_host(recs)
-    out.unfinished = int((~over).sum())
+        u = L.uniform(x0)
+        margin[live] = np.minimum(margin[live], L.cdf_margin(logits[live], u))
+        return L.sample_host(logits[live], ok, u)[0]
+
+    out = _playout_host(pos, key, ctr, max_plies, komi, choose, "sampled")
     out.min_margin = margin
     return out
 
@@ -315,6 +291,7 @@ def owner_host(recs):
     return out
 
 
+
 # ---- whole random playouts in one launch, and the Monte-Carlo value ----------------------------------------------------------
 def select_index(x0, n):
     """The rank, among n playable points in ascending order, that the Philox word x0 selects: ((x0 >> 8) * n) >> 24, in
@@ -322,55 +299,49 @@ def select_index(x0, n):
     return ((np.asarray(x0, np.uint64) >> np.uint64(8)) * np.asarray(n, np.uint64)) >> np.uint64(24)
 
 
-def _counters_array(counters, G):
-    ctr = np.array(counters.cpu().numpy() if hasattr(counters, "cpu") else counters, np.int32)
-    if ctr.shape != (G, 4):
-        raise ValueError(f"counters must be int32 [{G}, 4]")
-    return ctr
+
+def _random_host(pos, key, ctr, max_plies, komi, history):
+    """random_playouts on the host: the select_index-th playable point in ascending order, a pass when there is none."""
+    def choose(k, recs, live, ok, x0):
+        n = ok.sum(1)
+        pick = np.argmax(np.cumsum(ok, 1) > select_index(x0, n).astype(np.int64)[:, None], 1)
+        return np.where(n > 0, pick, go.PASS)
+
+    return _playout_host(pos, key, ctr, max_plies, komi, choose, "selected", history)
 
 
-def random_playouts(pos, seed, counters=None, max_plies=MAX_PLIES, rules="device", komi=R.KOMI, history=True, device=None):
+def random_playouts(pos, seed, counters=None, max_plies=MAX_PLIES, rules="device", komi=L.KOMI, history=True, device=None):
     """Play the records pos (uint8 [G,192], numpy or a tensor; not modified) to the end of the game with uniformly random
     eye-safe moves -> Finished, the fields finish_games returns (moves is None with history=False; no min_margin: nothing
     is rounded).  rules="device": one bkt_random_playouts launch per T.MAX_BATCH rows, then bkt_area_score.  rules="host":
-    the mirror on bk_pos_play / bk_pos_is_legal / bk_pos_possible_eye and reinforce.philox4x32_10; it needs no GPU and
+    the mirror on bk_pos_play / bk_pos_is_legal / bk_pos_possible_eye and lockstep.philox4x32_10; it needs no GPU and
     gives the same bits.  counters: int32 [G,4], the Philox counter words of ply 0 (word 1 runs on with the ply); default:
     default_counters, as finish_games.  A row's game depends on its record, the seed and its counters only.
     These are not finish_games(engine=None)'s games: that sampler goes through a float CDF."""
-    if rules not in ("device", "host"):
-        raise ValueError(f"rules must be 'device' or 'host', got {rules!r}")
+    L.check_rules(rules)
     max_plies = int(max_plies)
     if not 1 <= max_plies <= 1024:
         raise ValueError("max_plies must be 1..1024 (BKT_MAX_PLAYOUT_PLIES)")
-    is_tensor = not isinstance(pos, np.ndarray)
-    _check_records(pos, is_tensor)
+    _check_records(pos)
     G = len(pos)
     if counters is None:
-        counters = default_counters(G, record_turns(pos.cpu().numpy() if is_tensor else pos))
-    key = int(seed) & (2 ** 64 - 1)
+        counters = default_counters(G, record_turns(_numpy(pos)))
+    key = L.seed_u64(seed)
     if rules == "host":
-        recs = np.array(pos.cpu().numpy() if is_tensor else pos, np.uint8, order="C")
-        return _random_host(recs, key, _counters_array(counters, G), max_plies, komi, history)
-    return _random_device(pos, key, counters, max_plies, komi, history, device)
-
-
-def _device_of(pos, device):
-    import torch
-
-    if device is not None:
-        return torch.device(device)
-    if isinstance(pos, torch.Tensor) and pos.is_cuda:
-        return pos.device
-    return torch.device("cuda", torch.cuda.current_device())
+        return _random_host(pos, key, L.counters_to_host(counters, G), max_plies, komi, history)
+    dev = _device(device, None, pos)
+    pos = L.records_to_device(pos, dev)
+    ctr = L.counters_to_device(counters, G, dev, clone=False)
+    over, plies, moves, status = _play_random_device(pos, key, ctr, max_plies, history)
+    score, owner = _area_score_device(pos, komi, True)
+    _check_status(status, "selected")
+    return _finished(pos, moves, plies.cpu().numpy().astype(np.int64), over.cpu().numpy() != 0, score.cpu().numpy(),
+                     owner.cpu().numpy())
 
 
 def _play_random_device(pos, key, ctr, max_plies, history):
     """pos uint8 [G,192] and ctr int32 [G,4] on the device; pos is played on in place.
     -> (over uint8 [G], plies int32 [G], moves int16 [G,max_plies] or None, status int32 [G]), T.MAX_BATCH rows per launch."""
-    import torch
-
-    from . import _trainlib as T
-
     parts = [T.random_playouts(pos[s:s + T.MAX_BATCH], key, ctr[s:s + T.MAX_BATCH], max_plies, history=history)
              for s in range(0, len(pos), T.MAX_BATCH)]
     if len(parts) == 1:
@@ -379,94 +350,16 @@ def _play_random_device(pos, key, ctr, max_plies, history):
 
 
 def _area_score_device(pos, komi, owner):
-    import torch
-
-    from . import _trainlib as T
-
     parts = [T.area_score(pos[s:s + T.MAX_BATCH], komi, owner=owner) for s in range(0, len(pos), T.MAX_BATCH)]
     if len(parts) == 1:
         return parts[0]
     return tuple(torch.cat(col) for col in zip(*parts)) if owner else torch.cat(parts)
 
 
-def _random_device(pos, key, counters, max_plies, komi, history, device):
-    import torch
-
-    dev = _device_of(pos, device)
-    G = len(pos)
-    pos = (pos.to(dev) if isinstance(pos, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(pos)).to(dev))
-    pos = pos.contiguous().clone()
-    ctr = (counters.to(dev) if isinstance(counters, torch.Tensor) else
-           torch.from_numpy(np.ascontiguousarray(counters, np.int32)).to(dev)).contiguous()
-    if tuple(ctr.shape) != (G, 4) or ctr.dtype != torch.int32:
-        raise ValueError(f"counters must be int32 [{G}, 4]")
-    over, plies, moves, status = _play_random_device(pos, key, ctr, max_plies, history)
-    score, owner = _area_score_device(pos, komi, True)
-    if status.any().item():
-        s = int(torch.nonzero(status)[0, 0])
-        raise RuntimeError(f"row {s}: a selected move is illegal (status {int(status[s])}); the playable set and the rules "
-                           "disagree")
-    out = Finished()
-    out.records = pos
-    out.plies = plies.cpu().numpy().astype(np.int64)
-    out.moves = None
-    if history:
-        out.moves = np.ascontiguousarray(moves[:, :max(int(out.plies.max()), 1)].cpu().numpy())
-    out.over = over.cpu().numpy() != 0
-    out.score, out.owner = score.cpu().numpy(), owner.cpu().numpy()
-    out.unfinished = int((~out.over).sum())
-    return out
-
-
-def _random_host(recs, key, ctr, max_plies, komi, history):
-    lib, play = go.golib(), R._play_fn()
-    G = len(recs)
-    over = np.zeros(G, bool)
-    plies = np.zeros(G, np.int64)
-    hist = np.full((G, max_plies), MOVE_NONE, np.int16)
-    kw = R.seed_key(key)
-    ctr = ctr.view(np.uint32).copy()
-    tmp = (ctypes.c_uint8 * 81)()
-    for k in range(max_plies):
-        if over.all():
-            break
-        if k:
-            ctr[:, 1] += np.uint32(1)                                      # wraps at 2^32, as the kernel's c1 + k
-        live = np.nonzero(~over)[0]
-        ok = playable_host(recs[live])
-        idx = select_index(R.philox4x32_10(ctr[live], kw)[:, 0], ok.sum(1))
-        for g, row, i in zip(live.tolist(), ok, idx.tolist()):
-            points = np.nonzero(row)[0]
-            m = int(points[i]) if len(points) else go.PASS
-            hist[g, k] = m
-            plies[g] += 1
-            p = ctypes.cast(recs[g].ctypes.data, _PP)
-            if m < 0 and p.contents.last_move == go.PASS:
-                over[g] = True
-            if play(recs[g].ctypes.data, m):
-                raise RuntimeError(f"row {g}: selected move {m} is illegal; the playable set and the rules disagree")
-            lib.bk_pos_liberties(p, tmp)
-    out = Finished()
-    out.records = recs
-    out.plies = plies
-    out.moves = np.ascontiguousarray(hist[:, :max(int(plies.max()), 1)]) if history else None
-    out.over = over
-    out.score = np.array([lib.bk_pos_area_score(ctypes.cast(recs[g].ctypes.data, _PP), komi) for g in range(G)],
-                         np.float32)
-    out.owner = owner_host(recs)
-    out.unfinished = int((~over).sum())
-    return out
-
-
 def value_counters(recs, n):
     """The Philox counters of playout_value, int32 [R * n, 4] (numpy): playout j of a record whose Zobrist field is h uses
     (h & 0xFFFFFFFF, 0, h >> 32, 4 * j + STREAM_VALUE) -- the record names its own draws, never its row."""
-    h = np.ascontiguousarray(recs[:, 184:192]).view(np.uint32)            # [R, 2]: the low and the high word
-    c = np.zeros((len(recs), n, 4), np.uint32)
-    c[:, :, 0] = h[:, :1]
-    c[:, :, 2] = h[:, 1:]
-    c[:, :, 3] = 4 * np.arange(n, dtype=np.uint32) + STREAM_VALUE
-    return c.reshape(-1, 4).view(np.int32)
+    return L.game_counters(L.record_hash_words(recs).view(np.uint64), 0, L.value_streams(n))
 
 
 def _check_playouts(n):
@@ -478,45 +371,29 @@ def _check_playouts(n):
 
 def _playout_value_device(recs, n, key, komi, max_plies=MAX_PLIES):
     """recs: a uint8 [R,192] tensor on the device -> float32 [R] on the device; nothing here waits for the device."""
-    import torch
-
-    R_ = len(recs)
     pos = recs.repeat_interleave(n, 0)                                     # a copy: the caller's records stay
-    ctr = torch.zeros((R_, n, 4), dtype=torch.int32, device=recs.device)
-    h = recs[:, 184:192].contiguous().view(torch.int32)                    # [R, 2]: the low and the high word of the hash
-    ctr[:, :, 0] = h[:, :1]
-    ctr[:, :, 2] = h[:, 1:]
-    ctr[:, :, 3] = 4 * torch.arange(n, dtype=torch.int32, device=recs.device) + STREAM_VALUE
-    _play_random_device(pos, key, ctr.view(-1, 4), max_plies, False)
-    black_wins = _area_score_device(pos, komi, False).view(R_, n) > 0
-    black_to_move = (recs[:, 172] & 1) == 0                                # the low byte of `turn`
-    w = (black_wins == black_to_move[:, None]).sum(1)
+    _play_random_device(pos, key, L.value_counters_device(recs, n), max_plies, False)
+    black_wins = _area_score_device(pos, komi, False).view(len(recs), n) > 0
+    w = (black_wins == L.black_to_move(recs)[:, None]).sum(1)
     return (2 * w - n).to(torch.float32) / n
 
 
-def playout_value(recs, n, seed, rules="device", komi=R.KOMI, device=None):
+def playout_value(recs, n, seed, rules="device", komi=L.KOMI, device=None):
     """The Monte-Carlo value of each record, float32 [R] (numpy): (2 w - n) / n, w = the number of n uniformly random
     eye-safe playouts (random_playouts, capped at MAX_PLIES and then scored as they stand) that the side to move wins --
     black wins iff the area score is > 0.  A pure function of the record, `seed` and `n` (value_counters): the row index
     and the rest of the batch do not enter.  recs: uint8 [R,192], numpy or a tensor."""
-    if rules not in ("device", "host"):
-        raise ValueError(f"rules must be 'device' or 'host', got {rules!r}")
+    L.check_rules(rules)
     n = _check_playouts(n)
-    is_tensor = not isinstance(recs, np.ndarray)
-    _check_records(recs, is_tensor)
-    key = int(seed) & (2 ** 64 - 1)
+    _check_records(recs)
+    key = L.seed_u64(seed)
     if rules == "device":
-        import torch
-
-        dev = _device_of(recs, device)
-        t = recs.to(dev) if is_tensor else torch.from_numpy(np.ascontiguousarray(recs)).to(dev)
-        return _playout_value_device(t.contiguous(), n, key, komi).cpu().numpy()
-    recs = np.array(recs.cpu().numpy() if is_tensor else recs, np.uint8, order="C")
+        t = L.records_to_device(recs, _device(device, None, recs), clone=False)
+        return _playout_value_device(t, n, key, komi).cpu().numpy()
+    recs = np.array(_numpy(recs), np.uint8, order="C")
     fin = _random_host(np.repeat(recs, n, 0), key, value_counters(recs, n), MAX_PLIES, komi, False)
-    black_wins = fin.score.reshape(len(recs), n) > 0
-    black_to_move = (record_turns(recs) & 1) == 0
-    w = (black_wins == black_to_move[:, None]).sum(1)
-    return ((2 * w - n).astype(np.float32) / np.float32(n)).astype(np.float32)
+    w = (fin.score.reshape(len(recs), n) > 0) == L.black_to_move(recs)[:, None]
+    return ((2 * w.sum(1) - n).astype(np.float32) / np.float32(n)).astype(np.float32)
 
 
 class PlayoutEvaluator:
@@ -529,12 +406,11 @@ class PlayoutEvaluator:
     step loop as its own bk_evaluator, which would compute no playouts -- this class goes through callback_evaluator."""
     wants_positions = True
 
-    def __init__(self, engine, playouts=64, seed=0, rules="device", komi=R.KOMI):
-        if rules not in ("device", "host"):
-            raise ValueError(f"rules must be 'device' or 'host', got {rules!r}")
+    def __init__(self, engine, playouts=64, seed=0, rules="device", komi=L.KOMI):
+        L.check_rules(rules)
         self.policy_engine = engine
         self.playouts = _check_playouts(playouts)
-        self.seed = int(seed) & (2 ** 64 - 1)
+        self.seed = L.seed_u64(seed)
         self.rules, self.komi = rules, komi
         self.positions = self.batches = 0
 
@@ -551,9 +427,7 @@ class PlayoutEvaluator:
         if self.rules == "host":
             values = playout_value(recs, self.playouts, self.seed, rules="host", komi=self.komi)
         else:
-            import torch
-
-            dev = torch.device("cuda", self.policy_engine.device_id)
+            dev = _device(None, self.policy_engine)
             values = _playout_value_device(torch.from_numpy(recs).to(dev), self.playouts, self.seed, self.komi)
         return ticket, values
 
@@ -596,15 +470,13 @@ def _as_records(positions):
     return np.ascontiguousarray(recs)
 
 
-def rollout_score(positions, engine, n=256, seed=0, komi=R.KOMI, rules="device", max_plies=MAX_PLIES, device=None,
+def rollout_score(positions, engine, n=256, seed=0, komi=L.KOMI, rules="device", max_plies=MAX_PLIES, device=None,
                   one_launch=False):
     """n playouts (finish_games) of every position -> a list of RolloutScore.  positions: go.Game objects or uint8
     [P,192] records.  Playout j of position i is game i * n + j of one finish_games call: deterministic per seed.
     one_launch=True (engine must be None): the uniformly random playouts of random_playouts instead, any number of rows."""
     recs = _as_records(positions)
-    n = int(n)
-    if n < 1:
-        raise ValueError("n must be at least 1")
+    n = _check_playouts(n)
     P = len(recs)
     if one_launch:
         if engine is not None:
@@ -662,7 +534,7 @@ def _parse(argv):
                     help="uniformly random playouts, each played to its end inside one kernel launch (not with -p)")
     ap.add_argument("-n", dest="n", type=int, default=256, help="playouts")
     ap.add_argument("--seed", type=int, default=0)
-    ap.add_argument("--komi", type=float, default=R.KOMI)
+    ap.add_argument("--komi", type=float, default=L.KOMI)
     ap.add_argument("--device", type=int, default=0)
     args = ap.parse_args(argv)
     if args.n < 1:
@@ -689,16 +561,15 @@ def sgf_position(path, move=None):
 
 
 def main(argv=None):
-    import torch
-
     args = _parse(argv)
     game = sgf_position(args.sgf, args.move)
     torch.cuda.set_device(args.device)
     eng = None
     if args.p is not None:
+        from .reinforce import policy_engine
         from .train import load_weights
 
-        eng = R.policy_engine(load_weights(args.p), args.device, min(args.n, 4096))
+        eng = policy_engine(load_weights(args.p), args.device, min(args.n, 4096))
     try:
         r = rollout_score([game], eng, n=args.n, seed=args.seed, komi=args.komi,
                           device=torch.device("cuda", args.device), one_launch=args.random)[0]

@@ -11,7 +11,7 @@ import torch
 
 from bokego_amd import _trainlib as T
 from bokego_amd import genvals as GV
-from bokego_amd import go, train
+from bokego_amd import go, lockstep, train
 from bokego_amd import reinforce as R
 from conftest import GOLDEN
 from test_reinforce_device_cpu import crafted_boards, host_scores, mirror_score, records_from_boards
@@ -226,9 +226,9 @@ def test_device_path_runs_no_host_rules(engines, monkeypatch):
     def no_play():
         raise AssertionError("the device path asked for bk_pos_play")
 
-    monkeypatch.setattr(R, "_play_fn", no_play)
-    real = R.features_batch
-    monkeypatch.setattr(R, "features_batch", lambda recs, out: (calls.append(len(recs)), real(recs, out))[1])
+    monkeypatch.setattr(lockstep, "_play_fn", no_play)
+    real = lockstep.features_batch
+    monkeypatch.setattr(lockstep, "features_batch", lambda recs, out: (calls.append(len(recs)), real(recs, out))[1])
     games = R.play_games(*engines, 2, 8, seed=9, rules="device")
     assert games.length.min() > 60 and len(calls) <= 1
     with pytest.raises(AssertionError):

@@ -346,6 +346,27 @@ def test_pair_form_and_the_cap(engine, ply40):
     assert np.array_equal(cut.score, host_area)                      # scored as it stands
 
 
+@pytest.mark.parametrize("pair", [False, True])
+def test_an_engine_smaller_than_the_batch(ply40, pair):
+    """Seven records through an engine of max_batch 4 (the rows of a slice go to it four at a time) play the games of the
+    same call through an engine of max_batch 8, field for field: once in the single form, once in the pair form."""
+    sd = train.load_weights(os.path.join(GOLDEN, "policy_19.bkw"))
+    fins = []
+    for max_batch in (4, 8):
+        e = R.policy_engine(sd, 0, max_batch)
+        try:
+            fins.append(RO.finish_games(ply40[:7], (e, e), SEED, sides=(3,), max_plies=40) if pair else
+                        RO.finish_games(ply40[:7], e, SEED, max_plies=40))
+        finally:
+            e.close()
+    small, big = fins
+    assert torch.equal(small.records, big.records) and small.unfinished == big.unfinished
+    for k in ("moves", "over", "plies", "score", "owner"):
+        a, b = getattr(small, k), getattr(big, k)
+        assert a.dtype == b.dtype and a.shape == b.shape and np.array_equal(a, b), k
+    assert len(big.moves) == 7 and (big.moves >= 0).any(1).all()     # games were played, not only passes
+
+
 # ---- 5. a board whose answer needs no network -------------------------------------------------------------------------------------
 @pytest.mark.parametrize("with_engine", [True, False])
 def test_the_board_that_needs_no_network(engine, with_engine):
