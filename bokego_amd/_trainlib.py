@@ -45,12 +45,15 @@ SYMBOLS = {
     "bkt_playout_step": (_I, [_P, _P, _I, _P, _P, _P, _P, _P]),
     "bkt_area_score": (_I, [_P, _I, _F, _P, _P, _P]),
     "bkt_random_playouts": (_I, [_P, _I, _U64, _P, _I, _P, _P, _P, _P, _P]),
+    "bkt_pattern_codes": (_I, [_P, _I, _P, _P]),
+    "bkt_pattern_playouts": (_I, [_P, _I, _U64, _P, _P, _I, _P, _P, _P, _P, _P]),
 }
 MAX_BATCH = 65536          # BKT_MAX_BATCH
 PRECISIONS = ("fp32", "bf16")
 POS_BYTES = 192            # sizeof(bk_pos)
 MOVE_NONE = -2             # BKT_MOVE_NONE: bkt_playout_step leaves the row alone
 MAX_PLAYOUT_PLIES = 1024   # BKT_MAX_PLAYOUT_PLIES
+PATTERN_ENTRIES = 131072   # BKT_PATTERN_ENTRIES
 
 _lib = None
 
@@ -352,11 +355,8 @@ def area_score(pos, komi=5.5, owner=False):
     return (score, own) if owner else score
 
 
-def random_playouts(pos, seed, counters, max_plies, over=None, history=True):
-    """Whole uniformly random playouts in one launch, in place (bkt_random_playouts): pos uint8 [B,192], counters int32
-    [B,4] (the Philox counter words of ply 0; word 1 runs on with the ply), 1 <= max_plies <= MAX_PLAYOUT_PLIES.  over: None
-    (no game has ended) or uint8 [B], updated in place; rows whose flag is set are left alone.
-    -> (over uint8 [B], plies int32 [B], moves int16 [B,max_plies] or None with history=False, status int32 [B])."""
+def _playouts(name, pos, seed, counters, table, max_plies, over, history):
+    """bkt_random_playouts, or bkt_pattern_playouts with its table argument after the counters."""
     B, max_plies = _pos_batch(pos), int(max_plies)
     if not 1 <= max_plies <= MAX_PLAYOUT_PLIES:
         raise ValueError(f"max_plies must be 1..{MAX_PLAYOUT_PLIES}, got {max_plies}")
@@ -365,9 +365,35 @@ def random_playouts(pos, seed, counters, max_plies, over=None, history=True):
     plies = torch.empty((B,), dtype=torch.int32, device=pos.device)
     status = torch.empty((B,), dtype=torch.int32, device=pos.device)
     moves = torch.empty((B, max_plies), dtype=torch.int16, device=pos.device) if history else None
-    _check(load().bkt_random_playouts(_dev(pos, "pos", dtype=torch.uint8), B, seed_u64(seed),
-                                      _dev(counters, "counters", (B, 4), torch.int32), max_plies,
-                                      _dev(over, "over", (B,), torch.uint8), _dev(plies, "plies", dtype=torch.int32),
-                                      None if moves is None else _dev(moves, "moves", dtype=torch.int16),
-                                      _dev(status, "status", dtype=torch.int32), _stream(pos)), "bkt_random_playouts")
+    _check(getattr(load(), name)(_dev(pos, "pos", dtype=torch.uint8), B, seed_u64(seed),
+                                 _dev(counters, "counters", (B, 4), torch.int32), *table, max_plies,
+                                 _dev(over, "over", (B,), torch.uint8), _dev(plies, "plies", dtype=torch.int32),
+                                 None if moves is None else _dev(moves, "moves", dtype=torch.int16),
+                                 _dev(status, "status", dtype=torch.int32), _stream(pos)), name)
     return over, plies, moves, status
+
+
+def random_playouts(pos, seed, counters, max_plies, over=None, history=True):
+    """Whole uniformly random playouts in one launch, in place (bkt_random_playouts): pos uint8 [B,192], counters int32
+    [B,4] (the Philox counter words of ply 0; word 1 runs on with the ply), 1 <= max_plies <= MAX_PLAYOUT_PLIES.  over: None
+    (no game has ended) or uint8 [B], updated in place; rows whose flag is set are left alone.
+    -> (over uint8 [B], plies int32 [B], moves int16 [B,max_plies] or None with history=False, status int32 [B])."""
+    return _playouts("bkt_random_playouts", pos, seed, counters, (), max_plies, over, history)
+
+
+def pattern_playouts(pos, seed, counters, table, max_plies, over=None, history=True):
+    """random_playouts with the pattern-weighted draw (bkt_pattern_playouts): table int16 [PATTERN_ENTRIES] on the device of
+    pos, the bits of the uint16 weights (torch has no uint16 arithmetic; nothing here computes with them)."""
+    if table.device != pos.device:
+        raise ValueError("the pattern table must be on the device of pos")
+    return _playouts("bkt_pattern_playouts", pos, seed, counters, (_dev(table, "table", (PATTERN_ENTRIES,), torch.int16),),
+                     max_plies, over, history)
+
+
+def pattern_codes(pos):
+    """The 3x3 pattern index of every point (bkt_pattern_codes): pos uint8 [B,192] (read only) -> int32 [B,81]."""
+    B = _pos_batch(pos)
+    codes = torch.empty((B, 81), dtype=torch.int32, device=pos.device)
+    _check(load().bkt_pattern_codes(_dev(pos, "pos", dtype=torch.uint8), B, _dev(codes, "codes", dtype=torch.int32),
+                                    _stream(pos)), "bkt_pattern_codes")
+    return codes

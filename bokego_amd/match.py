@@ -231,6 +231,8 @@ def parse_args(argv=None):
     ap.add_argument("--playout-value", type=int, default=0, metavar="N",
                     help="N > 0: the in-process engine searches without a value net, on the Monte-Carlo value of N random "
                          "playouts (-v is then not loaded; not with --engine)")
+    ap.add_argument("--playout-patterns", default=None, metavar="FILE",
+                    help="with --playout-value: the table of 3x3 pattern weights its playouts draw their moves by")
     ap.add_argument("--opponent", default="policy", help='"policy" (raw policy, no search) or a GTP command line')
     ap.add_argument("--komi", type=float, default=5.5)
     ap.add_argument("--sgf", default=None, help="prefix for SGF records")
@@ -247,6 +249,8 @@ def parse_args(argv=None):
         ap.error("--playout-value must not be negative")
     if args.playout_value and args.engine is not None:
         ap.error("--playout-value configures the in-process engine: it does not go with --engine")
+    if args.playout_patterns is not None and not args.playout_value:
+        ap.error("--playout-patterns weights the playouts of --playout-value: it needs --playout-value N")
     return args
 
 
@@ -259,9 +263,10 @@ def main(argv=None):
         from .mcts_native import Position
         pi = nnet.HipPolicyNet(load_state_dict(args.p), precision=args.precision)
     if args.engine is None and args.playout_value > 0:
+        more = {} if args.playout_patterns is None else {"playout_patterns": args.playout_patterns}
         a = InProcessEngine(NativeGTP(Position(), pi, None, no_sim=True, time_lim=None, n_rollouts=args.r,
-                                      playout_value=args.playout_value),
-                            name=args.engine_name or f"boke-hip-r{args.r}-mc{args.playout_value}")
+                                      playout_value=args.playout_value, **more),
+                            name=args.engine_name or f"boke-hip-r{args.r}-mc{args.playout_value}" + ("-pat" if more else ""))
     elif args.engine is None:
         val = nnet.HipValueNet(load_state_dict(args.v), precision=args.precision)
         a = InProcessEngine(NativeGTP(Position(), pi, val, no_sim=True, time_lim=None, n_rollouts=args.r),

@@ -132,7 +132,8 @@ class _ChildrenView(Mapping):
 class NativeMCTS:
     """kwargs as the reference's MCTS: expand_thresh, exploration_weight, noise_weight, device; plus
     `evaluator` (anything with __call__(feats_u8, n_policy) -> (probs, values)) and `max_batch`; `playout_value=N` (with
-    `playout_seed`, and `playout_rules="host"` for the host mirror where there is no GPU): rollout.PlayoutEvaluator."""
+    `playout_seed`, and `playout_rules="host"` for the host mirror where there is no GPU): rollout.PlayoutEvaluator;
+    `playout_patterns=` (a patterns.PatternTable or the path of one, with playout_value): its pattern-weighted playouts."""
 
     def __init__(self, root=None, policy_net=None, value_net=None, **kwargs):
         if policy_net is None and kwargs.get("evaluator") is None:
@@ -143,6 +144,9 @@ class NativeMCTS:
         self.playout_value = int(kwargs.get("playout_value") or 0)
         self.playout_seed = int(kwargs.get("playout_seed", 0))
         self.playout_rules = kwargs.get("playout_rules", "device")     # "host": the playouts on the host rules, the same bits
+        self.playout_patterns = kwargs.get("playout_patterns")         # None: uniformly random playouts
+        if self.playout_patterns is not None and not self.playout_value:
+            raise TypeError("playout_patterns weights the playouts of playout_value=N: it needs playout_value")
         if self.playout_value:
             if self.playout_value < 0:
                 raise ValueError("playout_value must not be negative")
@@ -228,7 +232,10 @@ class NativeMCTS:
         if not callable(get):
             raise RuntimeError(self.NO_HIP)
         from . import rollout
-        return rollout.PlayoutEvaluator(get(), self.playout_value, seed=self.playout_seed, rules=self.playout_rules)
+        if self.playout_patterns is None:
+            return rollout.PlayoutEvaluator(get(), self.playout_value, seed=self.playout_seed, rules=self.playout_rules)
+        return rollout.PlayoutEvaluator(get(), self.playout_value, seed=self.playout_seed, rules=self.playout_rules,
+                                        patterns=self.playout_patterns)
 
     def _evaluator_from_nets(self):
         policy_net, value_net = self.policy_net, self.value_net

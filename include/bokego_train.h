@@ -215,6 +215,26 @@ int bkt_area_score(const void *pos, int batch, float komi, float *score, int8_t 
 int bkt_random_playouts(void *pos, int batch, uint64_t seed, const uint32_t *counters, int max_plies, uint8_t *over,
                         int32_t *plies, int16_t *moves, int32_t *status, void *stream);
 
+/* The 3x3 pattern index of every point of every record (bokego_amd/patterns.py), occupied or not:
+ * codes[b*81 + s] for s = 9r + c, relative to the record's side to move (black on an even turn).  The eight neighbours in
+ * the order (dr, dc) = (-1,0) (+1,0) (0,-1) (0,+1) (-1,-1) (-1,+1) (+1,-1) (+1,+1) give a 2-bit state each -- 0 empty, 1 a
+ * stone of the side to move, 2 an opponent stone, 3 off the board -- and code = sum of state_i << 2i (16 bits).  near = 1
+ * when the record's last_move is a board point with max(|r - r_lm|, |c - c_lm|) <= 1, else 0 (a pass, no move).
+ * index = near << 16 | code, in [0, BKT_PATTERN_ENTRIES).  The records are read only.
+ * 1 <= batch <= BKT_MAX_BATCH; pos and codes must not be NULL; else BKT_ERR_ARG. */
+#define BKT_PATTERN_ENTRIES 131072
+int bkt_pattern_codes(const void *pos, int batch, int32_t *codes, void *stream);
+
+/* Whole pattern-weighted playouts in ONE launch: bkt_random_playouts' contract in every respect except the draw.  table:
+ * uint16 [BKT_PATTERN_ENTRIES] on the device; the weight of a point s is w_s = max(table[index of s], 1).  At a ply with
+ * the playable set P and the same Philox word x0:
+ *   S = the sum of w_s over P (at most 81 * 65535 < 2^23);  t = ((uint64_t)(x0 >> 8) * S) >> 24;
+ *   the move is the first point of P, in ascending order, whose inclusive prefix sum of w exceeds t; BK_PASS when P is
+ *   empty.  Integer arithmetic only: no float, no fallback rule.  A table of one constant plays bkt_random_playouts' games.
+ * The argument checks are bkt_random_playouts'; a NULL table is BKT_ERR_ARG too, and nothing is launched. */
+int bkt_pattern_playouts(void *pos, int batch, uint64_t seed, const uint32_t *counters, const uint16_t *table, int max_plies,
+                         uint8_t *over, int32_t *plies, int16_t *moves, int32_t *status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
