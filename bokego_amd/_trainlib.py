@@ -47,6 +47,8 @@ SYMBOLS = {
     "bkt_random_playouts": (_I, [_P, _I, _U64, _P, _I, _P, _P, _P, _P, _P]),
     "bkt_pattern_codes": (_I, [_P, _I, _P, _P]),
     "bkt_pattern_playouts": (_I, [_P, _I, _U64, _P, _P, _I, _P, _P, _P, _P, _P]),
+    "bkt_tactical_codes": (_I, [_P, _I, _P, _P]),
+    "bkt_tactical_playouts": (_I, [_P, _I, _U64, _P, _P, _P, _I, _P, _P, _P, _P, _P]),
 }
 MAX_BATCH = 65536          # BKT_MAX_BATCH
 PRECISIONS = ("fp32", "bf16")
@@ -54,6 +56,7 @@ POS_BYTES = 192            # sizeof(bk_pos)
 MOVE_NONE = -2             # BKT_MOVE_NONE: bkt_playout_step leaves the row alone
 MAX_PLAYOUT_PLIES = 1024   # BKT_MAX_PLAYOUT_PLIES
 PATTERN_ENTRIES = 131072   # BKT_PATTERN_ENTRIES
+TACTIC_ENTRIES = 64        # BKT_TACTIC_ENTRIES
 
 _lib = None
 
@@ -356,7 +359,7 @@ def area_score(pos, komi=5.5, owner=False):
 
 
 def _playouts(name, pos, seed, counters, table, max_plies, over, history):
-    """bkt_random_playouts, or bkt_pattern_playouts with its table argument after the counters."""
+    """bkt_random_playouts, or bkt_pattern_playouts / bkt_tactical_playouts with their table arguments after the counters."""
     B, max_plies = _pos_batch(pos), int(max_plies)
     if not 1 <= max_plies <= MAX_PLAYOUT_PLIES:
         raise ValueError(f"max_plies must be 1..{MAX_PLAYOUT_PLIES}, got {max_plies}")
@@ -396,4 +399,24 @@ def pattern_codes(pos):
     codes = torch.empty((B, 81), dtype=torch.int32, device=pos.device)
     _check(load().bkt_pattern_codes(_dev(pos, "pos", dtype=torch.uint8), B, _dev(codes, "codes", dtype=torch.int32),
                                     _stream(pos)), "bkt_pattern_codes")
+    return codes
+
+
+def tactical_playouts(pos, seed, counters, table, tactics, max_plies, over=None, history=True):
+    """pattern_playouts whose weights are multiplied by a second table (bkt_tactical_playouts): tactics int16
+    [TACTIC_ENTRIES] on the device of pos, the bits of the uint16 entries (256: neutral), indexed by the tactical code;
+    table: pattern_playouts' table, or None for no patterns (every pattern weight 256)."""
+    if tactics.device != pos.device or (table is not None and table.device != pos.device):
+        raise ValueError("the pattern table and the tactics table must be on the device of pos")
+    return _playouts("bkt_tactical_playouts", pos, seed, counters,
+                     (None if table is None else _dev(table, "table", (PATTERN_ENTRIES,), torch.int16),
+                      _dev(tactics, "tactics", (TACTIC_ENTRIES,), torch.int16)), max_plies, over, history)
+
+
+def tactical_codes(pos):
+    """The tactical code of every point (bkt_tactical_codes): pos uint8 [B,192] (read only) -> int32 [B,81]."""
+    B = _pos_batch(pos)
+    codes = torch.empty((B, 81), dtype=torch.int32, device=pos.device)
+    _check(load().bkt_tactical_codes(_dev(pos, "pos", dtype=torch.uint8), B, _dev(codes, "codes", dtype=torch.int32),
+                                     _stream(pos)), "bkt_tactical_codes")
     return codes

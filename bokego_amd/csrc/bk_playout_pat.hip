@@ -2,7 +2,7 @@
 // and through it bk_playout.hip, so that both still compile alone for the resource tests that pin their kernels), and
 // appended after them the pattern-weighted playouts of bokego_amd/patterns.py (include/bokego_train.h):
 // bkt_pattern_codes, the 3x3 pattern index of every point of a record, and bkt_pattern_playouts, bkt_random_playouts with a
-// weighted draw.
+// weighted draw.  bk_playout_tac.hip, included as text at the end, adds the tactical playouts on top of these.
 //
 // The index of a point s = 9r + c, relative to the side to move: the eight neighbours in the order (-1,0) (+1,0) (0,-1)
 // (0,+1) (-1,-1) (-1,+1) (+1,-1) (+1,+1) give two bits each (0 empty, 1 the mover's stone, 2 the opponent's, 3 off the
@@ -179,3 +179,5 @@ extern "C" int bkt_pattern_playouts(void* pos, int batch, uint64_t seed, const u
                        max_plies, over, plies, moves, status);
     return hipGetLastError() == hipSuccess ? BKT_OK : BKT_ERR_HIP;
 }
+
+#include "bk_playout_tac.hip"   // the tactical playouts: text, part of this translation unit

@@ -18,7 +18,9 @@ score of the board as it stands and the reference's command list.
 `--playout-value N` (N > 0) searches without a value net: the value of a leaf is the share of N uniformly random playouts
 its side to move wins (rollout.PlayoutEvaluator).  Not together with `-v`, `--simulate` or `--python-tree`; it
 needs the HIP engine as `--rollout-score` does.  `--playout-patterns FILE` (with `--playout-value`) draws the playouts'
-moves in proportion to the 3x3 pattern weights of a table fitted by `python -m bokego_amd.patterns fit`.
+moves in proportion to the 3x3 pattern weights of a table fitted by `python -m bokego_amd.patterns fit` (DESIGN 17);
+`--playout-tactics FILE` (with `--playout-value`) multiplies them by the capture / escape / atari weights of a table fitted
+by `python -m bokego_amd.tactics fit`.
 """
 import argparse
 import os
@@ -463,6 +465,9 @@ def build_parser():
     ap.add_argument("--playout-patterns", default=None, metavar="FILE",
                     help="with --playout-value: draw the playouts' moves by the 3x3 pattern weights of this table "
                          "(python -m bokego_amd.patterns fit)")
+    ap.add_argument("--playout-tactics", default=None, metavar="FILE",
+                    help="with --playout-value: multiply the playouts' weights by the tactical weights of this table "
+                         "(python -m bokego_amd.tactics fit)")
     ap.add_argument("--python-tree", action="store_true", help="search with the Python tree instead of the native one")
     ap.set_defaults(v_given=False)
     return ap
@@ -490,6 +495,8 @@ def parse_args(argv=None):
                 ap.error(f"--playout-value takes the place of a value net: not allowed with {flag}")
     if args.playout_patterns is not None and not args.playout_value:
         ap.error("--playout-patterns weights the playouts of --playout-value: it needs --playout-value N")
+    if args.playout_tactics is not None and not args.playout_value:
+        ap.error("--playout-tactics weights the playouts of --playout-value: it needs --playout-value N")
     return args
 
 
@@ -505,6 +512,8 @@ def main(argv=None):
     more = {"playout_value": args.playout_value} if args.playout_value else {}
     if args.playout_patterns is not None:
         more["playout_patterns"] = args.playout_patterns
+    if args.playout_tactics is not None:
+        more["playout_tactics"] = args.playout_tactics
     gtp = cls(root, pi, val, no_sim=not args.simulate, time_lim=None if args.r else args.t, n_rollouts=args.r, pondering=args.ponder,
               rollout_score=args.rollout_score, **more)
     gtp.start()

@@ -233,6 +233,8 @@ def parse_args(argv=None):
                          "playouts (-v is then not loaded; not with --engine)")
     ap.add_argument("--playout-patterns", default=None, metavar="FILE",
                     help="with --playout-value: the table of 3x3 pattern weights its playouts draw their moves by")
+    ap.add_argument("--playout-tactics", default=None, metavar="FILE",
+                    help="with --playout-value: the table of tactical weights that multiply its playouts' weights")
     ap.add_argument("--opponent", default="policy", help='"policy" (raw policy, no search) or a GTP command line')
     ap.add_argument("--komi", type=float, default=5.5)
     ap.add_argument("--sgf", default=None, help="prefix for SGF records")
@@ -251,6 +253,8 @@ def parse_args(argv=None):
         ap.error("--playout-value configures the in-process engine: it does not go with --engine")
     if args.playout_patterns is not None and not args.playout_value:
         ap.error("--playout-patterns weights the playouts of --playout-value: it needs --playout-value N")
+    if args.playout_tactics is not None and not args.playout_value:
+        ap.error("--playout-tactics weights the playouts of --playout-value: it needs --playout-value N")
     return args
 
 
@@ -264,6 +268,8 @@ def main(argv=None):
         pi = nnet.HipPolicyNet(load_state_dict(args.p), precision=args.precision)
     if args.engine is None and args.playout_value > 0:
         more = {} if args.playout_patterns is None else {"playout_patterns": args.playout_patterns}
+        if args.playout_tactics is not None:
+            more["playout_tactics"] = args.playout_tactics
         a = InProcessEngine(NativeGTP(Position(), pi, None, no_sim=True, time_lim=None, n_rollouts=args.r,
                                       playout_value=args.playout_value, **more),
                             name=args.engine_name or f"boke-hip-r{args.r}-mc{args.playout_value}" + ("-pat" if more else ""))

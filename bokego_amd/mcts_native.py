@@ -133,7 +133,8 @@ class NativeMCTS:
     """kwargs as the reference's MCTS: expand_thresh, exploration_weight, noise_weight, device; plus
     `evaluator` (anything with __call__(feats_u8, n_policy) -> (probs, values)) and `max_batch`; `playout_value=N` (with
     `playout_seed`, and `playout_rules="host"` for the host mirror where there is no GPU): rollout.PlayoutEvaluator;
-    `playout_patterns=` (a patterns.PatternTable or the path of one, with playout_value): its pattern-weighted playouts."""
+    `playout_patterns=` (a patterns.PatternTable or the path of one, with playout_value): its pattern-weighted playouts;
+    `playout_tactics=` (a tactics.TacticTable or the path of one, with playout_value): its tactical weights."""
 
     def __init__(self, root=None, policy_net=None, value_net=None, **kwargs):
         if policy_net is None and kwargs.get("evaluator") is None:
@@ -147,6 +148,9 @@ class NativeMCTS:
         self.playout_patterns = kwargs.get("playout_patterns")         # None: uniformly random playouts
         if self.playout_patterns is not None and not self.playout_value:
             raise TypeError("playout_patterns weights the playouts of playout_value=N: it needs playout_value")
+        self.playout_tactics = kwargs.get("playout_tactics")           # None: no tactical weights
+        if self.playout_tactics is not None and not self.playout_value:
+            raise TypeError("playout_tactics weights the playouts of playout_value=N: it needs playout_value")
         if self.playout_value:
             if self.playout_value < 0:
                 raise ValueError("playout_value must not be negative")
@@ -232,10 +236,12 @@ class NativeMCTS:
         if not callable(get):
             raise RuntimeError(self.NO_HIP)
         from . import rollout
-        if self.playout_patterns is None:
-            return rollout.PlayoutEvaluator(get(), self.playout_value, seed=self.playout_seed, rules=self.playout_rules)
-        return rollout.PlayoutEvaluator(get(), self.playout_value, seed=self.playout_seed, rules=self.playout_rules,
-                                        patterns=self.playout_patterns)
+        more = {}
+        if self.playout_patterns is not None:
+            more["patterns"] = self.playout_patterns
+        if self.playout_tactics is not None:
+            more["tactics"] = self.playout_tactics
+        return rollout.PlayoutEvaluator(get(), self.playout_value, seed=self.playout_seed, rules=self.playout_rules, **more)
 
     def _evaluator_from_nets(self):
         policy_net, value_net = self.policy_net, self.value_net

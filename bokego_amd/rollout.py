@@ -28,10 +28,13 @@ point in ascending order -- so the host mirror (rules="host") equals the device 
 playout_value turns it into the classical Monte-Carlo value of a position, the share of n such playouts the side to
 move wins, and PlayoutEvaluator hands that value to the tree search in place of a value net (priors from the policy).
 
-    python -m bokego_amd.rollout --sgf FILE [--move K] --random [--patterns FILE] [-n 256] [--seed S]   # the one-launch playouts
+    python -m bokego_amd.rollout --sgf FILE [--move K] --random [--patterns FILE] [--tactics FILE] [-n 256] [--seed S]   # one launch
 
 patterns= (a patterns.PatternTable; --patterns FILE) draws those moves in proportion to 3x3 pattern weights instead
 (bkt_pattern_playouts; bokego_amd/patterns.py): opt-in, and with patterns=None every call is what it was.
+tactics= (a tactics.TacticTable; --tactics FILE) multiplies those weights -- or, without patterns, a constant -- by the
+capture / escape / atari weight of each point's tactical code (bkt_tactical_playouts; bokego_amd/tactics.py):
+opt-in likewise, and with tactics=None the same launches run as before.
 
 rules="host" is one loop (_playout_host) on the host rules with the same draws (lockstep's play_host, features_batch
 and area_score_host, bk_pos_is_legal, bk_pos_possible_eye, lockstep.sample_host in float64): the reference the tests
@@ -303,9 +306,10 @@ def select_index(x0, n):
 
 
 
-def _random_host(pos, key, ctr, max_plies, komi, history, table=None):
+def _random_host(pos, key, ctr, max_plies, komi, history, table=None, tactics=None):
     """random_playouts on the host: the select_index-th playable point in ascending order, a pass when there is none; with
-    a table (a patterns.PatternTable), patterns.select_weighted on the entries of the points' pattern indices."""
+    a table (a patterns.PatternTable), patterns.select_weighted on the entries of the points' pattern indices; with tactics
+    (a tactics.TacticTable), tactics.select_tactical on those entries (or none) and the entries of the tactical codes."""
     def choose(k, recs, live, ok, x0):
         n = ok.sum(1)
         pick = np.argmax(np.cumsum(ok, 1) > select_index(x0, n).astype(np.int64)[:, None], 1)
@@ -314,9 +318,19 @@ def _random_host(pos, key, ctr, max_plies, komi, history, table=None):
     def choose_weighted(k, recs, live, ok, x0):
         return PT.select_weighted(x0, table.entries(PT.codes_host(recs[live])), ok)
 
+    def choose_tactical(k, recs, live, ok, x0):
+        part = recs[live]
+        entries = None if table is None else table.entries(PT.codes_host(part))
+        return TC.select_tactical(x0, entries, tactics.entries(TC.codes_host(part)), ok)
+
     if table is not None:
         from . import patterns as PT
-    return _playout_host(pos, key, ctr, max_plies, komi, choose if table is None else choose_weighted, "selected", history)
+    if tactics is not None:
+        from . import tactics as TC
+        choose = choose_tactical
+    elif table is not None:
+        choose = choose_weighted
+    return _playout_host(pos, key, ctr, max_plies, komi, choose, "selected", history)
 
 
 def _table(patterns):
@@ -327,8 +341,16 @@ def _table(patterns):
     return as_table(patterns)
 
 
+def _tactics(tactics):
+    """tactics= of the callers below: None, a tactics.TacticTable, a uint16 array or a path -> None or a TacticTable."""
+    if tactics is None:
+        return None
+    from .tactics import as_tactics
+    return as_tactics(tactics)
+
+
 def random_playouts(pos, seed, counters=None, max_plies=MAX_PLIES, rules="device", komi=L.KOMI, history=True, device=None,
-                    patterns=None):
+                    patterns=None, tactics=None):
     """Play the records pos (uint8 [G,192], numpy or a tensor; not modified) to the end of the game with uniformly random
     eye-safe moves -> Finished, the fields finish_games returns (moves is None with history=False; no min_margin: nothing
     is rounded).  rules="device": one bkt_random_playouts launch per T.MAX_BATCH rows, then bkt_area_score.  rules="host":
@@ -337,9 +359,11 @@ def random_playouts(pos, seed, counters=None, max_plies=MAX_PLIES, rules="device
     default_counters, as finish_games.  A row's game depends on its record, the seed and its counters only.
     These are not finish_games(engine=None)'s games: that sampler goes through a float CDF.
     patterns: None, or a table of 3x3 pattern weights (patterns.PatternTable, or what patterns.as_table takes): the move is
-    then drawn in proportion to the weights of the playable points (bkt_pattern_playouts), on the same words."""
+    then drawn in proportion to the weights of the playable points (bkt_pattern_playouts), on the same words.
+    tactics: None, or a table of tactical weights (tactics.TacticTable, or what tactics.as_tactics takes) that multiply the
+    pattern weights, or a constant without patterns (bkt_tactical_playouts)."""
     L.check_rules(rules)
-    table = _table(patterns)
+    table, tactics = _table(patterns), _tactics(tactics)
     max_plies = int(max_plies)
     if not 1 <= max_plies <= 1024:
         raise ValueError("max_plies must be 1..1024 (BKT_MAX_PLAYOUT_PLIES)")
@@ -349,21 +373,26 @@ def random_playouts(pos, seed, counters=None, max_plies=MAX_PLIES, rules="device
         counters = default_counters(G, record_turns(_numpy(pos)))
     key = L.seed_u64(seed)
     if rules == "host":
-        return _random_host(pos, key, L.counters_to_host(counters, G), max_plies, komi, history, table)
+        return _random_host(pos, key, L.counters_to_host(counters, G), max_plies, komi, history, table, tactics)
     dev = _device(device, None, pos)
     pos = L.records_to_device(pos, dev)
     ctr = L.counters_to_device(counters, G, dev, clone=False)
-    over, plies, moves, status = _play_random_device(pos, key, ctr, max_plies, history, table)
+    over, plies, moves, status = _play_random_device(pos, key, ctr, max_plies, history, table, tactics)
     score, owner = _area_score_device(pos, komi, True)
     _check_status(status, "selected")
     return _finished(pos, moves, plies.cpu().numpy().astype(np.int64), over.cpu().numpy() != 0, score.cpu().numpy(),
                      owner.cpu().numpy())
 
 
-def _play_random_device(pos, key, ctr, max_plies, history, table=None):
-    """pos uint8 [G,192] and ctr int32 [G,4] on the device; pos is played on in place; table: None or a PatternTable.
+def _play_random_device(pos, key, ctr, max_plies, history, table=None, tactics=None):
+    """pos uint8 [G,192] and ctr int32 [G,4] on the device; pos is played on in place; table: None or a PatternTable;
+    tactics: None or a TacticTable.
     -> (over uint8 [G], plies int32 [G], moves int16 [G,max_plies] or None, status int32 [G]), T.MAX_BATCH rows per launch."""
-    if table is None:
+    if tactics is not None:
+        w, t = None if table is None else table.device(pos.device), tactics.device(pos.device)
+        parts = [T.tactical_playouts(pos[s:s + T.MAX_BATCH], key, ctr[s:s + T.MAX_BATCH], w, t, max_plies, history=history)
+                 for s in range(0, len(pos), T.MAX_BATCH)]
+    elif table is None:
         parts = [T.random_playouts(pos[s:s + T.MAX_BATCH], key, ctr[s:s + T.MAX_BATCH], max_plies, history=history)
                  for s in range(0, len(pos), T.MAX_BATCH)]
     else:
@@ -395,30 +424,30 @@ def _check_playouts(n):
     return n
 
 
-def _playout_value_device(recs, n, key, komi, max_plies=MAX_PLIES, table=None):
+def _playout_value_device(recs, n, key, komi, max_plies=MAX_PLIES, table=None, tactics=None):
     """recs: a uint8 [R,192] tensor on the device -> float32 [R] on the device; nothing here waits for the device."""
     pos = recs.repeat_interleave(n, 0)                                     # a copy: the caller's records stay
-    _play_random_device(pos, key, L.value_counters_device(recs, n), max_plies, False, table)
+    _play_random_device(pos, key, L.value_counters_device(recs, n), max_plies, False, table, tactics)
     black_wins = _area_score_device(pos, komi, False).view(len(recs), n) > 0
     w = (black_wins == L.black_to_move(recs)[:, None]).sum(1)
     return (2 * w - n).to(torch.float32) / n
 
 
-def playout_value(recs, n, seed, rules="device", komi=L.KOMI, device=None, patterns=None):
+def playout_value(recs, n, seed, rules="device", komi=L.KOMI, device=None, patterns=None, tactics=None):
     """The Monte-Carlo value of each record, float32 [R] (numpy): (2 w - n) / n, w = the number of n uniformly random
     eye-safe playouts (random_playouts, capped at MAX_PLIES and then scored as they stand) that the side to move wins --
     black wins iff the area score is > 0.  A pure function of the record, `seed` and `n` (value_counters): the row index
-    and the rest of the batch do not enter.  recs: uint8 [R,192], numpy or a tensor.  patterns: as random_playouts."""
+    and the rest of the batch do not enter.  recs: uint8 [R,192], numpy or a tensor.  patterns, tactics: as random_playouts."""
     L.check_rules(rules)
-    table = _table(patterns)
+    table, tactics = _table(patterns), _tactics(tactics)
     n = _check_playouts(n)
     _check_records(recs)
     key = L.seed_u64(seed)
     if rules == "device":
         t = L.records_to_device(recs, _device(device, None, recs), clone=False)
-        return _playout_value_device(t, n, key, komi, table=table).cpu().numpy()
+        return _playout_value_device(t, n, key, komi, table=table, tactics=tactics).cpu().numpy()
     recs = np.array(_numpy(recs), np.uint8, order="C")
-    fin = _random_host(np.repeat(recs, n, 0), key, value_counters(recs, n), MAX_PLIES, komi, False, table)
+    fin = _random_host(np.repeat(recs, n, 0), key, value_counters(recs, n), MAX_PLIES, komi, False, table, tactics)
     w = (fin.score.reshape(len(recs), n) > 0) == L.black_to_move(recs)[:, None]
     return ((2 * w.sum(1) - n).astype(np.float32) / np.float32(n)).astype(np.float32)
 
@@ -433,9 +462,10 @@ class PlayoutEvaluator:
     step loop as its own bk_evaluator, which would compute no playouts -- this class goes through callback_evaluator."""
     wants_positions = True
 
-    def __init__(self, engine, playouts=64, seed=0, rules="device", komi=L.KOMI, patterns=None):
+    def __init__(self, engine, playouts=64, seed=0, rules="device", komi=L.KOMI, patterns=None, tactics=None):
         L.check_rules(rules)
         self.patterns = _table(patterns)                                  # None: uniformly random playouts
+        self.tactics = _tactics(tactics)                                  # None: no tactical weights (DESIGN 18)
         self.policy_engine = engine
         self.playouts = _check_playouts(playouts)
         self.seed = L.seed_u64(seed)
@@ -453,11 +483,12 @@ class PlayoutEvaluator:
             ticket = self.policy_engine.submit_positions(recs[:n_policy], logits=False, probs=True, value=False,
                                                          n_policy=n_policy)
         if self.rules == "host":
-            values = playout_value(recs, self.playouts, self.seed, rules="host", komi=self.komi, patterns=self.patterns)
+            values = playout_value(recs, self.playouts, self.seed, rules="host", komi=self.komi, patterns=self.patterns,
+                                   tactics=self.tactics)
         else:
             dev = _device(None, self.policy_engine)
             values = _playout_value_device(torch.from_numpy(recs).to(dev), self.playouts, self.seed, self.komi,
-                                           table=self.patterns)
+                                           table=self.patterns, tactics=self.tactics)
         return ticket, values
 
     def finish(self, handle, normalise=None):
@@ -500,21 +531,23 @@ def _as_records(positions):
 
 
 def rollout_score(positions, engine, n=256, seed=0, komi=L.KOMI, rules="device", max_plies=MAX_PLIES, device=None,
-                  one_launch=False, patterns=None):
+                  one_launch=False, patterns=None, tactics=None):
     """n playouts (finish_games) of every position -> a list of RolloutScore.  positions: go.Game objects or uint8
     [P,192] records.  Playout j of position i is game i * n + j of one finish_games call: deterministic per seed.
     one_launch=True (engine must be None): the uniformly random playouts of random_playouts instead, any number of rows;
-    patterns (with one_launch=True only): random_playouts' table of pattern weights."""
+    patterns, tactics (with one_launch=True only): random_playouts' tables of pattern and of tactical weights."""
     recs = _as_records(positions)
     n = _check_playouts(n)
     P = len(recs)
     if patterns is not None and not one_launch:
         raise ValueError("patterns weight the one-launch playouts: one_launch=True")
+    if tactics is not None and not one_launch:
+        raise ValueError("tactics weight the one-launch playouts: one_launch=True")
     if one_launch:
         if engine is not None:
             raise ValueError("one_launch=True plays uniformly random playouts: engine must be None")
         fin = random_playouts(np.repeat(recs, n, 0), seed, max_plies=max_plies, rules=rules, komi=komi, history=False,
-                              device=device, patterns=patterns)
+                              device=device, patterns=patterns, tactics=tactics)
     else:
         fin = finish_games(np.repeat(recs, n, 0), engine, seed, max_plies=max_plies, rules=rules, device=device, komi=komi)
     owner = fin.owner.reshape(P, n, 81).astype(np.float64).mean(1)
@@ -566,6 +599,8 @@ def _parse(argv):
                     help="uniformly random playouts, each played to its end inside one kernel launch (not with -p)")
     ap.add_argument("--patterns", default=None, metavar="FILE",
                     help="with --random: draw the moves by the 3x3 pattern weights of this table (python -m bokego_amd.patterns fit)")
+    ap.add_argument("--tactics", default=None, metavar="FILE",
+                    help="with --random: multiply the weights by the tactical weights of this table (python -m bokego_amd.tactics fit)")
     ap.add_argument("-n", dest="n", type=int, default=256, help="playouts")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--komi", type=float, default=L.KOMI)
@@ -577,6 +612,8 @@ def _parse(argv):
         ap.error("--random plays without a network: not with -p")
     if args.patterns is not None and not args.random:
         ap.error("--patterns weights the one-launch playouts: it needs --random")
+    if args.tactics is not None and not args.random:
+        ap.error("--tactics weights the one-launch playouts: it needs --random")
     if args.move is not None and args.move < 0:
         ap.error("--move must not be negative")
     if not (0 <= args.seed < 2 ** 64):
@@ -608,7 +645,8 @@ def main(argv=None):
         eng = policy_engine(load_weights(args.p), args.device, min(args.n, 4096))
     try:
         r = rollout_score([game], eng, n=args.n, seed=args.seed, komi=args.komi,
-                          device=torch.device("cuda", args.device), one_launch=args.random, patterns=args.patterns)[0]
+                          device=torch.device("cuda", args.device), one_launch=args.random, patterns=args.patterns,
+                          tactics=args.tactics)[0]
     finally:
         if eng is not None:
             eng.close()

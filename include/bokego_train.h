@@ -235,6 +235,34 @@ int bkt_pattern_codes(const void *pos, int batch, int32_t *codes, void *stream);
 int bkt_pattern_playouts(void *pos, int batch, uint64_t seed, const uint32_t *counters, const uint16_t *table, int max_plies,
                          uint8_t *over, int32_t *plies, int16_t *moves, int32_t *status, void *stream);
 
+/* The tactical code of every point of every record (bokego_amd/tactics.py), occupied or not:
+ * codes[b*81 + q].  With F the 27 planes bk_features_batch_u8(record, fresh = 0) gives (a non-zero entry of planes 6..26
+ * holds the count, capped at 7):
+ *   cap = the value on planes 20..26 at q (stones captured by playing q), or 0;  C = min(cap, 3);
+ *   la  = the value on planes 13..19 at q (liberties after playing q), or 0 when q is not legal;
+ *         A = 0 for la <= 1, 1 for la == 2, 2 for la >= 3;
+ *   E = 1 when some on-board 4-neighbour t of q has F[0][t] != 0 and F[6][t] != 0 (a stone of the side to move whose
+ *       cached liberty count is 1);
+ *   G = 1 when some on-board 4-neighbour t has F[1][t] != 0 and F[7][t] != 0 (an opponent stone whose cached count is 2);
+ *   code = C | A << 2 | E << 4 | G << 5, in [0, BKT_TACTIC_ENTRIES).
+ * The liberty planes are the reference's cache and can be stale: the code is a function of the record's bytes.
+ * The records are read only.  1 <= batch <= BKT_MAX_BATCH; pos and codes must not be NULL; else BKT_ERR_ARG. */
+#define BKT_TACTIC_ENTRIES 64
+int bkt_tactical_codes(const void *pos, int batch, int32_t *codes, void *stream);
+
+/* Whole tactical playouts in ONE launch: bkt_pattern_playouts' contract with a second table.  tactics: uint16
+ * [BKT_TACTIC_ENTRIES] on the device, 256 = neutral; table: as bkt_pattern_playouts', or NULL for no patterns.  The weight
+ * of a playable point s is
+ *   P = max(table[pattern index of s], 1), or 256 when table is NULL;  T = tactics[tactical code of s];
+ *   w_s = max(1, (P * T) >> 8)      (a 32-bit product; w_s < 2^24, so a row's sum S <= 81 * 2^24 < 2^31)
+ * and the draw is bkt_pattern_playouts': t = ((uint64_t)(x0 >> 8) * S) >> 24 on the same Philox word, the first point of
+ * P in ascending order whose inclusive prefix sum of w exceeds t, BK_PASS when P is empty.  A tactics table of 256
+ * everywhere plays bkt_pattern_playouts' games, and with table NULL bkt_random_playouts' games, byte for byte.
+ * The argument checks are bkt_pattern_playouts' except that table may be NULL; a NULL tactics is BKT_ERR_ARG. */
+int bkt_tactical_playouts(void *pos, int batch, uint64_t seed, const uint32_t *counters, const uint16_t *table,
+                          const uint16_t *tactics, int max_plies, uint8_t *over, int32_t *plies, int16_t *moves,
+                          int32_t *status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
