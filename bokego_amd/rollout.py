@@ -388,17 +388,15 @@ def _play_random_device(pos, key, ctr, max_plies, history, table=None, tactics=N
     """pos uint8 [G,192] and ctr int32 [G,4] on the device; pos is played on in place; table: None or a PatternTable;
     tactics: None or a TacticTable.
     -> (over uint8 [G], plies int32 [G], moves int16 [G,max_plies] or None, status int32 [G]), T.MAX_BATCH rows per launch."""
+    w = None if table is None else table.device(pos.device)
     if tactics is not None:
-        w, t = None if table is None else table.device(pos.device), tactics.device(pos.device)
-        parts = [T.tactical_playouts(pos[s:s + T.MAX_BATCH], key, ctr[s:s + T.MAX_BATCH], w, t, max_plies, history=history)
-                 for s in range(0, len(pos), T.MAX_BATCH)]
+        play, tables = T.tactical_playouts, (w, tactics.device(pos.device))
     elif table is None:
-        parts = [T.random_playouts(pos[s:s + T.MAX_BATCH], key, ctr[s:s + T.MAX_BATCH], max_plies, history=history)
-                 for s in range(0, len(pos), T.MAX_BATCH)]
+        play, tables = T.random_playouts, ()
     else:
-        w = table.device(pos.device)
-        parts = [T.pattern_playouts(pos[s:s + T.MAX_BATCH], key, ctr[s:s + T.MAX_BATCH], w, max_plies, history=history)
-                 for s in range(0, len(pos), T.MAX_BATCH)]
+        play, tables = T.pattern_playouts, (w,)
+    parts = [play(pos[s:s + T.MAX_BATCH], key, ctr[s:s + T.MAX_BATCH], *tables, max_plies, history=history)
+             for s in range(0, len(pos), T.MAX_BATCH)]
     if len(parts) == 1:
         return parts[0]
     return tuple(None if col[0] is None else torch.cat(col) for col in zip(*parts))

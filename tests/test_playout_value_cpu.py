@@ -258,3 +258,20 @@ def test_the_kernel_builds_without_spills_or_scratch(tmp_path):
     assert len(spills) == 2 * len(kernels) and len(scratch) == len(kernels)
     assert all(int(n) == 0 for _, n in spills), spills
     assert all(int(n) == 0 for n in scratch), scratch
+
+
+@pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")
+def test_the_playout_kernels_keep_their_register_and_lds_budget(tmp_path):
+    """The three playout kernels are one ply loop (bk_playout_mc.hip's playouts<Draw>) around __noinline__ helpers that keep
+    it within 128 VGPRs: 4 waves/SIMD.  LDS bytes per block: what the three separate kernels used before they shared it."""
+    r = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
+                        "-Rpass-analysis=kernel-resource-usage", os.path.join(CSRC, "bk_playout_pat.hip"),
+                        "-o", str(tmp_path / "t.so")], capture_output=True, text=True, cwd=str(tmp_path))
+    assert r.returncode == 0, r.stderr[-2000:]
+    blocks = re.split(r"Function Name: ", r.stderr)[1:]
+    for name, lds in (("random_playouts_kernel", 5088), ("pattern_playouts_kernel", 6128), ("tactical_playouts_kernel", 12832)):
+        (block,) = [b for b in blocks if name in b.split()[0]]
+        field = lambda pat: int(re.search(pat + r": (\d+)", block).group(1))  # noqa: E731
+        assert field(r"Occupancy \[waves/SIMD\]") >= 4 and field(r" VGPRs") <= 128, block
+        assert field(r"ScratchSize \[bytes/lane\]") == 0 and field(r"SGPRs Spill") == 0 and field(r"VGPRs Spill") == 0, block
+        assert field(r"LDS Size \[bytes/block\]") <= lds, block
