@@ -49,6 +49,7 @@ SYMBOLS = {
     "bkt_pattern_playouts": (_I, [_P, _I, _U64, _P, _P, _I, _P, _P, _P, _P, _P]),
     "bkt_tactical_codes": (_I, [_P, _I, _P, _P]),
     "bkt_tactical_playouts": (_I, [_P, _I, _U64, _P, _P, _P, _I, _P, _P, _P, _P, _P]),
+    "bkt_amaf_counts": (_I, [_P, _I, _P, _I, _I, _P, _P, _P]),
 }
 MAX_BATCH = 65536          # BKT_MAX_BATCH
 PRECISIONS = ("fp32", "bf16")
@@ -57,6 +58,7 @@ MOVE_NONE = -2             # BKT_MOVE_NONE: bkt_playout_step leaves the row alon
 MAX_PLAYOUT_PLIES = 1024   # BKT_MAX_PLAYOUT_PLIES
 PATTERN_ENTRIES = 131072   # BKT_PATTERN_ENTRIES
 TACTIC_ENTRIES = 64        # BKT_TACTIC_ENTRIES
+MAX_SAMPLE_ROWS = 1 << 24  # BKT_MAX_SAMPLE_ROWS
 
 _lib = None
 
@@ -420,3 +422,29 @@ def tactical_codes(pos):
     _check(load().bkt_tactical_codes(_dev(pos, "pos", dtype=torch.uint8), B, _dev(codes, "codes", dtype=torch.int32),
                                      _stream(pos)), "bkt_tactical_codes")
     return codes
+
+
+def amaf_counts(moves, won, records, playouts):
+    """The all-moves-as-first counts of whole playouts (bkt_amaf_counts): moves int16 [records * playouts, max_plies], the
+    history random_playouts / pattern_playouts / tactical_playouts write, rows r * playouts .. of record r; won uint8
+    [records * playouts], non-zero where the side to move at the record won the row's playout.
+    -> (played int32 [records, 81], won_at int32 [records, 81]): the rows in which the side to move was the first to play
+    the point, and those of them it won."""
+    records, playouts = int(records), int(playouts)
+    if records < 1 or playouts < 1 or records * playouts > MAX_SAMPLE_ROWS:
+        raise ValueError(f"records and playouts must be at least 1 and records * playouts at most {MAX_SAMPLE_ROWS}, "
+                         f"got {records} x {playouts}")
+    if not isinstance(moves, torch.Tensor) or moves.dim() != 2 or moves.shape[0] != records * playouts:
+        raise ValueError(f"moves must be [{records * playouts}, max_plies]")
+    max_plies = int(moves.shape[1])
+    if not 1 <= max_plies <= MAX_PLAYOUT_PLIES:
+        raise ValueError(f"max_plies must be 1..{MAX_PLAYOUT_PLIES}, got {max_plies}")
+    played = torch.empty((records, 81), dtype=torch.int32, device=moves.device)
+    won_at = torch.empty((records, 81), dtype=torch.int32, device=moves.device)
+    if isinstance(won, torch.Tensor) and won.device != moves.device:
+        raise ValueError("won must be on the device of moves")
+    _check(load().bkt_amaf_counts(_dev(moves, "moves", dtype=torch.int16), max_plies,
+                                  _dev(won, "won", (records * playouts,), torch.uint8), records, playouts,
+                                  _dev(played, "played", dtype=torch.int32), _dev(won_at, "won_at", dtype=torch.int32),
+                                  _stream(moves)), "bkt_amaf_counts")
+    return played, won_at

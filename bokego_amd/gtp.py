@@ -468,6 +468,9 @@ def build_parser():
     ap.add_argument("--playout-tactics", default=None, metavar="FILE",
                     help="with --playout-value: multiply the playouts' weights by the tactical weights of this table "
                          "(python -m bokego_amd.tactics fit)")
+    ap.add_argument("--playout-prior", type=float, default=0.0, metavar="LAMBDA",
+                    help="with --playout-value: that share (0..1) of the priors comes from the playouts' AMAF counts; with 1 "
+                         "no policy net is loaded")
     ap.add_argument("--python-tree", action="store_true", help="search with the Python tree instead of the native one")
     ap.set_defaults(v_given=False)
     return ap
@@ -497,6 +500,10 @@ def parse_args(argv=None):
         ap.error("--playout-patterns weights the playouts of --playout-value: it needs --playout-value N")
     if args.playout_tactics is not None and not args.playout_value:
         ap.error("--playout-tactics weights the playouts of --playout-value: it needs --playout-value N")
+    if not 0.0 <= args.playout_prior <= 1.0:
+        ap.error("--playout-prior must be within 0..1")
+    if args.playout_prior and not args.playout_value:
+        ap.error("--playout-prior reads the playouts of --playout-value: it needs --playout-value N")
     return args
 
 
@@ -504,7 +511,12 @@ def main(argv=None):
     args = parse_args(argv)
 
     from . import nnet
-    pi = nnet.HipPolicyNet(load_state_dict(args.p), device_id=args.gpu, precision=args.precision)
+    pi = None
+    if args.playout_prior != 1.0:
+        pi = nnet.HipPolicyNet(load_state_dict(args.p), device_id=args.gpu, precision=args.precision)
+    else:
+        import torch
+        torch.cuda.set_device(args.gpu)
     val = None
     if not args.playout_value:
         val = nnet.HipValueNet(load_state_dict(args.v), device_id=args.gpu, precision=args.precision)
@@ -514,6 +526,8 @@ def main(argv=None):
         more["playout_patterns"] = args.playout_patterns
     if args.playout_tactics is not None:
         more["playout_tactics"] = args.playout_tactics
+    if args.playout_prior:
+        more["playout_prior"] = args.playout_prior
     gtp = cls(root, pi, val, no_sim=not args.simulate, time_lim=None if args.r else args.t, n_rollouts=args.r, pondering=args.ponder,
               rollout_score=args.rollout_score, **more)
     gtp.start()

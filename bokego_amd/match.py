@@ -235,6 +235,9 @@ def parse_args(argv=None):
                     help="with --playout-value: the table of 3x3 pattern weights its playouts draw their moves by")
     ap.add_argument("--playout-tactics", default=None, metavar="FILE",
                     help="with --playout-value: the table of tactical weights that multiply its playouts' weights")
+    ap.add_argument("--playout-prior", type=float, default=0.0, metavar="LAMBDA",
+                    help="with --playout-value: that share (0..1) of its priors comes from the playouts' AMAF counts; with 1 "
+                         "the engine loads no policy net")
     ap.add_argument("--opponent", default="policy", help='"policy" (raw policy, no search) or a GTP command line')
     ap.add_argument("--komi", type=float, default=5.5)
     ap.add_argument("--sgf", default=None, help="prefix for SGF records")
@@ -255,6 +258,10 @@ def parse_args(argv=None):
         ap.error("--playout-patterns weights the playouts of --playout-value: it needs --playout-value N")
     if args.playout_tactics is not None and not args.playout_value:
         ap.error("--playout-tactics weights the playouts of --playout-value: it needs --playout-value N")
+    if not 0.0 <= args.playout_prior <= 1.0:
+        ap.error("--playout-prior must be within 0..1")
+    if args.playout_prior and not args.playout_value:
+        ap.error("--playout-prior reads the playouts of --playout-value: it needs --playout-value N")
     return args
 
 
@@ -265,14 +272,19 @@ def main(argv=None):
         from . import nnet
         from .gtp import NativeGTP, load_state_dict
         from .mcts_native import Position
-        pi = nnet.HipPolicyNet(load_state_dict(args.p), precision=args.precision)
+        if args.opponent == "policy" or args.engine is not None or args.playout_prior != 1.0:
+            pi = nnet.HipPolicyNet(load_state_dict(args.p), precision=args.precision)
     if args.engine is None and args.playout_value > 0:
         more = {} if args.playout_patterns is None else {"playout_patterns": args.playout_patterns}
         if args.playout_tactics is not None:
             more["playout_tactics"] = args.playout_tactics
-        a = InProcessEngine(NativeGTP(Position(), pi, None, no_sim=True, time_lim=None, n_rollouts=args.r,
-                                      playout_value=args.playout_value, **more),
-                            name=args.engine_name or f"boke-hip-r{args.r}-mc{args.playout_value}" + ("-pat" if more else ""))
+        name = f"boke-hip-r{args.r}-mc{args.playout_value}" + ("-pat" if more else "")
+        if args.playout_prior:
+            more["playout_prior"] = args.playout_prior
+            name += f"-amaf{args.playout_prior:g}"
+        a = InProcessEngine(NativeGTP(Position(), None if args.playout_prior == 1.0 else pi, None, no_sim=True, time_lim=None,
+                                      n_rollouts=args.r, playout_value=args.playout_value, **more),
+                            name=args.engine_name or name)
     elif args.engine is None:
         val = nnet.HipValueNet(load_state_dict(args.v), precision=args.precision)
         a = InProcessEngine(NativeGTP(Position(), pi, val, no_sim=True, time_lim=None, n_rollouts=args.r),

@@ -134,10 +134,15 @@ class NativeMCTS:
     `evaluator` (anything with __call__(feats_u8, n_policy) -> (probs, values)) and `max_batch`; `playout_value=N` (with
     `playout_seed`, and `playout_rules="host"` for the host mirror where there is no GPU): rollout.PlayoutEvaluator;
     `playout_patterns=` (a patterns.PatternTable or the path of one, with playout_value): its pattern-weighted playouts;
-    `playout_tactics=` (a tactics.TacticTable or the path of one, with playout_value): its tactical weights."""
+    `playout_tactics=` (a tactics.TacticTable or the path of one, with playout_value): its tactical weights (DESIGN 18);
+    `playout_prior=` (0..1, with playout_value): that share of the priors comes from the playouts' AMAF counts, and with 1.0
+    policy_net may be None -- a search without any network."""
 
     def __init__(self, root=None, policy_net=None, value_net=None, **kwargs):
-        if policy_net is None and kwargs.get("evaluator") is None:
+        self.playout_prior = float(kwargs.get("playout_prior") or 0.0)   # 0: the priors are the policy net's alone
+        if self.playout_prior and not kwargs.get("playout_value"):
+            raise TypeError("playout_prior reads the playouts of playout_value=N: it needs playout_value")
+        if policy_net is None and kwargs.get("evaluator") is None and self.playout_prior != 1.0:
             raise TypeError("Missing required keywork argument: 'policy_net'")
         self.no_sim = kwargs.get("no_sim", True)
         # OPT-IN, not the reference's search: playout_value=N > 0 -- no value net; a leaf's value is the share of N uniformly
@@ -234,9 +239,11 @@ class NativeMCTS:
     def _playout_evaluator(self, policy_net):
         get = getattr(policy_net, "engine", None)
         if not callable(get):
-            raise RuntimeError(self.NO_HIP)
+            if policy_net is not None or self.playout_prior != 1.0:
+                raise RuntimeError(self.NO_HIP)
+            get = lambda: None                                           # noqa: E731  (no network: every prior from the playouts)
         from . import rollout
-        more = {}
+        more = {"prior": self.playout_prior} if self.playout_prior else {}
         if self.playout_patterns is not None:
             more["patterns"] = self.playout_patterns
         if self.playout_tactics is not None:
@@ -304,7 +311,7 @@ class NativeMCTS:
         """an unpickled tree gets its evaluator from the nets the caller has put back (mcts.py:106-108); called before anything
         is changed in the native tree, so that a tree without nets refuses the call and stays as it is"""
         if self.evaluator is None:
-            if self.policy_net is None:
+            if self.policy_net is None and getattr(self, "playout_prior", 0.0) != 1.0:
                 raise RuntimeError("this tree was unpickled without its networks: set tree.policy_net / tree.value_net first")
             self.evaluator = self._evaluator_from_nets()
 

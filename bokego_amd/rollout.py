@@ -36,6 +36,13 @@ tactics= (a tactics.TacticTable; --tactics FILE) multiplies those weights -- or,
 capture / escape / atari weight of each point's tactical code (bkt_tactical_playouts; bokego_amd/tactics.py):
 opt-in likewise, and with tactics=None the same launches run as before.
 
+playout_amaf keeps what those playouts otherwise throw away: beside the value, for every point the number of playouts in
+which the side to move was the first to play it and the number of those it won -- the all-moves-as-first (AMAF) counts,
+one bkt_amaf_counts reduction over the playouts' move history.  amaf_prior turns them into a search prior, and
+PlayoutEvaluator(prior=1.0) into an engine that searches with no network at all.
+
+    python -m bokego_amd.rollout --sgf FILE [--move K] --random --amaf [-n 256]   # the value and the heaviest prior moves
+
 rules="host" is one loop (_playout_host) on the host rules with the same draws (lockstep's play_host, features_batch
 and area_score_host, bk_pos_is_legal, bk_pos_possible_eye, lockstep.sample_host in float64): the reference the tests
 compare the device with.  With engine=None it needs no GPU.
@@ -58,9 +65,9 @@ MOVE_NONE = -2             # BKT_MOVE_NONE; in the history: the game was over be
 SEKI_THRESHOLD = 0.5       # |mean ownership| of a stone's point below this: the stone is in seki (rollout_score)
 POS_BYTES = L.POS_BYTES
 
-__all__ = ["MAX_PLIES", "MOVE_NONE", "Finished", "PlayoutEvaluator", "RolloutScore", "default_counters", "finish_games",
-           "format_score", "owner_board", "owner_host", "playable_host", "playout_value", "random_playouts", "record_turns",
-           "rollout_score", "sgf_position"]
+__all__ = ["MAX_PLIES", "MOVE_NONE", "Amaf", "Finished", "PlayoutEvaluator", "RolloutScore", "amaf_counts_host", "amaf_prior",
+           "default_counters", "finish_games", "format_score", "owner_board", "owner_host", "playable_host", "playout_amaf",
+           "playout_value", "random_playouts", "record_turns", "rollout_score", "sgf_position"]
 
 
 class Finished:
@@ -422,13 +429,38 @@ def _check_playouts(n):
     return n
 
 
+def _playouts_won_device(recs, n, key, komi, max_plies, table, tactics, history):
+    """n playouts of each record of recs (a uint8 [R,192] tensor on the device) -> (won bool [R,n]: the side to move at the
+    record won the playout, moves int16 [R * n, max_plies] or None without history), on the device."""
+    pos = recs.repeat_interleave(n, 0)                                     # a copy: the caller's records stay
+    moves = _play_random_device(pos, key, L.value_counters_device(recs, n), max_plies, history, table, tactics)[2]
+    black_wins = _area_score_device(pos, komi, False).view(len(recs), n) > 0
+    return black_wins == L.black_to_move(recs)[:, None], moves
+
+
+def _value_of_wins(w, n):
+    """(2 w - n) / n as the host mirror's float32, on the device.  The device's float32 division is not correctly rounded
+    (3 / 7 comes out one ulp high), its float64 division is; and rounding twice changes nothing below n = 2^29: a quotient
+    of |x| <= 1 that is no float32 midpoint m lies at least |m| / (2^24 n) from it, beyond half a float64 ulp.  When n is a
+    power of two both divisions are exact."""
+    return ((2 * w - n).to(torch.float64) / n).to(torch.float32)
+
+
 def _playout_value_device(recs, n, key, komi, max_plies=MAX_PLIES, table=None, tactics=None):
     """recs: a uint8 [R,192] tensor on the device -> float32 [R] on the device; nothing here waits for the device."""
-    pos = recs.repeat_interleave(n, 0)                                     # a copy: the caller's records stay
-    _play_random_device(pos, key, L.value_counters_device(recs, n), max_plies, False, table, tactics)
-    black_wins = _area_score_device(pos, komi, False).view(len(recs), n) > 0
-    w = (black_wins == L.black_to_move(recs)[:, None]).sum(1)
-    return (2 * w - n).to(torch.float32) / n
+    won, _ = _playouts_won_device(recs, n, key, komi, max_plies, table, tactics, False)
+    return _value_of_wins(won.sum(1), n)
+
+
+def _playout_amaf_device(recs, n, key, komi, counted=None, max_plies=MAX_PLIES, table=None, tactics=None):
+    """_playout_value_device's games with their history, and one bkt_amaf_counts over the rows of the first `counted`
+    records (default: all) -> (value float32 [R], wins int64 [R], played int32 [counted,81], won int32 [counted,81]) on the
+    device; nothing here waits for it."""
+    counted = len(recs) if counted is None else counted
+    won, moves = _playouts_won_device(recs, n, key, komi, max_plies, table, tactics, True)
+    w = won.sum(1)
+    played, won_at = T.amaf_counts(moves[:counted * n], won[:counted].to(torch.uint8).reshape(-1), counted, n)
+    return _value_of_wins(w, n), w, played, won_at
 
 
 def playout_value(recs, n, seed, rules="device", komi=L.KOMI, device=None, patterns=None, tactics=None):
@@ -444,10 +476,109 @@ def playout_value(recs, n, seed, rules="device", komi=L.KOMI, device=None, patte
     if rules == "device":
         t = L.records_to_device(recs, _device(device, None, recs), clone=False)
         return _playout_value_device(t, n, key, komi, table=table, tactics=tactics).cpu().numpy()
+    return _playout_host_wins(recs, n, key, komi, table, tactics, False)[0]
+
+
+def _playout_host_wins(recs, n, key, komi, table, tactics, history):
+    """playout_value on the host mirror -> (value float32 [R], won bool [R,n], moves int16 [R * n, L] or None)."""
     recs = np.array(_numpy(recs), np.uint8, order="C")
-    fin = _random_host(np.repeat(recs, n, 0), key, value_counters(recs, n), MAX_PLIES, komi, False, table, tactics)
+    fin = _random_host(np.repeat(recs, n, 0), key, value_counters(recs, n), MAX_PLIES, komi, history, table, tactics)
     w = (fin.score.reshape(len(recs), n) > 0) == L.black_to_move(recs)[:, None]
-    return ((2 * w.sum(1) - n).astype(np.float32) / np.float32(n)).astype(np.float32)
+    return ((2 * w.sum(1) - n).astype(np.float32) / np.float32(n)).astype(np.float32), w, fin.moves
+
+
+class Amaf:
+    """What playout_amaf returns, rows in the order of the records (numpy).
+
+    value   float32 [R]     playout_value's value, bit for bit
+    wins    int32 [R]       the playouts the side to move won: the w of (2 w - n) / n
+    played  int32 [R,81]    the playouts in which the side to move was the first to play the point
+    won     int32 [R,81]    those of them it won
+    n       int             the playouts per record
+    """
+
+    def __init__(self, value, wins, played, won, n):
+        self.value, self.wins, self.played, self.won, self.n = value, wins, played, won, int(n)
+
+
+def amaf_counts_host(moves, won, records, playouts):
+    """bkt_amaf_counts in numpy: moves int16 [records * playouts, max_plies] (a point 0..80, -1 = pass, <= MOVE_NONE ends the
+    row, anything above 80 is ignored), won [records * playouts] (non-zero: the side to move at the record won the row's
+    playout) -> (played, won_at) int32 [records, 81].  A row counts for the point s when the smallest ply k with
+    moves[row, k] == s is even -- the side to move at the record plays the even plies: played += 1, won_at += the row's won."""
+    records, playouts = int(records), int(playouts)
+    moves, won = np.asarray(moves), np.asarray(won).reshape(-1) != 0
+    if records < 1 or playouts < 1 or moves.ndim != 2 or len(moves) != records * playouts or len(won) != len(moves):
+        raise ValueError(f"moves must be [{records} * {playouts}, max_plies] and won [{records} * {playouts}]")
+    G, P = moves.shape
+    use = (np.cumsum(moves <= MOVE_NONE, 1) == 0) & (moves >= 0) & (moves <= 80)
+    row, ply = np.nonzero(use)
+    first = np.full((G, 81), P, np.int64)                                  # P: never played
+    np.minimum.at(first, (row, moves[row, ply].astype(np.int64)), ply)
+    counts = (first < P) & (first % 2 == 0)
+    played = counts.reshape(records, playouts, 81).sum(1)
+    won_at = (counts & won[:, None]).reshape(records, playouts, 81).sum(1)
+    return played.astype(np.int32), won_at.astype(np.int32)
+
+
+def playout_amaf(recs, n, seed, rules="device", komi=L.KOMI, device=None, patterns=None, tactics=None):
+    """playout_value's n playouts of each record with what else they tell -> Amaf: the value (the history does not enter a
+    game: the same bits), the wins, and the all-moves-as-first counts of every point (amaf_counts_host has the definition).
+    rules="device": the playout launches with their history, `won` built in torch, one bkt_amaf_counts; rules="host": the
+    mirror end to end, the same integers.  recs, patterns, tactics: as playout_value."""
+    L.check_rules(rules)
+    table, tactics = _table(patterns), _tactics(tactics)
+    n = _check_playouts(n)
+    _check_records(recs)
+    key = L.seed_u64(seed)
+    if rules == "device":
+        t = L.records_to_device(recs, _device(device, None, recs), clone=False)
+        value, w, played, won_at = _playout_amaf_device(t, n, key, komi, table=table, tactics=tactics)
+        return Amaf(value.cpu().numpy(), w.cpu().numpy().astype(np.int32), played.cpu().numpy(), won_at.cpu().numpy(), n)
+    value, w, moves = _playout_host_wins(recs, n, key, komi, table, tactics, True)
+    played, won_at = amaf_counts_host(moves, w.reshape(-1), len(w), n)
+    return Amaf(value, w.sum(1).astype(np.int32), played, won_at, n)
+
+
+PRIOR_K = 4.0              # amaf_prior's defaults: plausible, and not tuned (DESIGN 19)
+PRIOR_TEMPERATURE = 0.1
+
+
+def legal_host(recs):
+    """bool [n,81]: bk_pos_legal_moves of every record."""
+    lib = go.golib()
+    out = np.zeros((len(recs), 81), bool)
+    buf = (ctypes.c_uint8 * 81)()
+    for i in range(len(recs)):
+        lib.bk_pos_legal_moves(L.pos_ptr(recs[i]), buf)
+        out[i] = np.frombuffer(buf, np.uint8) != 0
+    return out
+
+
+def amaf_prior(recs, amaf, k=PRIOR_K, temperature=PRIOR_TEMPERATURE):
+    """A search prior from the counts of playout_amaf(recs, ...) -> float32 [R,81], computed on the host in float64 from the
+    integers, so that device and host playouts give the same floats.  With wbar = wins / n, the win rate of all n playouts,
+        q_s = (won_s + k * wbar) / (played_s + k)      the AMAF win rate of the point, k playouts' worth of wbar mixed in,
+        p_s = exp((q_s - max q over the legal points) / temperature) on the legal points (bk_pos_legal_moves), 0 elsewhere,
+    each row divided by its sum; a record without a legal point gets 1/81 everywhere.  k and temperature must be > 0; their
+    defaults, 4.0 and 0.1, are plausible and untuned."""
+    k, temperature = float(k), float(temperature)
+    if not k > 0 or not temperature > 0:
+        raise ValueError("k and temperature must be greater than 0")
+    recs = np.array(_numpy(recs), np.uint8, order="C")
+    _check_records(recs)
+    played, won = np.asarray(amaf.played, np.float64), np.asarray(amaf.won, np.float64)
+    if played.shape != (len(recs), 81) or won.shape != played.shape:
+        raise ValueError(f"the counts must be [{len(recs)}, 81], one row per record")
+    wbar = np.asarray(amaf.wins, np.float64) / float(amaf.n)
+    q = (won + k * wbar[:, None]) / (played + k)
+    legal = legal_host(recs)
+    top = np.where(legal, q, -np.inf).max(1, keepdims=True)
+    some = legal.any(1)
+    top[~some] = 0.0
+    p = np.where(legal, np.exp((q - top) / temperature), 0.0)
+    p[~some] = 1.0
+    return (p / p.sum(1, keepdims=True)).astype(np.float32)
 
 
 class PlayoutEvaluator:
@@ -456,14 +587,28 @@ class PlayoutEvaluator:
     selfplay.EngineEvaluator(value=False) asks), the values of all its rows from playout_value(playouts, seed).  The
     engine's request and the playout launch do not depend on each other and are in flight together between submit and
     finish.  rules="host": the values from the host mirror (the same bits; for tests).
+    prior (0..1, default 0: exactly the above) mixes the priors with what the request's own playouts say about the moves:
+    the playouts then run with their history (playout_amaf), the counts of the first n_policy rows give amaf_prior(k=prior_k,
+    temperature=prior_temperature), and the priors handed on are (1 - prior) * the engine's + prior * amaf_prior, mixed in
+    float64, cast to float32 and normalised as before.  With prior=1 the engine is never asked and may be None: a search
+    without any network.
     The engine is kept as `policy_engine`, not `engine`: selfplay.run_pools_native hands an evaluator's `engine` to the C
     step loop as its own bk_evaluator, which would compute no playouts -- this class goes through callback_evaluator."""
     wants_positions = True
 
-    def __init__(self, engine, playouts=64, seed=0, rules="device", komi=L.KOMI, patterns=None, tactics=None):
+    def __init__(self, engine, playouts=64, seed=0, rules="device", komi=L.KOMI, patterns=None, tactics=None, prior=0.0,
+                 prior_k=PRIOR_K, prior_temperature=PRIOR_TEMPERATURE):
         L.check_rules(rules)
         self.patterns = _table(patterns)                                  # None: uniformly random playouts
         self.tactics = _tactics(tactics)                                  # None: no tactical weights (DESIGN 18)
+        self.prior = float(prior)
+        if not 0.0 <= self.prior <= 1.0:
+            raise ValueError("prior must be within 0..1")
+        self.prior_k, self.prior_temperature = float(prior_k), float(prior_temperature)
+        if not self.prior_k > 0 or not self.prior_temperature > 0:
+            raise ValueError("prior_k and prior_temperature must be greater than 0")
+        if engine is None and self.prior < 1.0:
+            raise TypeError("engine=None goes with prior=1.0 only: below it the priors need a policy engine")
         self.policy_engine = engine
         self.playouts = _check_playouts(playouts)
         self.seed = L.seed_u64(seed)
@@ -477,26 +622,39 @@ class PlayoutEvaluator:
         self.positions += len(recs)
         self.batches += 1
         ticket = None
-        if n_policy:
+        if n_policy and self.prior < 1.0:
             ticket = self.policy_engine.submit_positions(recs[:n_policy], logits=False, probs=True, value=False,
                                                          n_policy=n_policy)
+        more = dict(komi=self.komi, table=self.patterns, tactics=self.tactics)
+        if n_policy and self.prior > 0.0:                                 # the playouts with their history, and the counts
+            if self.rules == "host":
+                values, w, moves = _playout_host_wins(recs, self.playouts, self.seed, history=True, **more)
+                counts = amaf_counts_host(moves[:n_policy * self.playouts], w[:n_policy].reshape(-1), n_policy, self.playouts)
+                w = w.sum(1)
+            else:
+                t = torch.from_numpy(recs).to(_device(None, self.policy_engine))
+                values, w, *counts = _playout_amaf_device(t, self.playouts, self.seed, counted=n_policy, **more)
+            return ticket, values, (recs[:n_policy], w[:n_policy], *counts)
         if self.rules == "host":
-            values = playout_value(recs, self.playouts, self.seed, rules="host", komi=self.komi, patterns=self.patterns,
-                                   tactics=self.tactics)
+            values = _playout_host_wins(recs, self.playouts, self.seed, history=False, **more)[0]
         else:
-            dev = _device(None, self.policy_engine)
-            values = _playout_value_device(torch.from_numpy(recs).to(dev), self.playouts, self.seed, self.komi,
-                                           table=self.patterns, tactics=self.tactics)
-        return ticket, values
+            values = _playout_value_device(torch.from_numpy(recs).to(_device(None, self.policy_engine)), self.playouts,
+                                           self.seed, **more)
+        return ticket, values, None
 
     def finish(self, handle, normalise=None):
-        ticket, values = handle
-        if ticket is None:
-            probs = np.zeros((0, 81), np.float32)
-        else:
-            if normalise is None:
-                from .selfplay import normalise_like_categorical as normalise
-            probs = normalise(self.policy_engine.wait(ticket)["probs"])
+        ticket, values, counted = handle
+        if normalise is None:
+            from .selfplay import normalise_like_categorical as normalise
+        probs = np.zeros((0, 81), np.float32) if ticket is None else self.policy_engine.wait(ticket)["probs"]
+        if counted is not None:
+            recs, w, played, won = (_numpy(x) for x in counted)
+            prior = amaf_prior(recs, Amaf(None, w, played, won, self.playouts), self.prior_k, self.prior_temperature)
+            if ticket is not None:
+                prior = ((1.0 - self.prior) * probs.astype(np.float64) + self.prior * prior.astype(np.float64))
+            probs = prior.astype(np.float32)
+        if len(probs):
+            probs = normalise(probs)
         return probs, (values if isinstance(values, np.ndarray) else values.cpu().numpy())
 
     def __call__(self, recs, n_policy):
@@ -599,11 +757,15 @@ def _parse(argv):
                     help="with --random: draw the moves by the 3x3 pattern weights of this table (python -m bokego_amd.patterns fit)")
     ap.add_argument("--tactics", default=None, metavar="FILE",
                     help="with --random: multiply the weights by the tactical weights of this table (python -m bokego_amd.tactics fit)")
+    ap.add_argument("--amaf", action="store_true",
+                    help="with --random: print the Monte-Carlo value and the ten heaviest moves of the AMAF prior instead of the score")
     ap.add_argument("-n", dest="n", type=int, default=256, help="playouts")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--komi", type=float, default=L.KOMI)
     ap.add_argument("--device", type=int, default=0)
     args = ap.parse_args(argv)
+    if args.amaf and not args.random:
+        ap.error("--amaf reads the one-launch playouts: it needs --random")
     if args.n < 1:
         ap.error("-n must be at least 1")
     if args.random and args.p is not None:
@@ -635,6 +797,15 @@ def main(argv=None):
     args = _parse(argv)
     game = sgf_position(args.sgf, args.move)
     torch.cuda.set_device(args.device)
+    if args.amaf:
+        recs = _as_records(game)
+        a = playout_amaf(recs, args.n, args.seed, komi=args.komi, device=torch.device("cuda", args.device),
+                         patterns=args.patterns, tactics=args.tactics)
+        prior = amaf_prior(recs, a)[0]
+        print(json.dumps({"value": float(a.value[0]), "wins": int(a.wins[0]), "playouts": args.n,
+                          "prior": [{"move": go.unsquash(s), "prior": float(prior[s]), "played": int(a.played[0, s]),
+                                     "won": int(a.won[0, s])} for s in np.argsort(-prior, kind="stable")[:10].tolist()]}))
+        return
     eng = None
     if args.p is not None:
         from .reinforce import policy_engine

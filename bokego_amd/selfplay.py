@@ -812,7 +812,7 @@ def write_records(out_dir, games, visits=None, komi=5.5):
         json.dump(rec, f)
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser(description="MCTS self-play generation on the HIP engine")
     ap.add_argument("--games", type=int, default=512)
     ap.add_argument("--rollouts", type=int, default=400)
@@ -830,7 +830,36 @@ def main():
     ap.add_argument("--task-cap", type=int, default=None, help="soft limit of a batch in network tasks (default: whole rounds of workgroups for fp32, none for f16x2; 0: none)")
     ap.add_argument("--replay-shard", metavar="RANK/WORLD", default=None,
                     help="re-play the games a failed rank owned (e.g. 3/8: the gids with gid %% 8 == 3) in this process")
-    args = ap.parse_args()
+    ap.add_argument("--playout-value", type=int, default=0, metavar="N",
+                    help="N > 0: no value net is loaded -- a leaf's value is the share of N random playouts its side to move wins "
+                         "(rollout.PlayoutEvaluator; not with --value or --host-encode)")
+    ap.add_argument("--playout-prior", type=float, default=0.0, metavar="LAMBDA",
+                    help="with --playout-value: that share (0..1) of the priors comes from the playouts' AMAF counts; with 1 no "
+                         "policy net is loaded either (not with --policy): self-play from no network at all")
+    ap.add_argument("--playout-patterns", default=None, metavar="FILE",
+                    help="with --playout-value: the table of 3x3 pattern weights its playouts draw their moves by")
+    ap.add_argument("--playout-tactics", default=None, metavar="FILE",
+                    help="with --playout-value: the table of tactical weights that multiply its playouts' weights")
+    args = ap.parse_args(argv)
+    if args.playout_value < 0:
+        ap.error("--playout-value must not be negative")
+    if args.playout_value:
+        for flag, on in (("--value", args.value is not None), ("--host-encode", args.host_encode)):
+            if on:
+                ap.error(f"--playout-value takes the place of a value net on position records: not allowed with {flag}")
+    if not 0.0 <= args.playout_prior <= 1.0:
+        ap.error("--playout-prior must be within 0..1")
+    for flag, given in (("--playout-prior", args.playout_prior), ("--playout-patterns", args.playout_patterns is not None),
+                        ("--playout-tactics", args.playout_tactics is not None)):
+        if given and not args.playout_value:
+            ap.error(f"{flag} goes with the playouts of --playout-value: it needs --playout-value N")
+    if args.playout_prior == 1.0 and args.policy is not None:
+        ap.error("--playout-prior 1 searches without a policy net: not allowed with --policy")
+    return args
+
+
+def main(argv=None):
+    args = parse_args(argv)
 
     import torch
     from .bkw import load_bkw
@@ -860,9 +889,18 @@ def main():
         ck = torch.load(path, map_location="cpu")
         return ck.get("model_state_dict", ck)
 
-    eng = LeafEngine(load(args.policy, "policy_19.bkw"), load(args.value, "value_synth.bkw"), device_id=local_rank,
-                     max_batch=args.max_batch, precision=args.precision)
-    ev = EngineEvaluator(eng, gpu_encode=not args.host_encode)
+    if args.playout_value:
+        from .rollout import PlayoutEvaluator
+        eng = None
+        if args.playout_prior != 1.0:
+            eng = LeafEngine(load(args.policy, "policy_19.bkw"), None, device_id=local_rank, max_batch=args.max_batch,
+                             precision=args.precision)
+        ev = PlayoutEvaluator(eng, args.playout_value, patterns=args.playout_patterns, tactics=args.playout_tactics,
+                              prior=args.playout_prior)
+    else:
+        eng = LeafEngine(load(args.policy, "policy_19.bkw"), load(args.value, "value_synth.bkw"), device_id=local_rank,
+                         max_batch=args.max_batch, precision=args.precision)
+        ev = EngineEvaluator(eng, gpu_encode=not args.host_encode)
     gids = None
     if args.replay_shard:
         r, w = (int(v) for v in args.replay_shard.split("/"))
@@ -888,7 +926,8 @@ def main():
                           "first_move_hist": total["first_move_hist"]}))
     if args.out:
         write_records(os.path.join(args.out, f"rank{rank}"), local["games"], local["visits"])
-    eng.close()
+    if eng is not None:
+        eng.close()
     if world > 1:
         dist.destroy_process_group()
 

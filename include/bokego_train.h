@@ -263,6 +263,21 @@ int bkt_tactical_playouts(void *pos, int batch, uint64_t seed, const uint32_t *c
                           const uint16_t *tactics, int max_plies, uint8_t *over, int32_t *plies, int16_t *moves,
                           int32_t *status, void *stream);
 
+/* The all-moves-as-first (AMAF) counts of whole playouts (bokego_amd/rollout.py playout_amaf), read from the
+ * history the three bkt_*_playouts calls write.  moves [records * playouts, max_plies] int16: a point 0..80, BK_PASS, or
+ * BKT_MOVE_NONE from the ply at which the row was over; rows r * playouts .. (r + 1) * playouts - 1 belong to record r.
+ * won[row] != 0: the side to move at the record won that playout.  Ply 0 is that side's, so it plays the even plies.
+ * For a row and a point s let k be the smallest ply with moves[row, k] == s, looking no further than the first entry
+ * <= BKT_MOVE_NONE, which ends the row.  If k exists and is even, the row counts for s:
+ *   played[r * 81 + s] += 1,  won_at[r * 81 + s] += (won[row] != 0).
+ * A point the opponent played first does not count for the row, whatever is played there later; passes are skipped; an
+ * entry above 80 is ignored (entries are compared, never used as an index).  Every entry of played and won_at
+ * [records, 81] is written, zeros included.  Integers only: the counts do not depend on any order.
+ * moves, won, played and won_at must not be NULL; records >= 1, playouts >= 1, records * playouts <= BKT_MAX_SAMPLE_ROWS,
+ * 1 <= max_plies <= BKT_MAX_PLAYOUT_PLIES; else BKT_ERR_ARG and nothing is launched. */
+int bkt_amaf_counts(const int16_t *moves, int max_plies, const uint8_t *won, int records, int playouts, int32_t *played,
+                    int32_t *won_at, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
