@@ -50,6 +50,7 @@ SYMBOLS = {
     "bkt_tactical_codes": (_I, [_P, _I, _P, _P]),
     "bkt_tactical_playouts": (_I, [_P, _I, _U64, _P, _P, _P, _I, _P, _P, _P, _P, _P]),
     "bkt_amaf_counts": (_I, [_P, _I, _P, _I, _I, _P, _P, _P]),
+    "bkt_amaf_counts_sides": (_I, [_P, _I, _P, _I, _I, _P, _P, _P]),
 }
 MAX_BATCH = 65536          # BKT_MAX_BATCH
 PRECISIONS = ("fp32", "bf16")
@@ -424,12 +425,8 @@ def tactical_codes(pos):
     return codes
 
 
-def amaf_counts(moves, won, records, playouts):
-    """The all-moves-as-first counts of whole playouts (bkt_amaf_counts): moves int16 [records * playouts, max_plies], the
-    history random_playouts / pattern_playouts / tactical_playouts write, rows r * playouts .. of record r; won uint8
-    [records * playouts], non-zero where the side to move at the record won the row's playout.
-    -> (played int32 [records, 81], won_at int32 [records, 81]): the rows in which the side to move was the first to play
-    the point, and those of them it won."""
+def _amaf_args(moves, won, records, playouts):
+    """The checks amaf_counts and amaf_counts_sides share -> (records, playouts, max_plies)."""
     records, playouts = int(records), int(playouts)
     if records < 1 or playouts < 1 or records * playouts > MAX_SAMPLE_ROWS:
         raise ValueError(f"records and playouts must be at least 1 and records * playouts at most {MAX_SAMPLE_ROWS}, "
@@ -439,12 +436,37 @@ def amaf_counts(moves, won, records, playouts):
     max_plies = int(moves.shape[1])
     if not 1 <= max_plies <= MAX_PLAYOUT_PLIES:
         raise ValueError(f"max_plies must be 1..{MAX_PLAYOUT_PLIES}, got {max_plies}")
-    played = torch.empty((records, 81), dtype=torch.int32, device=moves.device)
-    won_at = torch.empty((records, 81), dtype=torch.int32, device=moves.device)
     if isinstance(won, torch.Tensor) and won.device != moves.device:
         raise ValueError("won must be on the device of moves")
+    return records, playouts, max_plies
+
+
+def amaf_counts(moves, won, records, playouts):
+    """The all-moves-as-first counts of whole playouts (bkt_amaf_counts): moves int16 [records * playouts, max_plies], the
+    history random_playouts / pattern_playouts / tactical_playouts write, rows r * playouts .. of record r; won uint8
+    [records * playouts], non-zero where the side to move at the record won the row's playout.
+    -> (played int32 [records, 81], won_at int32 [records, 81]): the rows in which the side to move was the first to play
+    the point, and those of them it won."""
+    records, playouts, max_plies = _amaf_args(moves, won, records, playouts)
+    played = torch.empty((records, 81), dtype=torch.int32, device=moves.device)
+    won_at = torch.empty((records, 81), dtype=torch.int32, device=moves.device)
     _check(load().bkt_amaf_counts(_dev(moves, "moves", dtype=torch.int16), max_plies,
                                   _dev(won, "won", (records * playouts,), torch.uint8), records, playouts,
                                   _dev(played, "played", dtype=torch.int32), _dev(won_at, "won_at", dtype=torch.int32),
                                   _stream(moves)), "bkt_amaf_counts")
+    return played, won_at
+
+
+def amaf_counts_sides(moves, won, records, playouts):
+    """amaf_counts for both sides of every history (bkt_amaf_counts_sides): the same moves and won
+    -> (played int32 [records, 2, 81], won_at int32 [records, 2, 81]): side 0 is the side to move at the record -- its rows
+    are amaf_counts' output -- and side 1 its opponent: the rows in which that side was the first to play the point, and
+    those of them it won (the opponent wins a row whose won is 0)."""
+    records, playouts, max_plies = _amaf_args(moves, won, records, playouts)
+    played = torch.empty((records, 2, 81), dtype=torch.int32, device=moves.device)
+    won_at = torch.empty((records, 2, 81), dtype=torch.int32, device=moves.device)
+    _check(load().bkt_amaf_counts_sides(_dev(moves, "moves", dtype=torch.int16), max_plies,
+                                        _dev(won, "won", (records * playouts,), torch.uint8), records, playouts,
+                                        _dev(played, "played", dtype=torch.int32), _dev(won_at, "won_at", dtype=torch.int32),
+                                        _stream(moves)), "bkt_amaf_counts_sides")
     return played, won_at

@@ -133,6 +133,24 @@ struct Game {
     bool analyze = false;
     std::unordered_map<int, std::vector<int>> variations;
 
+    // ---- RAVE (bk_pool_set_rave, opt-in) -------------------------------------------------------------------------
+    // rave_k > 0: a value may arrive with the AMAF record of the playouts behind it (bk_pool_deliver_rave), and every rollout
+    // that ends on a node with a record adds it -- and the moves of its own path -- to the RAVE tables of the nodes it
+    // passed (rave_backup), which select_rave() blends into the children's means.  Everything lives beside the node arrays,
+    // so that TNode, the off path and the snapshots of a tree without RAVE stay what they were.
+    static constexpr int kRaveRec = 2 + 4 * 81;   // a record: playouts n, wins w, played[2][81], won_at[2][81]
+    static constexpr int kRaveTab = 2 * 81;       // a table: rn[81], rw[81]
+    double rave_k = 0.0;
+    std::vector<int32_t> rv_tab_of, rv_rec_of;    // per node: offset of its table in rv_tabs / of its record in rv_recs, -1 =
+                                                  // none; grown on demand, a node beyond their end has neither
+    std::vector<int64_t> rv_tabs, sc_tabs;
+    std::vector<int32_t> rv_recs, sc_recs, sc_tab_of, sc_rec_of;
+    int rave_tab(int id) const { return (size_t)id < rv_tab_of.size() ? rv_tab_of[(size_t)id] : -1; }
+    int rave_rec(int id) const { return (size_t)id < rv_rec_of.size() ? rv_rec_of[(size_t)id] : -1; }
+    void rave_clear() {
+        rv_tab_of.clear(); rv_rec_of.clear(); rv_tabs.clear(); rv_recs.clear();
+    }
+
     Game(const bk_search_params& p, uint64_t seed) : prm(p), rng(seed) {}
 
     static uint64_t key_hash(const bk_pos& p) { return p.hash ^ (0x9E3779B97F4A7C15ull * (uint64_t)(uint16_t)p.last_move); }
@@ -310,7 +328,40 @@ struct Game {
         }
     }
 
+    // select() at a node with a RAVE table: a child whose move m has a = rn[m] > 0 AMAF playouts is scored by
+    //   (1 - beta) * (-avg) + beta * (2 rw[m] / a - 1) + c * prior[m] * sqrt(total) / (1 + N),  beta = a / (a + N + a N / k),
+    // k = rave_k in visits (N counts visits, a counts playouts); a child without AMAF playouts by select()'s own expression.
+    int select_rave(int id, const int64_t* rn) const {
+        const TNode& nd = nodes[id];
+        const int* kids = &kid_ids[nd.kids_off];
+        const int64_t* rw = rn + 81;
+        long total = 0;
+        for (int i = 0; i < nd.n_kids; ++i) total += nodes[kids[i]].N;
+        if (total == 0) total = 1;
+        const double sq = std::sqrt((double)total), c = prm.c_puct;
+        const double* prior = &priors[nd.prior_off];
+        int best = -1;
+        double best_s = 0;
+        for (int i = 0; i < nd.n_kids; ++i) {
+            const TNode& k = nodes[kids[i]];
+            const double e = c * prior[k.mv] * sq;
+            double s = k.N == 0 ? e : -k.avg + (e / (double)(1 + k.N));
+            const int64_t a = rn[k.mv];
+            if (a > 0) {
+                const double ad = (double)a, n = (double)k.N;
+                const double beta = ad / (ad + n + ad * n / rave_k);
+                s = ((1.0 - beta) * -k.avg + beta * (2.0 * (double)rw[k.mv] / ad - 1.0)) + (e / (double)(1 + k.N));
+            }
+            if (best < 0 || s > best_s) { best = kids[i]; best_s = s; }
+        }
+        return best;
+    }
+
     int select(int id) const {  // mcts.py:219-234
+        if (rave_k > 0.0) {                             // (off: one compare, then the instructions below as ever)
+            const int t = rave_tab(id);
+            if (t >= 0) return select_rave(id, &rv_tabs[(size_t)t]);
+        }
         const TNode& nd = nodes[id];
         const int* kids = &kid_ids[nd.kids_off];
         long total = 0;
@@ -511,6 +562,45 @@ struct Game {
             n.avg = n.V / (double)n.N;
             v = -v;
         }
+        if (rave_k > 0.0) rave_backup();
+    }
+
+    // The RAVE backup of one rollout (include/bokego_tree.h has the rule): the path p_0 .. p_L, m_j the move into
+    // p_j, and the leaf's record (n, w, played, won_at).  Node p_i, when it has priors, gets for its side (L - i) & 1 of the
+    // record -- side 0 moves at the leaf -- the path's own moves of that side (tree part: n playouts each, won w or n - w) and
+    // the record's counts of every point the path below p_i does not play (playout part): the first-play rule over tree path
+    // plus playout.  Integers only.
+    void rave_backup() {
+        const int L = (int)path.size() - 1;
+        const int ro = rave_rec(path[(size_t)L]);
+        if (ro < 0) return;                             // no record (a terminal node, a plain delivery): no table changes
+        if (rv_tab_of.size() < nodes.size()) rv_tab_of.resize(nodes.size(), -1);
+        const int32_t n = rv_recs[(size_t)ro], w = rv_recs[(size_t)ro + 1];
+        for (int i = 0; i <= L; ++i) {
+            if (!nodes[path[(size_t)i]].has_prior) continue;
+            int32_t& to = rv_tab_of[(size_t)path[(size_t)i]];
+            if (to < 0) {
+                to = (int32_t)rv_tabs.size();
+                rv_tabs.resize(rv_tabs.size() + kRaveTab, 0);
+            }
+            int64_t* rn = &rv_tabs[(size_t)to];
+            int64_t* rw = rn + 81;
+            const int side = (L - i) & 1;
+            const int32_t* played = &rv_recs[(size_t)ro + 2 + 81 * side];
+            const int32_t* won_at = played + 2 * 81;
+            bool in_path[81] = {false};                 // F: the board points among m_{i+1} .. m_L
+            for (int j = i + 1; j <= L; ++j) {
+                const int m = nodes[path[(size_t)j]].mv;
+                if (m < 0 || m >= 81 || in_path[m]) continue;
+                in_path[m] = true;
+                if ((j - i) & 1) {
+                    rn[m] += n;
+                    rw[m] += side == 0 ? w : n - w;
+                }
+            }
+            for (int s = 0; s < 81; ++s)
+                if (!in_path[s]) { rn[s] += played[s]; rw[s] += won_at[s]; }
+        }
     }
 
     void add_noise(int id) {  // mcts.py:366-369 with a per-game generator
@@ -593,6 +683,27 @@ struct Game {
             nn.push_back(n);
             npos.push_back(poses[old]);
             if (prm.simulate) nq.push_back(Qs[old]);
+        }
+        if (rave_k > 0.0) {                             // tables and records travel with the nodes that stay
+            sc_tab_of.assign(order.size(), -1);
+            sc_rec_of.assign(order.size(), -1);
+            sc_tabs.clear();
+            sc_recs.clear();
+            for (size_t i = 0; i < order.size(); ++i) {
+                const int t = rave_tab(order[i]), r = rave_rec(order[i]);
+                if (t >= 0) {
+                    sc_tab_of[i] = (int32_t)sc_tabs.size();
+                    sc_tabs.insert(sc_tabs.end(), rv_tabs.begin() + t, rv_tabs.begin() + t + kRaveTab);
+                }
+                if (r >= 0) {
+                    sc_rec_of[i] = (int32_t)sc_recs.size();
+                    sc_recs.insert(sc_recs.end(), rv_recs.begin() + r, rv_recs.begin() + r + kRaveRec);
+                }
+            }
+            rv_tab_of.swap(sc_tab_of);
+            rv_rec_of.swap(sc_rec_of);
+            rv_tabs.swap(sc_tabs);
+            rv_recs.swap(sc_recs);
         }
         Qs.swap(nq);
         nodes.swap(nn);       // the old arrays become next time's scratch
@@ -852,6 +963,19 @@ struct Game {
     void deliver_value(int id, float v) {
         TNode& n = nodes[id];
         if (!n.has_value) { n.value = v; n.has_value = 1; ++n_value_evals; }
+    }
+    // the value together with the AMAF record of the playouts it was made of: a node keeps the record that arrives with its
+    // value (the first delivery wins, as above); a terminal node keeps none
+    void deliver_value_rave(int id, float v, int32_t playouts, int32_t wins, const int32_t* played, const int32_t* won_at) {
+        const bool first = !nodes[id].has_value;
+        deliver_value(id, v);
+        if (!first || !(rave_k > 0.0) || nodes[id].terminal) return;
+        if (rv_rec_of.size() < nodes.size()) rv_rec_of.resize(nodes.size(), -1);
+        rv_rec_of[(size_t)id] = (int32_t)rv_recs.size();
+        rv_recs.push_back(playouts);
+        rv_recs.push_back(wins);
+        rv_recs.insert(rv_recs.end(), played, played + 2 * 81);
+        rv_recs.insert(rv_recs.end(), won_at, won_at + 2 * 81);
     }
 };
 
@@ -1436,7 +1560,17 @@ void bk_pool_phase_seconds(const bk_pool* p, double* out3) {   // advance, emit,
     out3[2] = p->t_deliver;
 }
 
-void bk_pool_deliver(bk_pool* p, const float* probs, const float* values) {
+}  // extern "C"
+
+namespace {
+struct RaveRows {   // the AMAF records of a delivery, one per row of `values` (bk_pool_deliver_rave); wins == nullptr: none
+    int32_t playouts = 0;
+    const int32_t* wins = nullptr;
+    const int32_t* played = nullptr;
+    const int32_t* won_at = nullptr;
+};
+
+void deliver_impl(bk_pool* p, const float* probs, const float* values, const RaveRows& rr) {
     const auto t0 = std::chrono::steady_clock::now();
     int npol = 0, nval = 0;
     for (size_t a = 0; a < p->active.size(); ++a) {
@@ -1447,14 +1581,18 @@ void bk_pool_deliver(bk_pool* p, const float* probs, const float* values) {
     const bool mapped = p->mapped;                                          // the batch was laid out by collect_dedup
     auto deliver_game = [&](int a) {
         Game& gm = p->games[p->active[a]];
+        auto value_row = [&](int id, int row) {
+            if (rr.wins) gm.deliver_value_rave(id, values[row], rr.playouts, rr.wins[row], rr.played + (size_t)row * 162, rr.won_at + (size_t)row * 162);
+            else gm.deliver_value(id, values[row]);
+        };
         if (mapped) {
             const std::vector<int>& rows = p->row_of[a];
             const size_t np_ = gm.req_policy.size();
             for (size_t i = 0; i < np_; ++i) {
                 gm.deliver_policy(gm.req_policy[i], probs + (size_t)rows[i] * 81);
-                if (values) gm.deliver_value(gm.req_policy[i], values[rows[i]]);
+                if (values) value_row(gm.req_policy[i], rows[i]);
             }
-            for (size_t i = 0; i < gm.req_value.size(); ++i) gm.deliver_value(gm.req_value[i], values[rows[np_ + i]]);
+            for (size_t i = 0; i < gm.req_value.size(); ++i) value_row(gm.req_value[i], rows[np_ + i]);
             gm.req_policy.clear();
             gm.req_value.clear();
             return;
@@ -1462,9 +1600,9 @@ void bk_pool_deliver(bk_pool* p, const float* probs, const float* values) {
         for (size_t i = 0; i < gm.req_policy.size(); ++i) {
             const int row = p->pol_off[a] + (int)i;
             gm.deliver_policy(gm.req_policy[i], probs + (size_t)row * 81);
-            if (values) gm.deliver_value(gm.req_policy[i], values[row]);
+            if (values) value_row(gm.req_policy[i], row);
         }
-        for (size_t i = 0; i < gm.req_value.size(); ++i) gm.deliver_value(gm.req_value[i], values[npol + p->val_off[a] + (int)i]);
+        for (size_t i = 0; i < gm.req_value.size(); ++i) value_row(gm.req_value[i], npol + p->val_off[a] + (int)i);
         gm.req_policy.clear();
         gm.req_value.clear();
     };
@@ -1475,6 +1613,42 @@ void bk_pool_deliver(bk_pool* p, const float* probs, const float* values) {
     p->active.clear();
     p->row_of.clear();
     p->t_deliver += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+}
+}  // namespace
+
+extern "C" {
+
+void bk_pool_deliver(bk_pool* p, const float* probs, const float* values) { deliver_impl(p, probs, values, RaveRows{}); }
+
+void bk_pool_deliver_rave(bk_pool* p, const float* probs, const float* values, int playouts, const int32_t* wins,
+                          const int32_t* played, const int32_t* won_at) {
+    RaveRows rr;
+    if (values && playouts > 0 && wins && played && won_at) {       // (anything less is a plain delivery)
+        rr.playouts = playouts; rr.wins = wins; rr.played = played; rr.won_at = won_at;
+    }
+    deliver_impl(p, probs, values, rr);
+}
+
+int bk_pool_set_rave(bk_pool* p, double equiv) {
+    if (!p || !(equiv >= 0.0) || !std::isfinite(equiv)) return -1;
+    for (const auto& g : p->games)                                   // RAVE lives in the fast branch of backprop() only
+        if (g.prm.leaves > 1 || g.prm.simulate || !g.prm.use_value || g.prm.value_weight != 1.0) return -1;
+    for (auto& g : p->games) {
+        g.rave_k = equiv;
+        if (equiv == 0.0) g.rave_clear();
+    }
+    return 0;
+}
+
+int bk_pool_node_rave(const bk_pool* p, int g, int id, int64_t* rn, int64_t* rw) {
+    if (!p || g < 0 || g >= (int)p->games.size() || !rn || !rw) return -1;
+    const Game& gm = p->games[g];
+    if (id < 0 || id >= (int)gm.nodes.size()) return -1;
+    const int t = gm.rave_tab(id);
+    if (t < 0) return -1;
+    std::memcpy(rn, &gm.rv_tabs[(size_t)t], 81 * sizeof(int64_t));
+    std::memcpy(rw, &gm.rv_tabs[(size_t)t + 81], 81 * sizeof(int64_t));
+    return 0;
 }
 
 int bk_pool_n_games(const bk_pool* p) { return (int)p->games.size(); }
@@ -1792,6 +1966,13 @@ void snapshot_game(const Game& gm, SnapWriter& w) {
     const int64_t vq[2] = {gm.sum_root_value_q, gm.sum_abs_root_value_q};
     w.pod(vq);
     w.pod(gm.n_root_values);
+    if (gm.rave_k > 0.0) {                               // RAVE on: the parameter, the tables and the records follow; off: not a byte
+        w.pod(gm.rave_k);
+        w.vec(gm.rv_tab_of);
+        w.vec(gm.rv_rec_of);
+        w.vec(gm.rv_tabs);
+        w.vec(gm.rv_recs);
+    }
 }
 
 // false: the bytes are not a snapshot this build can take (the game is left untouched)
@@ -1823,6 +2004,30 @@ bool restore_game(Game& dst, const uint8_t* buf, size_t len) {
     uint8_t flags[2];
     int64_t vq[2];
     r.pod(cnt); r.pod(gm.final_score); r.pod(flags); r.pod(gm.root_visits); r.pod(vq); r.pod(gm.n_root_values);
+    if (r.ok && r.p != r.end) {                          // a tree with RAVE on (snapshot_game): its parameter, tables and records
+        r.pod(gm.rave_k); r.vec(gm.rv_tab_of); r.vec(gm.rv_rec_of); r.vec(gm.rv_tabs); r.vec(gm.rv_recs);
+        if (!r.ok || !(gm.rave_k > 0.0) || !std::isfinite(gm.rave_k)) return false;
+        if (prm.leaves > 1 || prm.simulate || !prm.use_value || prm.value_weight != 1.0) return false;   // (bk_pool_set_rave's rule)
+        if (gm.rv_tab_of.size() > gm.nodes.size() || gm.rv_rec_of.size() > gm.nodes.size()) return false;
+        if (gm.rv_tabs.size() % Game::kRaveTab || gm.rv_recs.size() % Game::kRaveRec) return false;
+        for (int32_t o : gm.rv_tab_of)
+            if (o != -1 && (o < 0 || o % Game::kRaveTab || (size_t)o + Game::kRaveTab > gm.rv_tabs.size())) return false;
+        for (int32_t o : gm.rv_rec_of)
+            if (o != -1 && (o < 0 || o % Game::kRaveRec || (size_t)o + Game::kRaveRec > gm.rv_recs.size())) return false;
+        for (size_t t = 0; t < gm.rv_tabs.size(); t += Game::kRaveTab)         // counts that can be added to for a long time yet
+            for (int s = 0; s < 81; ++s) {
+                const int64_t a = gm.rv_tabs[t + (size_t)s], b = gm.rv_tabs[t + 81 + (size_t)s];
+                if (a < 0 || a > ((int64_t)1 << 56) || b < 0 || b > a) return false;
+            }
+        for (size_t q = 0; q < gm.rv_recs.size(); q += Game::kRaveRec) {
+            const int32_t n_ = gm.rv_recs[q], w_ = gm.rv_recs[q + 1];
+            if (n_ < 1 || w_ < 0 || w_ > n_) return false;
+            for (int s = 0; s < 2 * 81; ++s) {
+                const int32_t a = gm.rv_recs[q + 2 + (size_t)s], b = gm.rv_recs[q + 2 + 2 * 81 + (size_t)s];
+                if (a < 0 || a > n_ || b < 0 || b > a) return false;
+            }
+        }
+    }
     if (!r.ok || r.p != r.end) return false;
     gm.n_value_evals = cnt[0]; gm.n_policy_evals = cnt[1]; gm.n_requests = cnt[2];
     gm.manual = flags[0] != 0; gm.analyze = flags[1] != 0;

@@ -471,6 +471,9 @@ def build_parser():
     ap.add_argument("--playout-prior", type=float, default=0.0, metavar="LAMBDA",
                     help="with --playout-value: that share (0..1) of the priors comes from the playouts' AMAF counts; with 1 "
                          "no policy net is loaded")
+    ap.add_argument("--playout-rave", type=float, nargs="?", const=4.0, default=0.0, metavar="K",
+                    help="with --playout-value: RAVE -- the playouts' two-sided AMAF counts are backed up into per-node tables and "
+                         "blended into the selection with the equivalence parameter K (visits; 4 when no value is given: the one of 4, 16 and 64 that won its 100-game match, DESIGN 20)")
     ap.add_argument("--python-tree", action="store_true", help="search with the Python tree instead of the native one")
     ap.set_defaults(v_given=False)
     return ap
@@ -504,6 +507,10 @@ def parse_args(argv=None):
         ap.error("--playout-prior must be within 0..1")
     if args.playout_prior and not args.playout_value:
         ap.error("--playout-prior reads the playouts of --playout-value: it needs --playout-value N")
+    if not 0.0 <= args.playout_rave < float("inf"):
+        ap.error("--playout-rave must be a finite number, 0 or more")
+    if args.playout_rave and not args.playout_value:
+        ap.error("--playout-rave reads the playouts of --playout-value: it needs --playout-value N")
     return args
 
 
@@ -528,6 +535,8 @@ def main(argv=None):
         more["playout_tactics"] = args.playout_tactics
     if args.playout_prior:
         more["playout_prior"] = args.playout_prior
+    if args.playout_rave:
+        more["playout_rave"] = args.playout_rave
     gtp = cls(root, pi, val, no_sim=not args.simulate, time_lim=None if args.r else args.t, n_rollouts=args.r, pondering=args.ponder,
               rollout_score=args.rollout_score, **more)
     gtp.start()

@@ -238,6 +238,8 @@ def parse_args(argv=None):
     ap.add_argument("--playout-prior", type=float, default=0.0, metavar="LAMBDA",
                     help="with --playout-value: that share (0..1) of its priors comes from the playouts' AMAF counts; with 1 "
                          "the engine loads no policy net")
+    ap.add_argument("--playout-rave", type=float, nargs="?", const=4.0, default=0.0, metavar="K",
+                    help="with --playout-value: RAVE with the equivalence parameter K (visits; 4 when no value is given, DESIGN 20)")
     ap.add_argument("--opponent", default="policy", help='"policy" (raw policy, no search) or a GTP command line')
     ap.add_argument("--komi", type=float, default=5.5)
     ap.add_argument("--sgf", default=None, help="prefix for SGF records")
@@ -262,6 +264,10 @@ def parse_args(argv=None):
         ap.error("--playout-prior must be within 0..1")
     if args.playout_prior and not args.playout_value:
         ap.error("--playout-prior reads the playouts of --playout-value: it needs --playout-value N")
+    if not 0.0 <= args.playout_rave < float("inf"):
+        ap.error("--playout-rave must be a finite number, 0 or more")
+    if args.playout_rave and not args.playout_value:
+        ap.error("--playout-rave reads the playouts of --playout-value: it needs --playout-value N")
     return args
 
 
@@ -282,6 +288,9 @@ def main(argv=None):
         if args.playout_prior:
             more["playout_prior"] = args.playout_prior
             name += f"-amaf{args.playout_prior:g}"
+        if args.playout_rave:
+            more["playout_rave"] = args.playout_rave
+            name += f"-rave{args.playout_rave:g}"
         a = InProcessEngine(NativeGTP(Position(), None if args.playout_prior == 1.0 else pi, None, no_sim=True, time_lim=None,
                                       n_rollouts=args.r, playout_value=args.playout_value, **more),
                             name=args.engine_name or name)

@@ -136,12 +136,19 @@ class NativeMCTS:
     `playout_patterns=` (a patterns.PatternTable or the path of one, with playout_value): its pattern-weighted playouts;
     `playout_tactics=` (a tactics.TacticTable or the path of one, with playout_value): its tactical weights (DESIGN 18);
     `playout_prior=` (0..1, with playout_value): that share of the priors comes from the playouts' AMAF counts, and with 1.0
-    policy_net may be None -- a search without any network."""
+    policy_net may be None -- a search without any network (DESIGN 19);
+    `playout_rave=k` (> 0, with playout_value): RAVE -- the playouts' two-sided AMAF counts are backed up into per-node tables
+    and blended into the selection with the equivalence parameter k (bk_pool_set_rave); `rave(node)` reads a table."""
 
     def __init__(self, root=None, policy_net=None, value_net=None, **kwargs):
         self.playout_prior = float(kwargs.get("playout_prior") or 0.0)   # 0: the priors are the policy net's alone
         if self.playout_prior and not kwargs.get("playout_value"):
             raise TypeError("playout_prior reads the playouts of playout_value=N: it needs playout_value")
+        self.playout_rave = float(kwargs.get("playout_rave") or 0.0)     # 0: no RAVE
+        if self.playout_rave and not kwargs.get("playout_value"):
+            raise TypeError("playout_rave reads the playouts of playout_value=N: it needs playout_value")
+        if not 0.0 <= self.playout_rave < float("inf"):
+            raise ValueError("playout_rave must be a finite number >= 0")
         if policy_net is None and kwargs.get("evaluator") is None and self.playout_prior != 1.0:
             raise TypeError("Missing required keywork argument: 'policy_net'")
         self.no_sim = kwargs.get("no_sim", True)
@@ -216,6 +223,8 @@ class NativeMCTS:
         self.children = _ChildrenView(self)
         self._lib = self._pool._lib
         self._lib.bk_pool_set_manual(self._pool._h, 1)
+        if self.playout_rave:
+            self._pool.set_rave(self.playout_rave)
         self.komi = getattr(root, "komi", 5.5) if root is not None else 5.5
         if root is not None and root.key() != Position().key():
             self._set_position(root)
@@ -248,6 +257,8 @@ class NativeMCTS:
             more["patterns"] = self.playout_patterns
         if self.playout_tactics is not None:
             more["tactics"] = self.playout_tactics
+        if getattr(self, "playout_rave", 0.0):
+            more["rave"] = True
         return rollout.PlayoutEvaluator(get(), self.playout_value, seed=self.playout_seed, rules=self.playout_rules, **more)
 
     def _evaluator_from_nets(self):
@@ -462,7 +473,7 @@ class NativeMCTS:
                 rows = np.frombuffer(bytes(node._pos), np.uint8).reshape(1, 192).copy()
             else:
                 rows = planes[None]
-            probs, _ = self.evaluator(rows, 1)
+            probs = self.evaluator(rows, 1)[0]               # (a RAVE evaluator hands back records as well)
             pr = torch.from_numpy(np.asarray(probs[0], np.float32))
         else:
             pr = d.probs.clone()                         # (the tree's own prior is left alone)
@@ -516,6 +527,13 @@ class NativeMCTS:
         w = self.value_net_weight
         q = self.Q._read(i) if not self.no_sim else 0.0
         return (((1 - w) * q + w * info.V) / info.N + 1) / 2
+
+    def rave(self, node=None):
+        """(rn, rw), int64 [81] each: the RAVE table of the root or of any node of the tree -- the AMAF playouts in which the
+        node's side to move was the first to play each point, and those of them it won (bk_pool_node_rave).  None
+        where there is no table: RAVE off, a position the tree never saw, a node no recorded rollout has passed yet."""
+        i = self._lib.bk_pool_root_id(self._pool._h, 0) if node is None else self._find(node)
+        return None if i < 0 else self._pool.node_rave(0, i)
 
     def child_stats(self):
         """{move: (N, V)} of the root's children."""

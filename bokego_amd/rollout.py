@@ -43,6 +43,10 @@ PlayoutEvaluator(prior=1.0) into an engine that searches with no network at all.
 
     python -m bokego_amd.rollout --sgf FILE [--move K] --random --amaf [-n 256]   # the value and the heaviest prior moves
 
+playout_amaf(sides=2) keeps the opponent's half of every history too (one bkt_amaf_counts_sides), and
+PlayoutEvaluator(rave=True) hands those two-sided counts of every row to the tree, whose RAVE tables are made of them
+(bk_pool_deliver_rave, NativeMCTS(playout_rave=k)).  `--amaf --sides 2` prints both sides' heaviest points.
+
 rules="host" is one loop (_playout_host) on the host rules with the same draws (lockstep's play_host, features_batch
 and area_score_host, bk_pos_is_legal, bk_pos_possible_eye, lockstep.sample_host in float64): the reference the tests
 compare the device with.  With engine=None it needs no GPU.
@@ -65,7 +69,8 @@ MOVE_NONE = -2             # BKT_MOVE_NONE; in the history: the game was over be
 SEKI_THRESHOLD = 0.5       # |mean ownership| of a stone's point below this: the stone is in seki (rollout_score)
 POS_BYTES = L.POS_BYTES
 
-__all__ = ["MAX_PLIES", "MOVE_NONE", "Amaf", "Finished", "PlayoutEvaluator", "RolloutScore", "amaf_counts_host", "amaf_prior",
+__all__ = ["MAX_PLIES", "MOVE_NONE", "Amaf", "Finished", "PlayoutEvaluator", "RolloutScore", "amaf_counts_host",
+           "amaf_counts_sides_host", "amaf_prior",
            "default_counters", "finish_games", "format_score", "owner_board", "owner_host", "playable_host", "playout_amaf",
            "playout_value", "random_playouts", "record_turns", "rollout_score", "sgf_position"]
 
@@ -452,14 +457,15 @@ def _playout_value_device(recs, n, key, komi, max_plies=MAX_PLIES, table=None, t
     return _value_of_wins(won.sum(1), n)
 
 
-def _playout_amaf_device(recs, n, key, komi, counted=None, max_plies=MAX_PLIES, table=None, tactics=None):
+def _playout_amaf_device(recs, n, key, komi, counted=None, max_plies=MAX_PLIES, table=None, tactics=None, sides=1):
     """_playout_value_device's games with their history, and one bkt_amaf_counts over the rows of the first `counted`
     records (default: all) -> (value float32 [R], wins int64 [R], played int32 [counted,81], won int32 [counted,81]) on the
-    device; nothing here waits for it."""
+    device; nothing here waits for it.  sides=2: one bkt_amaf_counts_sides instead, and the counts are [counted,2,81]."""
     counted = len(recs) if counted is None else counted
     won, moves = _playouts_won_device(recs, n, key, komi, max_plies, table, tactics, True)
     w = won.sum(1)
-    played, won_at = T.amaf_counts(moves[:counted * n], won[:counted].to(torch.uint8).reshape(-1), counted, n)
+    reduce = T.amaf_counts if sides == 1 else T.amaf_counts_sides
+    played, won_at = reduce(moves[:counted * n], won[:counted].to(torch.uint8).reshape(-1), counted, n)
     return _value_of_wins(w, n), w, played, won_at
 
 
@@ -495,6 +501,8 @@ class Amaf:
     played  int32 [R,81]    the playouts in which the side to move was the first to play the point
     won     int32 [R,81]    those of them it won
     n       int             the playouts per record
+    With playout_amaf(sides=2) played and won are [R,2,81]: [:, 0] as above, [:, 1] the same for the opponent, who wins
+    the playouts the side to move loses (amaf_counts_sides_host has the definition).
     """
 
     def __init__(self, value, wins, played, won, n):
@@ -521,11 +529,37 @@ def amaf_counts_host(moves, won, records, playouts):
     return played.astype(np.int32), won_at.astype(np.int32)
 
 
-def playout_amaf(recs, n, seed, rules="device", komi=L.KOMI, device=None, patterns=None, tactics=None):
+def amaf_counts_sides_host(moves, won, records, playouts):
+    """bkt_amaf_counts_sides in numpy (include/bokego_train.h has the definition): amaf_counts_host's moves and won ->
+    (played, won_at) int32 [records, 2, 81].  A row counts for the point s and the side k & 1, k the smallest ply with
+    moves[row, k] == s: side 0 is the side to move at the record and wins the rows with won != 0, side 1 its opponent, who
+    wins the others.  [:, 0] is amaf_counts_host's result."""
+    records, playouts = int(records), int(playouts)
+    moves, won = np.asarray(moves), np.asarray(won).reshape(-1) != 0
+    if records < 1 or playouts < 1 or moves.ndim != 2 or len(moves) != records * playouts or len(won) != len(moves):
+        raise ValueError(f"moves must be [{records} * {playouts}, max_plies] and won [{records} * {playouts}]")
+    G, P = moves.shape
+    use = (np.cumsum(moves <= MOVE_NONE, 1) == 0) & (moves >= 0) & (moves <= 80)
+    row, ply = np.nonzero(use)
+    first = np.full((G, 81), P, np.int64)                                  # P: never played
+    np.minimum.at(first, (row, moves[row, ply].astype(np.int64)), ply)
+    played, won_at = np.zeros((2, records, 2, 81), np.int32)
+    for side in (0, 1):
+        counts = (first < P) & (first % 2 == side)
+        played[:, side] = counts.reshape(records, playouts, 81).sum(1)
+        won_at[:, side] = (counts & (won == (side == 0))[:, None]).reshape(records, playouts, 81).sum(1)
+    return played, won_at
+
+
+def playout_amaf(recs, n, seed, rules="device", komi=L.KOMI, device=None, patterns=None, tactics=None, sides=1):
     """playout_value's n playouts of each record with what else they tell -> Amaf: the value (the history does not enter a
     game: the same bits), the wins, and the all-moves-as-first counts of every point (amaf_counts_host has the definition).
     rules="device": the playout launches with their history, `won` built in torch, one bkt_amaf_counts; rules="host": the
-    mirror end to end, the same integers.  recs, patterns, tactics: as playout_value."""
+    mirror end to end, the same integers.  recs, patterns, tactics: as playout_value.
+    sides=2: the counts of both sides, [R,2,81] (one bkt_amaf_counts_sides; amaf_counts_sides_host); value and wins are the
+    same either way."""
+    if sides not in (1, 2):
+        raise ValueError("sides must be 1 or 2")
     L.check_rules(rules)
     table, tactics = _table(patterns), _tactics(tactics)
     n = _check_playouts(n)
@@ -533,10 +567,10 @@ def playout_amaf(recs, n, seed, rules="device", komi=L.KOMI, device=None, patter
     key = L.seed_u64(seed)
     if rules == "device":
         t = L.records_to_device(recs, _device(device, None, recs), clone=False)
-        value, w, played, won_at = _playout_amaf_device(t, n, key, komi, table=table, tactics=tactics)
+        value, w, played, won_at = _playout_amaf_device(t, n, key, komi, table=table, tactics=tactics, sides=sides)
         return Amaf(value.cpu().numpy(), w.cpu().numpy().astype(np.int32), played.cpu().numpy(), won_at.cpu().numpy(), n)
     value, w, moves = _playout_host_wins(recs, n, key, komi, table, tactics, True)
-    played, won_at = amaf_counts_host(moves, w.reshape(-1), len(w), n)
+    played, won_at = (amaf_counts_host if sides == 1 else amaf_counts_sides_host)(moves, w.reshape(-1), len(w), n)
     return Amaf(value, w.sum(1).astype(np.int32), played, won_at, n)
 
 
@@ -561,15 +595,17 @@ def amaf_prior(recs, amaf, k=PRIOR_K, temperature=PRIOR_TEMPERATURE):
         q_s = (won_s + k * wbar) / (played_s + k)      the AMAF win rate of the point, k playouts' worth of wbar mixed in,
         p_s = exp((q_s - max q over the legal points) / temperature) on the legal points (bk_pos_legal_moves), 0 elsewhere,
     each row divided by its sum; a record without a legal point gets 1/81 everywhere.  k and temperature must be > 0; their
-    defaults, 4.0 and 0.1, are plausible and untuned."""
+    defaults, 4.0 and 0.1, are plausible and untuned.  Two-sided counts ([R,2,81], playout_amaf(sides=2)) are read at side 0."""
     k, temperature = float(k), float(temperature)
     if not k > 0 or not temperature > 0:
         raise ValueError("k and temperature must be greater than 0")
     recs = np.array(_numpy(recs), np.uint8, order="C")
     _check_records(recs)
     played, won = np.asarray(amaf.played, np.float64), np.asarray(amaf.won, np.float64)
+    if played.shape == (len(recs), 2, 81) and won.shape == played.shape:   # two-sided counts: the side to move's half
+        played, won = played[:, 0], won[:, 0]
     if played.shape != (len(recs), 81) or won.shape != played.shape:
-        raise ValueError(f"the counts must be [{len(recs)}, 81], one row per record")
+        raise ValueError(f"the counts must be [{len(recs)}, 81] or [{len(recs)}, 2, 81], one row per record")
     wbar = np.asarray(amaf.wins, np.float64) / float(amaf.n)
     q = (won + k * wbar[:, None]) / (played + k)
     legal = legal_host(recs)
@@ -592,13 +628,18 @@ class PlayoutEvaluator:
     temperature=prior_temperature), and the priors handed on are (1 - prior) * the engine's + prior * amaf_prior, mixed in
     float64, cast to float32 and normalised as before.  With prior=1 the engine is never asked and may be None: a search
     without any network.
+    rave=True: the playouts of ALL rows run with their history, one bkt_amaf_counts_sides reduces them, and finish returns a
+    third element, records = (playouts, wins int32 [B], played int32 [B,2,81], won_at int32 [B,2,81]), which
+    selfplay.GamePool.deliver hands to the tree's RAVE tables; the prior, when prior > 0, reads side 0 of the first
+    n_policy rows of the same counts -- one reduction launch, not two.  Probs and values are what they are without it.
     The engine is kept as `policy_engine`, not `engine`: selfplay.run_pools_native hands an evaluator's `engine` to the C
     step loop as its own bk_evaluator, which would compute no playouts -- this class goes through callback_evaluator."""
     wants_positions = True
 
     def __init__(self, engine, playouts=64, seed=0, rules="device", komi=L.KOMI, patterns=None, tactics=None, prior=0.0,
-                 prior_k=PRIOR_K, prior_temperature=PRIOR_TEMPERATURE):
+                 prior_k=PRIOR_K, prior_temperature=PRIOR_TEMPERATURE, rave=False):
         L.check_rules(rules)
+        self.rave = bool(rave)
         self.patterns = _table(patterns)                                  # None: uniformly random playouts
         self.tactics = _tactics(tactics)                                  # None: no tactical weights (DESIGN 18)
         self.prior = float(prior)
@@ -626,6 +667,16 @@ class PlayoutEvaluator:
             ticket = self.policy_engine.submit_positions(recs[:n_policy], logits=False, probs=True, value=False,
                                                          n_policy=n_policy)
         more = dict(komi=self.komi, table=self.patterns, tactics=self.tactics)
+        if self.rave:                                                     # every row with its history, both sides counted
+            if self.rules == "host":
+                values, w, moves = _playout_host_wins(recs, self.playouts, self.seed, history=True, **more)
+                counts = amaf_counts_sides_host(moves, w.reshape(-1), len(recs), self.playouts)
+                w = w.sum(1)
+            else:
+                t = torch.from_numpy(recs).to(_device(None, self.policy_engine))
+                values, w, *counts = _playout_amaf_device(t, self.playouts, self.seed, sides=2, **more)
+            counted = (recs[:n_policy], n_policy) if n_policy and self.prior > 0.0 else None
+            return ticket, values, counted, (w, *counts)
         if n_policy and self.prior > 0.0:                                 # the playouts with their history, and the counts
             if self.rules == "host":
                 values, w, moves = _playout_host_wins(recs, self.playouts, self.seed, history=True, **more)
@@ -643,10 +694,16 @@ class PlayoutEvaluator:
         return ticket, values, None
 
     def finish(self, handle, normalise=None):
-        ticket, values, counted = handle
+        ticket, values, counted, *rave = handle
         if normalise is None:
             from .selfplay import normalise_like_categorical as normalise
         probs = np.zeros((0, 81), np.float32) if ticket is None else self.policy_engine.wait(ticket)["probs"]
+        records = None
+        if rave:                                                          # (w, played, won_at) of every row, two-sided
+            w, played, won = (np.ascontiguousarray(_numpy(x), np.int32) for x in rave[0])
+            records = (self.playouts, w, played, won)
+            if counted is not None:
+                counted = (counted[0], w[:counted[1]], played[:counted[1]], won[:counted[1]])
         if counted is not None:
             recs, w, played, won = (_numpy(x) for x in counted)
             prior = amaf_prior(recs, Amaf(None, w, played, won, self.playouts), self.prior_k, self.prior_temperature)
@@ -655,7 +712,8 @@ class PlayoutEvaluator:
             probs = prior.astype(np.float32)
         if len(probs):
             probs = normalise(probs)
-        return probs, (values if isinstance(values, np.ndarray) else values.cpu().numpy())
+        values = values if isinstance(values, np.ndarray) else values.cpu().numpy()
+        return (probs, values, records) if records is not None else (probs, values)
 
     def __call__(self, recs, n_policy):
         return self.finish(self.submit(recs, n_policy))
@@ -759,6 +817,8 @@ def _parse(argv):
                     help="with --random: multiply the weights by the tactical weights of this table (python -m bokego_amd.tactics fit)")
     ap.add_argument("--amaf", action="store_true",
                     help="with --random: print the Monte-Carlo value and the ten heaviest moves of the AMAF prior instead of the score")
+    ap.add_argument("--sides", type=int, default=1, choices=(1, 2),
+                    help="with --amaf: 2 also prints the opponent's heaviest points (the two-sided counts RAVE is fed with)")
     ap.add_argument("-n", dest="n", type=int, default=256, help="playouts")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--komi", type=float, default=L.KOMI)
@@ -766,6 +826,8 @@ def _parse(argv):
     args = ap.parse_args(argv)
     if args.amaf and not args.random:
         ap.error("--amaf reads the one-launch playouts: it needs --random")
+    if args.sides != 1 and not args.amaf:
+        ap.error("--sides goes with --amaf")
     if args.n < 1:
         ap.error("-n must be at least 1")
     if args.random and args.p is not None:
@@ -800,11 +862,16 @@ def main(argv=None):
     if args.amaf:
         recs = _as_records(game)
         a = playout_amaf(recs, args.n, args.seed, komi=args.komi, device=torch.device("cuda", args.device),
-                         patterns=args.patterns, tactics=args.tactics)
+                         patterns=args.patterns, tactics=args.tactics, sides=args.sides)
         prior = amaf_prior(recs, a)[0]
-        print(json.dumps({"value": float(a.value[0]), "wins": int(a.wins[0]), "playouts": args.n,
-                          "prior": [{"move": go.unsquash(s), "prior": float(prior[s]), "played": int(a.played[0, s]),
-                                     "won": int(a.won[0, s])} for s in np.argsort(-prior, kind="stable")[:10].tolist()]}))
+        played, won = (a.played[0], a.won[0]) if args.sides == 1 else (a.played[0, 0], a.won[0, 0])
+        out = {"value": float(a.value[0]), "wins": int(a.wins[0]), "playouts": args.n,
+               "prior": [{"move": go.unsquash(s), "prior": float(prior[s]), "played": int(played[s]),
+                          "won": int(won[s])} for s in np.argsort(-prior, kind="stable")[:10].tolist()]}
+        if args.sides == 2:                                               # the opponent's points, by the playouts they were played in
+            out["opponent"] = [{"move": go.unsquash(s), "played": int(a.played[0, 1, s]), "won": int(a.won[0, 1, s])}
+                               for s in np.argsort(-a.played[0, 1], kind="stable")[:10].tolist()]
+        print(json.dumps(out))
         return
     eng = None
     if args.p is not None:

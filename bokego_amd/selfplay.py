@@ -75,6 +75,9 @@ TREE_SYMBOLS = {
     "bk_pool_collect": (ctypes.c_int, [_VP, _VP, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]),
     "bk_pool_collect_pos": (ctypes.c_int, [_VP, _VP, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]),
     "bk_pool_deliver": (None, [_VP, _VP, _VP]),
+    "bk_pool_set_rave": (ctypes.c_int, [_VP, ctypes.c_double]),
+    "bk_pool_deliver_rave": (None, [_VP, _VP, _VP, ctypes.c_int, _VP, _VP, _VP]),
+    "bk_pool_node_rave": (ctypes.c_int, [_VP, ctypes.c_int, ctypes.c_int, _VP, _VP]),
     "bk_pool_phase_seconds": (None, [_VP, _VP]),
     "bk_pool_set_dedup": (None, [_VP, ctypes.c_int]),
     "bk_pool_set_lanes": (None, [_VP, ctypes.c_int]),
@@ -241,10 +244,35 @@ class GamePool:
         B = self._lib.bk_pool_collect_pos(self._h, self._recs.ctypes.data, self.cap, ctypes.byref(npol))
         return self._recs[:B], npol.value
 
-    def deliver(self, probs, values):
+    def deliver(self, probs, values, records=None):
+        """records: None, or the AMAF records of the rows of `values` (bk_pool_deliver_rave; a pool with set_rave(k > 0)
+        builds its RAVE tables of them): (playouts, wins int32 [B], played int32 [B,2,81], won_at int32 [B,2,81])."""
         probs = np.ascontiguousarray(probs, dtype=np.float32)
         values = np.ascontiguousarray(values, dtype=np.float32)
-        self._lib.bk_pool_deliver(self._h, probs.ctypes.data, values.ctypes.data)
+        if records is None:
+            self._lib.bk_pool_deliver(self._h, probs.ctypes.data, values.ctypes.data)
+            return
+        playouts, wins, played, won_at = records
+        wins, played, won_at = (np.ascontiguousarray(x, dtype=np.int32) for x in (wins, played, won_at))
+        B = len(values)
+        if int(playouts) < 1 or wins.shape != (B,) or played.shape != (B, 2, 81) or won_at.shape != (B, 2, 81):
+            raise ValueError(f"records must be (playouts >= 1, wins [{B}], played [{B},2,81], won_at [{B},2,81])")
+        self._lib.bk_pool_deliver_rave(self._h, probs.ctypes.data, values.ctypes.data, int(playouts), wins.ctypes.data,
+                                       played.ctypes.data, won_at.ctypes.data)
+
+    def set_rave(self, equiv):
+        """RAVE on the pool's games (bk_pool_set_rave): equiv > 0 is the equivalence parameter k, 0 switches it off.
+        ValueError when the pool's search mode has no RAVE (leaves > 1, simulate, no value net) or equiv is no such number."""
+        if self._lib.bk_pool_set_rave(self._h, float(equiv)):
+            raise ValueError(f"bk_pool_set_rave refused equiv={equiv!r}: it must be finite and >= 0, and the search the plain "
+                             "one (leaves = 1, no simulation, a value with weight 1)")
+
+    def node_rave(self, g, node_id):
+        """(rn, rw) int64 [81] each: the RAVE table of node `node_id` of game g (bk_pool_node_rave); None if it has none."""
+        rn, rw = np.empty(81, np.int64), np.empty(81, np.int64)
+        if self._lib.bk_pool_node_rave(self._h, int(g), int(node_id), rn.ctypes.data, rw.ctypes.data):
+            return None
+        return rn, rw
 
     @property
     def n_done(self):
@@ -376,7 +404,7 @@ def callback_evaluator(evaluator):
             r = np.ctypeslib.as_array((ctypes.c_uint8 * (B * 192)).from_address(recs)).reshape(B, 192)
             if not getattr(evaluator, "wants_positions", False):
                 raise TypeError("the native step loop hands over position records: the evaluator must take them (RecordEvaluator)")
-            p, v = evaluator.finish(evaluator.submit(r, n_policy), normalise=lambda x: x)
+            p, v = evaluator.finish(evaluator.submit(r, n_policy), normalise=lambda x: x)[:2]   # (bk_evaluator carries no AMAF records)
             if n_policy:
                 np.ctypeslib.as_array((ctypes.c_float * (n_policy * 81)).from_address(probs))[:] = np.asarray(p, np.float32).reshape(-1)
             np.ctypeslib.as_array((ctypes.c_float * B).from_address(values))[:] = np.asarray(v, np.float32).reshape(-1)
@@ -427,8 +455,7 @@ def run_pools(pools, evaluator, progress=None):
     while any(live) or any(h is not None for h in inflight):
         for i, pool in enumerate(pools):
             if inflight[i] is not None:
-                probs, values = evaluator.finish(inflight[i], normalise=normalise_rows)
-                pool.deliver(probs, values)
+                pool.deliver(*evaluator.finish(inflight[i], normalise=normalise_rows))   # (probs, values[, AMAF records])
                 inflight[i] = None
             if live[i]:
                 feats, npol = pool.collect_positions() if getattr(evaluator, "wants_positions", False) else pool.collect()

@@ -278,6 +278,21 @@ int bkt_tactical_playouts(void *pos, int batch, uint64_t seed, const uint32_t *c
 int bkt_amaf_counts(const int16_t *moves, int max_plies, const uint8_t *won, int records, int playouts, int32_t *played,
                     int32_t *won_at, void *stream);
 
+/* The same counts for both sides of every history: the AMAF records of the tree's RAVE tables (bk_pool_deliver_rave,
+ * include/bokego_tree.h).  moves, won and the row-to-record mapping are bkt_amaf_counts'.  For a row and a point
+ * s let k be the smallest ply with moves[row, k] == s, looking no further than the first entry <= BKT_MOVE_NONE.  If k
+ * exists, the row counts for side k & 1 -- side 0 is the side to move at the record, side 1 its opponent, who wins the
+ * rows with won[row] == 0:
+ *   played[(r * 2 + (k & 1)) * 81 + s] += 1,
+ *   won_at[(r * 2 + (k & 1)) * 81 + s] += ((won[row] != 0) == ((k & 1) == 0)).
+ * A point counts once per row, for the side that played it first, so played[r, 0, s] + played[r, 1, s] <= playouts.
+ * Passes are skipped; an entry above 80 is ignored (entries are compared, never used as an index).  Every entry of
+ * played and won_at [records, 2, 81] is written, zeros included.  Integers only: the counts do not depend on any order,
+ * and side 0 equals bkt_amaf_counts' output on the same input, integer for integer.
+ * The argument checks are bkt_amaf_counts': else BKT_ERR_ARG, nothing is launched and nothing written. */
+int bkt_amaf_counts_sides(const int16_t *moves, int max_plies, const uint8_t *won, int records, int playouts,
+                          int32_t *played, int32_t *won_at, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

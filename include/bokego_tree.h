@@ -143,6 +143,44 @@ void bk_pool_set_task_cap(bk_pool *p, int tasks);
 /* probs: [n_policy][81] (already Categorical-normalised), values: [B], same order as collected */
 void bk_pool_deliver(bk_pool *p, const float *probs, const float *values);
 
+/*
+ * RAVE (opt-in, off by default): UCT's means blended with all-moves-as-first statistics of the playouts behind the
+ * values (bkt_amaf_counts_sides, include/bokego_train.h).  No struct changes: it comes in through these three symbols.
+ *
+ *   bk_pool_set_rave(p, equiv)   equiv = 0: off; > 0: the equivalence parameter k of the selection below, for every game of the
+ *                                pool.  Returns -1 and changes nothing when equiv is negative or not finite, or when the pool's
+ *                                parameters have leaves > 1, simulate set, use_value == 0 or value_weight != 1: RAVE lives in
+ *                                the plain backup only.  Switching it off drops the tables and records.
+ *   bk_pool_deliver_rave         bk_pool_deliver plus one AMAF record per row of `values`, rows as `values` has them (either
+ *                                collect's layout): wins[row] = the playouts the row's side to move won, of `playouts`; played and
+ *                                won_at [B][2][81] as bkt_amaf_counts_sides writes them (side 0 = the side to move; counts within
+ *                                0..playouts).  A node keeps the record that arrives with its value -- the first delivery wins --
+ *                                and a terminal node keeps none.  With RAVE off the records are ignored.
+ *   bk_pool_node_rave            the node's table rn[81], rw[81]; -1 if it has none (no recorded rollout has passed it yet).
+ *
+ * Backup.  A rollout has the path p_0 (root) .. p_L (leaf), m_j the move that leads to p_j, and the leaf's record A = (n =
+ * playouts, w = wins, played, won_at); if the leaf has no record -- a terminal node, a value from plain bk_pool_deliver, every
+ * value of bk_pools_run, whose callbacks cannot carry records: a RAVE pool driven by the C loop searches exactly as with RAVE
+ * off -- the rollout updates no table.  Otherwise every p_i that has priors gets (a table of zeros first, if it has none), with
+ * side = (L - i) & 1 and F = the board points among m_{i+1} .. m_L:
+ *   tree part     for j = i+1 .. L with (j - i) odd, m_j a board point not among m_{i+1} .. m_{j-1}:
+ *                 rn[m_j] += n;  rw[m_j] += (side == 0 ? w : n - w)
+ *   playout part  for every point s not in F:  rn[s] += played[side][s];  rw[s] += won_at[side][s]
+ * -- the first-play rule over tree path plus playout, in integers: no order of rollouts or deliveries can change a table.
+ *
+ * Select.  At a node with a table, for the child c reached by move m with a = rn[m] > 0:
+ *   beta = a / (a + N_c + a * N_c / k),   mean = (1 - beta) * (-avg_c) + beta * (2 rw[m] / a - 1),
+ *   score = mean + c_puct * prior[m] * sqrt(total) / (1 + N_c);
+ * with a == 0, at a node without a table, and with k == 0 the score is the plain one.  N_c counts visits, each backed by one
+ * value of n playouts; a counts playouts; k is in visits, and untuned.
+ * Pruning and re-rooting carry tables and records with the nodes they keep; a snapshot of a tree with RAVE on has them (and k)
+ * appended, one of a tree with RAVE off is byte for byte what it was.
+ */
+int bk_pool_set_rave(bk_pool *p, double equiv);
+void bk_pool_deliver_rave(bk_pool *p, const float *probs, const float *values, int playouts, const int32_t *wins,
+                          const int32_t *played, const int32_t *won_at);
+int bk_pool_node_rave(const bk_pool *p, int g, int id, int64_t *rn, int64_t *rw);
+
 /* host seconds this pool has spent so far advancing its games (select / expand / backup), writing request rows, and taking
  * deliveries: out3 = {advance, emit, deliver} (tools/selfplay_breakdown.py) */
 void bk_pool_phase_seconds(const bk_pool *p, double *out3);
