@@ -51,6 +51,7 @@ SYMBOLS = {
     "bkt_tactical_playouts": (_I, [_P, _I, _U64, _P, _P, _P, _I, _P, _P, _P, _P, _P]),
     "bkt_amaf_counts": (_I, [_P, _I, _P, _I, _I, _P, _P, _P]),
     "bkt_amaf_counts_sides": (_I, [_P, _I, _P, _I, _I, _P, _P, _P]),
+    "bkt_owner_counts": (_I, [_P, _I, _I, _F, _P, _P, _P, _P, _P, _P]),
 }
 MAX_BATCH = 65536          # BKT_MAX_BATCH
 PRECISIONS = ("fp32", "bf16")
@@ -470,3 +471,28 @@ def amaf_counts_sides(moves, won, records, playouts):
                                         _dev(played, "played", dtype=torch.int32), _dev(won_at, "won_at", dtype=torch.int32),
                                         _stream(moves)), "bkt_amaf_counts_sides")
     return played, won_at
+
+
+def owner_counts(pos, records, playouts, komi=5.5):
+    """The ownership, agreement and score-margin counts of whole playouts (bkt_owner_counts; include/bokego_train.h has the
+    definition): pos uint8 [records * playouts, 192], the final records (read only), rows r * playouts .. of record r
+    -> (black int32 [records, 81], white int32 [records, 81], agree int32 [records, 81], hist int32 [records, 163],
+    black_wins int32 [records]): the playouts in which the point ended up black's, white's and the winner's, the playouts
+    by their margin B - W + 81 before komi, and those black won (bkt_area_score's score > 0)."""
+    records, playouts = int(records), int(playouts)
+    if records < 1 or playouts < 1 or records * playouts > MAX_SAMPLE_ROWS:
+        raise ValueError(f"records and playouts must be at least 1 and records * playouts at most {MAX_SAMPLE_ROWS}, "
+                         f"got {records} x {playouts}")
+    if not isinstance(pos, torch.Tensor) or pos.dim() != 2 or tuple(pos.shape) != (records * playouts, POS_BYTES):
+        raise ValueError(f"pos must be [{records * playouts}, {POS_BYTES}]")
+    komi = float(komi)
+    if komi - komi != 0.0:
+        raise ValueError("komi must be finite")
+    black, white, agree = (torch.empty((records, 81), dtype=torch.int32, device=pos.device) for _ in range(3))
+    hist = torch.empty((records, 163), dtype=torch.int32, device=pos.device)
+    black_wins = torch.empty((records,), dtype=torch.int32, device=pos.device)
+    _check(load().bkt_owner_counts(_dev(pos, "pos", dtype=torch.uint8), records, playouts, komi,
+                                   _dev(black, "black", dtype=torch.int32), _dev(white, "white", dtype=torch.int32),
+                                   _dev(agree, "agree", dtype=torch.int32), _dev(hist, "hist", dtype=torch.int32),
+                                   _dev(black_wins, "black_wins", dtype=torch.int32), _stream(pos)), "bkt_owner_counts")
+    return black, white, agree, hist, black_wins

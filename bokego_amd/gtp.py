@@ -20,7 +20,9 @@ its side to move wins (rollout.PlayoutEvaluator).  Not together with 
 needs the HIP engine as `--rollout-score` does.  `--playout-patterns FILE` (with `--playout-value`) draws the playouts'
 moves in proportion to the 3x3 pattern weights of a table fitted by `python -m bokego_amd.patterns fit` (DESIGN 17);
 `--playout-tactics FILE` (with `--playout-value`) multiplies them by the capture / escape / atari weights of a table fitted
-by `python -m bokego_amd.tactics fit`.
+by `python -m bokego_amd.tactics fit`.  `--playout-criticality GAMMA` (with `--playout-prior`) adds Coulom's
+criticality to the playout prior.  With `--playout-value`, `--rollout-score N` scores by N playouts of the
+search's own kind (rollout.ownership_score): the engine without any network scores its own games.
 """
 import argparse
 import os
@@ -286,11 +288,18 @@ class _GTPProtocol:
     NO_HIP = "rollout scoring needs the HIP backend"
 
     def _rollout_result(self):
-        """rollout.rollout_score of the root with the policy net's HIP engine; None when the net has none."""
+        """rollout.rollout_score of the root with the policy net's HIP engine; None when the net has none.  With
+        playout_value=N the search has playouts of its own: rollout.ownership_score of the root by rollout_score_n of them --
+        uniform, pattern-weighted or tactical as the search's, on the evaluator's device and rules -- and no net is needed."""
+        from . import rollout
+        if getattr(self, "playout_value", 0):
+            ev, root = self.evaluator, self.root
+            device = None if ev.rules == "host" else rollout._device(None, ev.policy_engine)
+            return rollout.ownership_score([root], self.rollout_score_n, self.rollout_seed, komi=root.komi, rules=ev.rules,
+                                           device=device, patterns=ev.patterns, tactics=ev.tactics)[0]
         get = getattr(self.policy_net, "engine", None)
         if not callable(get):
             return None
-        from . import rollout
         root = self.root
         return rollout.rollout_score([root], get(), n=self.rollout_score_n, seed=self.rollout_seed, komi=root.komi)[0]
 
@@ -474,6 +483,9 @@ def build_parser():
     ap.add_argument("--playout-rave", type=float, nargs="?", const=4.0, default=0.0, metavar="K",
                     help="with --playout-value: RAVE -- the playouts' two-sided AMAF counts are backed up into per-node tables and "
                          "blended into the selection with the equivalence parameter K (visits; 4 when no value is given: the one of 4, 16 and 64 that won its 100-game match, DESIGN 20)")
+    ap.add_argument("--playout-criticality", type=float, default=0.0, metavar="GAMMA",
+                    help="with --playout-prior: add GAMMA times Coulom's criticality of each point, from the final boards of the "
+                         "same playouts, to the AMAF win rates the prior is made of (untuned; default 0: off, DESIGN 21)")
     ap.add_argument("--python-tree", action="store_true", help="search with the Python tree instead of the native one")
     ap.set_defaults(v_given=False)
     return ap
@@ -511,6 +523,10 @@ def parse_args(argv=None):
         ap.error("--playout-rave must be a finite number, 0 or more")
     if args.playout_rave and not args.playout_value:
         ap.error("--playout-rave reads the playouts of --playout-value: it needs --playout-value N")
+    if not 0.0 <= args.playout_criticality < float("inf"):
+        ap.error("--playout-criticality must be a finite number, 0 or more")
+    if args.playout_criticality and not args.playout_prior:
+        ap.error("--playout-criticality is a term of the playout prior: it needs --playout-prior")
     return args
 
 
@@ -537,6 +553,8 @@ def main(argv=None):
         more["playout_prior"] = args.playout_prior
     if args.playout_rave:
         more["playout_rave"] = args.playout_rave
+    if args.playout_criticality:
+        more["playout_criticality"] = args.playout_criticality
     gtp = cls(root, pi, val, no_sim=not args.simulate, time_lim=None if args.r else args.t, n_rollouts=args.r, pondering=args.ponder,
               rollout_score=args.rollout_score, **more)
     gtp.start()

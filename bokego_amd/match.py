@@ -240,6 +240,9 @@ def parse_args(argv=None):
                          "the engine loads no policy net")
     ap.add_argument("--playout-rave", type=float, nargs="?", const=4.0, default=0.0, metavar="K",
                     help="with --playout-value: RAVE with the equivalence parameter K (visits; 4 when no value is given, DESIGN 20)")
+    ap.add_argument("--playout-criticality", type=float, default=0.0, metavar="GAMMA",
+                    help="with --playout-prior: GAMMA times Coulom's criticality of each point is added to the AMAF win rates of its "
+                         "prior (untuned; default 0: off, DESIGN 21)")
     ap.add_argument("--opponent", default="policy", help='"policy" (raw policy, no search) or a GTP command line')
     ap.add_argument("--komi", type=float, default=5.5)
     ap.add_argument("--sgf", default=None, help="prefix for SGF records")
@@ -268,6 +271,10 @@ def parse_args(argv=None):
         ap.error("--playout-rave must be a finite number, 0 or more")
     if args.playout_rave and not args.playout_value:
         ap.error("--playout-rave reads the playouts of --playout-value: it needs --playout-value N")
+    if not 0.0 <= args.playout_criticality < float("inf"):
+        ap.error("--playout-criticality must be a finite number, 0 or more")
+    if args.playout_criticality and not args.playout_prior:
+        ap.error("--playout-criticality is a term of the playout prior: it needs --playout-prior")
     return args
 
 
@@ -291,6 +298,9 @@ def main(argv=None):
         if args.playout_rave:
             more["playout_rave"] = args.playout_rave
             name += f"-rave{args.playout_rave:g}"
+        if args.playout_criticality:
+            more["playout_criticality"] = args.playout_criticality
+            name += f"-crit{args.playout_criticality:g}"
         a = InProcessEngine(NativeGTP(Position(), None if args.playout_prior == 1.0 else pi, None, no_sim=True, time_lim=None,
                                       n_rollouts=args.r, playout_value=args.playout_value, **more),
                             name=args.engine_name or name)

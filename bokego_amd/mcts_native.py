@@ -138,7 +138,9 @@ class NativeMCTS:
     `playout_prior=` (0..1, with playout_value): that share of the priors comes from the playouts' AMAF counts, and with 1.0
     policy_net may be None -- a search without any network (DESIGN 19);
     `playout_rave=k` (> 0, with playout_value): RAVE -- the playouts' two-sided AMAF counts are backed up into per-node tables
-    and blended into the selection with the equivalence parameter k (bk_pool_set_rave); `rave(node)` reads a table."""
+    and blended into the selection with the equivalence parameter k (bk_pool_set_rave; DESIGN 20); `rave(node)` reads a table;
+    `playout_criticality=gamma` (> 0, with playout_prior): gamma times Coulom's criticality of each point, from the final
+    boards of the same playouts (bkt_owner_counts), is added to the AMAF win rates the prior is made of (untuned)."""
 
     def __init__(self, root=None, policy_net=None, value_net=None, **kwargs):
         self.playout_prior = float(kwargs.get("playout_prior") or 0.0)   # 0: the priors are the policy net's alone
@@ -149,6 +151,11 @@ class NativeMCTS:
             raise TypeError("playout_rave reads the playouts of playout_value=N: it needs playout_value")
         if not 0.0 <= self.playout_rave < float("inf"):
             raise ValueError("playout_rave must be a finite number >= 0")
+        self.playout_criticality = float(kwargs.get("playout_criticality") or 0.0)   # 0: the prior is AMAF's alone
+        if self.playout_criticality and not self.playout_prior:
+            raise TypeError("playout_criticality is a term of playout_prior: it needs playout_prior")
+        if not 0.0 <= self.playout_criticality < float("inf"):
+            raise ValueError("playout_criticality must be a finite number >= 0")
         if policy_net is None and kwargs.get("evaluator") is None and self.playout_prior != 1.0:
             raise TypeError("Missing required keywork argument: 'policy_net'")
         self.no_sim = kwargs.get("no_sim", True)
@@ -259,6 +266,8 @@ class NativeMCTS:
             more["tactics"] = self.playout_tactics
         if getattr(self, "playout_rave", 0.0):
             more["rave"] = True
+        if getattr(self, "playout_criticality", 0.0):
+            more["criticality"] = self.playout_criticality
         return rollout.PlayoutEvaluator(get(), self.playout_value, seed=self.playout_seed, rules=self.playout_rules, **more)
 
     def _evaluator_from_nets(self):

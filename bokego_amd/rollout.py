@@ -47,6 +47,14 @@ playout_amaf(sides=2) keeps the opponent's half of every history too (one bkt_am
 PlayoutEvaluator(rave=True) hands those two-sided counts of every row to the tree, whose RAVE tables are made of them
 (bk_pool_deliver_rave, NativeMCTS(playout_rave=k)).  `--amaf --sides 2` prints both sides' heaviest points.
 
+playout_ownership keeps the other thing a playout leaves behind, the final board: one bkt_owner_counts scores the final
+records of every record's n playouts and reduces them, in that launch, to integer counts -- how often each point ended up
+black's, white's and the winner's, the playouts by their margin, black's wins -- without an owner array ever reaching
+memory.  Ownership carries them: the mean ownership map, the mean margin and Coulom's criticality, which
+amaf_prior(criticality=, gamma=) and PlayoutEvaluator(criticality=gamma) can add to the prior (opt-in, untuned).
+
+    python -m bokego_amd.rollout --sgf FILE [--move K] --random --ownership [-n 256]   # the owner board and the critical points
+
 rules="host" is one loop (_playout_host) on the host rules with the same draws (lockstep's play_host, features_batch
 and area_score_host, bk_pos_is_legal, bk_pos_possible_eye, lockstep.sample_host in float64): the reference the tests
 compare the device with.  With engine=None it needs no GPU.
@@ -69,9 +77,10 @@ MOVE_NONE = -2             # BKT_MOVE_NONE; in the history: the game was over be
 SEKI_THRESHOLD = 0.5       # |mean ownership| of a stone's point below this: the stone is in seki (rollout_score)
 POS_BYTES = L.POS_BYTES
 
-__all__ = ["MAX_PLIES", "MOVE_NONE", "Amaf", "Finished", "PlayoutEvaluator", "RolloutScore", "amaf_counts_host",
+__all__ = ["MAX_PLIES", "MOVE_NONE", "Amaf", "Finished", "Ownership", "PlayoutEvaluator", "RolloutScore", "amaf_counts_host",
            "amaf_counts_sides_host", "amaf_prior",
-           "default_counters", "finish_games", "format_score", "owner_board", "owner_host", "playable_host", "playout_amaf",
+           "default_counters", "finish_games", "format_score", "owner_board", "ownership_score", "owner_counts_host", "owner_host",
+           "playable_host", "playout_amaf", "playout_ownership",
            "playout_value", "random_playouts", "record_turns", "rollout_score", "sgf_position"]
 
 
@@ -437,10 +446,15 @@ def _check_playouts(n):
 def _playouts_won_device(recs, n, key, komi, max_plies, table, tactics, history):
     """n playouts of each record of recs (a uint8 [R,192] tensor on the device) -> (won bool [R,n]: the side to move at the
     record won the playout, moves int16 [R * n, max_plies] or None without history), on the device."""
+    return _playouts_final_device(recs, n, key, komi, max_plies, table, tactics, history)[:2]
+
+
+def _playouts_final_device(recs, n, key, komi, max_plies, table, tactics, history):
+    """_playouts_won_device that also hands on the final records -> (won, moves, pos uint8 [R * n, 192])."""
     pos = recs.repeat_interleave(n, 0)                                     # a copy: the caller's records stay
     moves = _play_random_device(pos, key, L.value_counters_device(recs, n), max_plies, history, table, tactics)[2]
     black_wins = _area_score_device(pos, komi, False).view(len(recs), n) > 0
-    return black_wins == L.black_to_move(recs)[:, None], moves
+    return black_wins == L.black_to_move(recs)[:, None], moves, pos
 
 
 def _value_of_wins(w, n):
@@ -457,15 +471,19 @@ def _playout_value_device(recs, n, key, komi, max_plies=MAX_PLIES, table=None, t
     return _value_of_wins(won.sum(1), n)
 
 
-def _playout_amaf_device(recs, n, key, komi, counted=None, max_plies=MAX_PLIES, table=None, tactics=None, sides=1):
+def _playout_amaf_device(recs, n, key, komi, counted=None, max_plies=MAX_PLIES, table=None, tactics=None, sides=1,
+                         owned=0):
     """_playout_value_device's games with their history, and one bkt_amaf_counts over the rows of the first `counted`
     records (default: all) -> (value float32 [R], wins int64 [R], played int32 [counted,81], won int32 [counted,81]) on the
-    device; nothing here waits for it.  sides=2: one bkt_amaf_counts_sides instead, and the counts are [counted,2,81]."""
+    device; nothing here waits for it.  sides=2: one bkt_amaf_counts_sides instead, and the counts are [counted,2,81].
+    owned > 0: a fifth element, T.owner_counts of the final records of the first `owned` records (one bkt_owner_counts)."""
     counted = len(recs) if counted is None else counted
-    won, moves = _playouts_won_device(recs, n, key, komi, max_plies, table, tactics, True)
+    won, moves, pos = _playouts_final_device(recs, n, key, komi, max_plies, table, tactics, True)
     w = won.sum(1)
     reduce = T.amaf_counts if sides == 1 else T.amaf_counts_sides
     played, won_at = reduce(moves[:counted * n], won[:counted].to(torch.uint8).reshape(-1), counted, n)
+    if owned:
+        return _value_of_wins(w, n), w, played, won_at, T.owner_counts(pos[:owned * n], owned, n, komi)
     return _value_of_wins(w, n), w, played, won_at
 
 
@@ -485,12 +503,14 @@ def playout_value(recs, n, seed, rules="device", komi=L.KOMI, device=None, patte
     return _playout_host_wins(recs, n, key, komi, table, tactics, False)[0]
 
 
-def _playout_host_wins(recs, n, key, komi, table, tactics, history):
-    """playout_value on the host mirror -> (value float32 [R], won bool [R,n], moves int16 [R * n, L] or None)."""
+def _playout_host_wins(recs, n, key, komi, table, tactics, history, final=False):
+    """playout_value on the host mirror -> (value float32 [R], won bool [R,n], moves int16 [R * n, L] or None); final=True:
+    and the final records uint8 [R * n, 192]."""
     recs = np.array(_numpy(recs), np.uint8, order="C")
     fin = _random_host(np.repeat(recs, n, 0), key, value_counters(recs, n), MAX_PLIES, komi, history, table, tactics)
     w = (fin.score.reshape(len(recs), n) > 0) == L.black_to_move(recs)[:, None]
-    return ((2 * w.sum(1) - n).astype(np.float32) / np.float32(n)).astype(np.float32), w, fin.moves
+    value = ((2 * w.sum(1) - n).astype(np.float32) / np.float32(n)).astype(np.float32)
+    return (value, w, fin.moves, fin.records) if final else (value, w, fin.moves)
 
 
 class Amaf:
@@ -574,6 +594,103 @@ def playout_amaf(recs, n, seed, rules="device", komi=L.KOMI, device=None, patter
     return Amaf(value, w.sum(1).astype(np.int32), played, won_at, n)
 
 
+class Ownership:
+    """What playout_ownership returns, rows in the order of the records (numpy).
+
+    value       float32 [R]     playout_value's value, bit for bit
+    wins        int32 [R]       the playouts the side to move won: black_wins for a record with black to move, else n - black_wins
+    black       int32 [R,81]    the playouts at whose end the point was black's: a black stone or a black-only empty region
+    white       int32 [R,81]    the same for white
+    agree       int32 [R,81]    the playouts at whose end the point was the winner's
+    hist        int32 [R,163]   the playouts by their margin before komi: bin d + 81, d = black's points - white's
+    black_wins  int32 [R]       the playouts black won (area score > 0)
+    n           int             the playouts per record
+    mean_owner  float64 [R,81]  (black - white) / n: +1 black ... -1 white
+    mean_margin float64 [R]     the mean of d
+    """
+
+    def __init__(self, value, wins, black, white, agree, hist, black_wins, n):
+        self.value, self.wins, self.n = value, wins, int(n)
+        self.black, self.white, self.agree, self.hist, self.black_wins = black, white, agree, hist, black_wins
+
+    @property
+    def mean_owner(self):
+        return (self.black.astype(np.float64) - self.white.astype(np.float64)) / float(self.n)
+
+    @property
+    def mean_margin(self):
+        return (self.hist.astype(np.float64) * np.arange(-81.0, 82.0)).sum(1) / float(self.n)
+
+    def criticality(self):
+        """Coulom's criticality of every point, float64 [R,81]: agree / n - (black / n * black_wins / n + white / n *
+        (1 - black_wins / n)) -- how much more often the point goes to the winner than it would if owning it and winning
+        were independent.  Computed here from the integers: device and host playouts give the same floats."""
+        return criticality_of(self.black, self.white, self.agree, self.black_wins, self.n)
+
+
+def criticality_of(black, white, agree, black_wins, n):
+    """Ownership.criticality from the counts: [R,81] x3 and [R] integers, n playouts -> float64 [R,81]."""
+    n = float(n)
+    pb = (np.asarray(black_wins, np.float64) / n)[:, None]
+    return np.asarray(agree, np.float64) / n - (np.asarray(black, np.float64) / n * pb
+                                                + np.asarray(white, np.float64) / n * (1.0 - pb))
+
+
+def owner_counts_host(final_recs, records, playouts, komi=L.KOMI):
+    """bkt_owner_counts in numpy (include/bokego_train.h has the definition): final_recs uint8 [records * playouts, 192],
+    the final records, rows r * playouts .. of record r -> (black, white, agree int32 [records, 81], hist int32
+    [records, 163], black_wins int32 [records]).  The owner is owner_host's; a row is black's when
+    (float32)B - ((float32)W + komi) > 0 in float32 arithmetic, bkt_area_score's expression."""
+    records, playouts = int(records), int(playouts)
+    recs = np.asarray(_numpy(final_recs))
+    if records < 1 or playouts < 1 or recs.ndim != 2 or recs.shape != (records * playouts, POS_BYTES) or recs.dtype != np.uint8:
+        raise ValueError(f"final_recs must be uint8 [{records} * {playouts}, {POS_BYTES}]")
+    if not np.isfinite(np.float32(komi)):
+        raise ValueError("komi must be finite")
+    own = owner_host(recs)
+    isb, isw = own > 0, own < 0
+    B, W = isb.sum(1), isw.sum(1)
+    bw = (B.astype(np.float32) - (W.astype(np.float32) + np.float32(komi))) > 0
+    agree = (isb & bw[:, None]) | (isw & ~bw[:, None])
+    black, white, agree = (x.reshape(records, playouts, 81).sum(1).astype(np.int32) for x in (isb, isw, agree))
+    hist = np.zeros((records, 163), np.int32)
+    np.add.at(hist, (np.repeat(np.arange(records), playouts), B - W + 81), 1)
+    return black, white, agree, hist, bw.reshape(records, playouts).sum(1).astype(np.int32)
+
+
+def _playout_ownership_device(recs, n, key, komi, max_plies=MAX_PLIES, table=None, tactics=None):
+    """recs: a uint8 [R,192] tensor on the device -> (value float32 [R], wins int64 [R], black, white, agree, hist,
+    black_wins) on the device: the playout launch without history and one bkt_owner_counts on the final records -- no
+    bkt_area_score, no owner array; nothing here waits for the device."""
+    pos = recs.repeat_interleave(n, 0)                                     # a copy: the caller's records stay
+    _play_random_device(pos, key, L.value_counters_device(recs, n), max_plies, False, table, tactics)
+    counts = T.owner_counts(pos, len(recs), n, komi)
+    bw = counts[4].to(torch.int64)
+    w = torch.where(L.black_to_move(recs), bw, n - bw)
+    return (_value_of_wins(w, n), w, *counts)
+
+
+def playout_ownership(recs, n, seed, rules="device", komi=L.KOMI, device=None, patterns=None, tactics=None):
+    """playout_value's n playouts of each record -- the same counters, draws and cap -- with what their final boards tell
+    -> Ownership: the value (the same bits), the wins, and the ownership, agreement and margin counts of every record
+    (owner_counts_host has the definition).  rules="device": the playout launch without history and one bkt_owner_counts;
+    rules="host": the mirror end to end, the same integers.  recs, patterns, tactics: as playout_value."""
+    L.check_rules(rules)
+    table, tactics = _table(patterns), _tactics(tactics)
+    n = _check_playouts(n)
+    _check_records(recs)
+    key = L.seed_u64(seed)
+    if rules == "device":
+        t = L.records_to_device(recs, _device(device, None, recs), clone=False)
+        value, w, *counts = _playout_ownership_device(t, n, key, komi, table=table, tactics=tactics)
+        return Ownership(value.cpu().numpy(), w.cpu().numpy().astype(np.int32), *(c.cpu().numpy() for c in counts), n)
+    recs = np.array(_numpy(recs), np.uint8, order="C")
+    final = _playout_host_wins(recs, n, key, komi, table, tactics, False, final=True)[3]
+    counts = owner_counts_host(final, len(recs), n, komi)
+    w = np.where(L.black_to_move(recs), counts[4], n - counts[4]).astype(np.int32)
+    return Ownership(((2 * w - n).astype(np.float32) / np.float32(n)).astype(np.float32), w, *counts, n)
+
+
 PRIOR_K = 4.0              # amaf_prior's defaults: plausible, and not tuned (DESIGN 19)
 PRIOR_TEMPERATURE = 0.1
 
@@ -589,16 +706,21 @@ def legal_host(recs):
     return out
 
 
-def amaf_prior(recs, amaf, k=PRIOR_K, temperature=PRIOR_TEMPERATURE):
+def amaf_prior(recs, amaf, k=PRIOR_K, temperature=PRIOR_TEMPERATURE, criticality=None, gamma=0.0):
     """A search prior from the counts of playout_amaf(recs, ...) -> float32 [R,81], computed on the host in float64 from the
     integers, so that device and host playouts give the same floats.  With wbar = wins / n, the win rate of all n playouts,
         q_s = (won_s + k * wbar) / (played_s + k)      the AMAF win rate of the point, k playouts' worth of wbar mixed in,
         p_s = exp((q_s - max q over the legal points) / temperature) on the legal points (bk_pos_legal_moves), 0 elsewhere,
     each row divided by its sum; a record without a legal point gets 1/81 everywhere.  k and temperature must be > 0; their
-    defaults, 4.0 and 0.1, are plausible and untuned.  Two-sided counts ([R,2,81], playout_amaf(sides=2)) are read at side 0."""
-    k, temperature = float(k), float(temperature)
+    defaults, 4.0 and 0.1, are plausible and untuned.  Two-sided counts ([R,2,81], playout_amaf(sides=2)) are read at side 0.
+    criticality (float64 [R,81], Ownership.criticality()) with gamma > 0: q_s + gamma * criticality_s takes the place of q_s
+    (gamma is untuned).  criticality=None or gamma == 0: the floats above, bit for bit.  gamma must be finite and
+    not negative."""
+    k, temperature, gamma = float(k), float(temperature), float(gamma)
     if not k > 0 or not temperature > 0:
         raise ValueError("k and temperature must be greater than 0")
+    if not 0.0 <= gamma < float("inf"):
+        raise ValueError("gamma must be finite and not negative")
     recs = np.array(_numpy(recs), np.uint8, order="C")
     _check_records(recs)
     played, won = np.asarray(amaf.played, np.float64), np.asarray(amaf.won, np.float64)
@@ -608,6 +730,11 @@ def amaf_prior(recs, amaf, k=PRIOR_K, temperature=PRIOR_TEMPERATURE):
         raise ValueError(f"the counts must be [{len(recs)}, 81] or [{len(recs)}, 2, 81], one row per record")
     wbar = np.asarray(amaf.wins, np.float64) / float(amaf.n)
     q = (won + k * wbar[:, None]) / (played + k)
+    if criticality is not None and gamma > 0.0:
+        crit = np.asarray(criticality, np.float64)
+        if crit.shape != q.shape:
+            raise ValueError(f"criticality must be [{len(recs)}, 81], one row per record")
+        q = q + gamma * crit
     legal = legal_host(recs)
     top = np.where(legal, q, -np.inf).max(1, keepdims=True)
     some = legal.any(1)
@@ -632,14 +759,23 @@ class PlayoutEvaluator:
     third element, records = (playouts, wins int32 [B], played int32 [B,2,81], won_at int32 [B,2,81]), which
     selfplay.GamePool.deliver hands to the tree's RAVE tables; the prior, when prior > 0, reads side 0 of the first
     n_policy rows of the same counts -- one reduction launch, not two.  Probs and values are what they are without it.
+    criticality (gamma >= 0, default 0: exactly the above, the same launches; it needs prior > 0): the playouts keep their
+    final records, one bkt_owner_counts over the first n_policy rows gives their Ownership counts, and amaf_prior gets
+    criticality = Coulom's criticality of every point and gamma (untuned).  The values of all rows and, with
+    rave=True, the records are what they are without it.
     The engine is kept as `policy_engine`, not `engine`: selfplay.run_pools_native hands an evaluator's `engine` to the C
     step loop as its own bk_evaluator, which would compute no playouts -- this class goes through callback_evaluator."""
     wants_positions = True
 
     def __init__(self, engine, playouts=64, seed=0, rules="device", komi=L.KOMI, patterns=None, tactics=None, prior=0.0,
-                 prior_k=PRIOR_K, prior_temperature=PRIOR_TEMPERATURE, rave=False):
+                 prior_k=PRIOR_K, prior_temperature=PRIOR_TEMPERATURE, rave=False, criticality=0.0):
         L.check_rules(rules)
         self.rave = bool(rave)
+        self.criticality = float(criticality)
+        if not 0.0 <= self.criticality < float("inf"):
+            raise ValueError("criticality must be finite and not negative")
+        if self.criticality > 0.0 and not float(prior) > 0.0:
+            raise ValueError("criticality is a term of the playout prior: it needs prior > 0")
         self.patterns = _table(patterns)                                  # None: uniformly random playouts
         self.tactics = _tactics(tactics)                                  # None: no tactical weights (DESIGN 18)
         self.prior = float(prior)
@@ -667,25 +803,32 @@ class PlayoutEvaluator:
             ticket = self.policy_engine.submit_positions(recs[:n_policy], logits=False, probs=True, value=False,
                                                          n_policy=n_policy)
         more = dict(komi=self.komi, table=self.patterns, tactics=self.tactics)
+        owned = n_policy if n_policy and self.criticality > 0.0 else 0   # rows whose final boards are counted (then prior > 0)
+        final = ()                                                        # (the host's final records, when they are counted)
         if self.rave:                                                     # every row with its history, both sides counted
             if self.rules == "host":
-                values, w, moves = _playout_host_wins(recs, self.playouts, self.seed, history=True, **more)
+                values, w, moves, *final = _playout_host_wins(recs, self.playouts, self.seed, history=True,
+                                                              final=bool(owned), **more)
                 counts = amaf_counts_sides_host(moves, w.reshape(-1), len(recs), self.playouts)
                 w = w.sum(1)
             else:
                 t = torch.from_numpy(recs).to(_device(None, self.policy_engine))
-                values, w, *counts = _playout_amaf_device(t, self.playouts, self.seed, sides=2, **more)
+                values, w, *counts = _playout_amaf_device(t, self.playouts, self.seed, sides=2, owned=owned, **more)
             counted = (recs[:n_policy], n_policy) if n_policy and self.prior > 0.0 else None
-            return ticket, values, counted, (w, *counts)
+            if owned:
+                counted += (self._owned(final, counts, owned),)
+            return ticket, values, counted, (w, *counts[:2])
         if n_policy and self.prior > 0.0:                                 # the playouts with their history, and the counts
             if self.rules == "host":
-                values, w, moves = _playout_host_wins(recs, self.playouts, self.seed, history=True, **more)
+                values, w, moves, *final = _playout_host_wins(recs, self.playouts, self.seed, history=True,
+                                                              final=bool(owned), **more)
                 counts = amaf_counts_host(moves[:n_policy * self.playouts], w[:n_policy].reshape(-1), n_policy, self.playouts)
                 w = w.sum(1)
             else:
                 t = torch.from_numpy(recs).to(_device(None, self.policy_engine))
-                values, w, *counts = _playout_amaf_device(t, self.playouts, self.seed, counted=n_policy, **more)
-            return ticket, values, (recs[:n_policy], w[:n_policy], *counts)
+                values, w, *counts = _playout_amaf_device(t, self.playouts, self.seed, counted=n_policy, owned=owned, **more)
+            counted = (recs[:n_policy], w[:n_policy], *counts[:2])
+            return ticket, values, counted + ((self._owned(final, counts, owned),) if owned else ())
         if self.rules == "host":
             values = _playout_host_wins(recs, self.playouts, self.seed, history=False, **more)[0]
         else:
@@ -693,8 +836,18 @@ class PlayoutEvaluator:
                                            self.seed, **more)
         return ticket, values, None
 
+    def _owned(self, final, counts, owned):
+        """The owner counts of the first `owned` rows: from the host's final records, or the fifth element of
+        _playout_amaf_device's result."""
+        if self.rules == "host":
+            return owner_counts_host(final[0][:owned * self.playouts], owned, self.playouts, self.komi)
+        return counts[2]
+
     def finish(self, handle, normalise=None):
         ticket, values, counted, *rave = handle
+        owned = None
+        if counted is not None and self.criticality > 0.0:               # the last element: the owner counts
+            counted, owned = counted[:-1], [_numpy(x) for x in counted[-1]]
         if normalise is None:
             from .selfplay import normalise_like_categorical as normalise
         probs = np.zeros((0, 81), np.float32) if ticket is None else self.policy_engine.wait(ticket)["probs"]
@@ -706,7 +859,9 @@ class PlayoutEvaluator:
                 counted = (counted[0], w[:counted[1]], played[:counted[1]], won[:counted[1]])
         if counted is not None:
             recs, w, played, won = (_numpy(x) for x in counted)
-            prior = amaf_prior(recs, Amaf(None, w, played, won, self.playouts), self.prior_k, self.prior_temperature)
+            crit = None if owned is None else criticality_of(owned[0], owned[1], owned[2], owned[4], self.playouts)
+            prior = amaf_prior(recs, Amaf(None, w, played, won, self.playouts), self.prior_k, self.prior_temperature,
+                               criticality=crit, gamma=self.criticality)
             if ticket is not None:
                 prior = ((1.0 - self.prior) * probs.astype(np.float64) + self.prior * prior.astype(np.float64))
             probs = prior.astype(np.float32)
@@ -768,20 +923,36 @@ def rollout_score(positions, engine, n=256, seed=0, komi=L.KOMI, rules="device",
     score = fin.score.reshape(P, n).astype(np.float64)
     out = []
     for i in range(P):
-        r = RolloutScore()
-        r.mean_owner = owner[i]
-        r.black_win = float((score[i] > 0).mean())
-        r.mean_score = float(score[i].mean())
-        r.score = float((owner[i] > 0).sum()) - (float((owner[i] < 0).sum()) + float(komi))
-        board = recs[i, :81].view(np.int8)
-        r.status = [None] * 81
-        for s in np.nonzero(board)[0].tolist():
-            sign = 1.0 if board[s] == 1 else -1.0
-            m = owner[i, s]
-            r.status[s] = "seki" if abs(m) < SEKI_THRESHOLD else ("alive" if m * sign > 0 else "dead")
+        r = _score_of_owner(recs[i], owner[i], float((score[i] > 0).mean()), float(score[i].mean()), komi)
         r.unfinished = int((~fin.over.reshape(P, n)[i]).sum())
         out.append(r)
     return out
+
+
+def _score_of_owner(rec, mean_owner, black_win, mean_score, komi):
+    """A RolloutScore (without `unfinished`) from a record's mean ownership: the area by majority ownership and the status of
+    every stone, seki where |mean ownership| is below SEKI_THRESHOLD."""
+    r = RolloutScore()
+    r.mean_owner, r.black_win, r.mean_score = mean_owner, black_win, mean_score
+    r.score = float((mean_owner > 0).sum()) - (float((mean_owner < 0).sum()) + float(komi))
+    board = rec[:81].view(np.int8)
+    r.status = [None] * 81
+    for s in np.nonzero(board)[0].tolist():
+        sign = 1.0 if board[s] == 1 else -1.0
+        m = mean_owner[s]
+        r.status[s] = "seki" if abs(m) < SEKI_THRESHOLD else ("alive" if m * sign > 0 else "dead")
+    return r
+
+
+def ownership_score(positions, n, seed, komi=L.KOMI, **kw):
+    """rollout_score's score and status rules on playout_ownership's counts -> a list of RolloutScore (mean_score: the mean
+    margin less komi; no `unfinished`).  positions: go.Game objects or uint8 [P,192] records; kw: playout_ownership's rules,
+    device, patterns and tactics.  No network and no owner array: what the net-free GTP engine scores its games with."""
+    recs = _as_records(positions)
+    o = playout_ownership(recs, n, seed, komi=komi, **kw)
+    owner, margin = o.mean_owner, o.mean_margin
+    return [_score_of_owner(recs[i], owner[i], float(o.black_wins[i]) / o.n, float(margin[i]) - float(komi), komi)
+            for i in range(len(recs))]
 
 
 def format_score(score):
@@ -817,6 +988,8 @@ def _parse(argv):
                     help="with --random: multiply the weights by the tactical weights of this table (python -m bokego_amd.tactics fit)")
     ap.add_argument("--amaf", action="store_true",
                     help="with --random: print the Monte-Carlo value and the ten heaviest moves of the AMAF prior instead of the score")
+    ap.add_argument("--ownership", action="store_true",
+                    help="with --random: print the ownership map, the mean margin and the ten most critical points instead of the score")
     ap.add_argument("--sides", type=int, default=1, choices=(1, 2),
                     help="with --amaf: 2 also prints the opponent's heaviest points (the two-sided counts RAVE is fed with)")
     ap.add_argument("-n", dest="n", type=int, default=256, help="playouts")
@@ -826,6 +999,8 @@ def _parse(argv):
     args = ap.parse_args(argv)
     if args.amaf and not args.random:
         ap.error("--amaf reads the one-launch playouts: it needs --random")
+    if args.ownership and (not args.random or args.amaf):
+        ap.error("--ownership reads the one-launch playouts: it needs --random, and not --amaf")
     if args.sides != 1 and not args.amaf:
         ap.error("--sides goes with --amaf")
     if args.n < 1:
@@ -872,6 +1047,17 @@ def main(argv=None):
             out["opponent"] = [{"move": go.unsquash(s), "played": int(a.played[0, 1, s]), "won": int(a.won[0, 1, s])}
                                for s in np.argsort(-a.played[0, 1], kind="stable")[:10].tolist()]
         print(json.dumps(out))
+        return
+    if args.ownership:
+        o = playout_ownership(_as_records(game), args.n, args.seed, komi=args.komi, device=torch.device("cuda", args.device),
+                              patterns=args.patterns, tactics=args.tactics)
+        crit = o.criticality()[0]
+        print(json.dumps({"value": float(o.value[0]), "black_wins": int(o.black_wins[0]), "playouts": args.n,
+                          "mean_margin": float(o.mean_margin[0]),
+                          "critical": [{"move": go.unsquash(s), "criticality": float(crit[s]),
+                                        "owner": float(o.mean_owner[0, s])}
+                                       for s in np.argsort(-crit, kind="stable")[:10].tolist()]}))
+        print(owner_board(o.mean_owner[0]))
         return
     eng = None
     if args.p is not None:

@@ -867,6 +867,9 @@ def parse_args(argv=None):
                     help="with --playout-value: the table of 3x3 pattern weights its playouts draw their moves by")
     ap.add_argument("--playout-tactics", default=None, metavar="FILE",
                     help="with --playout-value: the table of tactical weights that multiply its playouts' weights")
+    ap.add_argument("--playout-criticality", type=float, default=0.0, metavar="GAMMA",
+                    help="with --playout-prior: GAMMA times Coulom's criticality of each point is added to the AMAF win rates of the "
+                         "prior (untuned; default 0: off)")
     args = ap.parse_args(argv)
     if args.playout_value < 0:
         ap.error("--playout-value must not be negative")
@@ -880,6 +883,10 @@ def parse_args(argv=None):
                         ("--playout-tactics", args.playout_tactics is not None)):
         if given and not args.playout_value:
             ap.error(f"{flag} goes with the playouts of --playout-value: it needs --playout-value N")
+    if not 0.0 <= args.playout_criticality < float("inf"):
+        ap.error("--playout-criticality must be a finite number, 0 or more")
+    if args.playout_criticality and not args.playout_prior:
+        ap.error("--playout-criticality is a term of the playout prior: it needs --playout-prior")
     if args.playout_prior == 1.0 and args.policy is not None:
         ap.error("--playout-prior 1 searches without a policy net: not allowed with --policy")
     return args
@@ -923,7 +930,7 @@ def main(argv=None):
             eng = LeafEngine(load(args.policy, "policy_19.bkw"), None, device_id=local_rank, max_batch=args.max_batch,
                              precision=args.precision)
         ev = PlayoutEvaluator(eng, args.playout_value, patterns=args.playout_patterns, tactics=args.playout_tactics,
-                              prior=args.playout_prior)
+                              prior=args.playout_prior, criticality=args.playout_criticality)
     else:
         eng = LeafEngine(load(args.policy, "policy_19.bkw"), load(args.value, "value_synth.bkw"), device_id=local_rank,
                          max_batch=args.max_batch, precision=args.precision)

@@ -293,6 +293,25 @@ int bkt_amaf_counts(const int16_t *moves, int max_plies, const uint8_t *won, int
 int bkt_amaf_counts_sides(const int16_t *moves, int max_plies, const uint8_t *won, int records, int playouts,
                           int32_t *played, int32_t *won_at, void *stream);
 
+/* What the final boards of whole playouts say beyond who won (bokego_amd/rollout.py playout_ownership): the
+ * ownership, agreement and score-margin counts of every record's playouts, scored and reduced in one launch.
+ * pos holds records * playouts final 192-byte records (bk_pos), read only; rows r * playouts .. (r + 1) * playouts - 1
+ * belong to record r (the layout of the three bkt_*_playouts calls' callers).  Board bytes are 0, 1 (black), 2 (white).
+ * Per row: own[s] is exactly the owner bkt_area_score defines -- +1 for a black stone or a black-only empty region, -1 for
+ * white, 0 otherwise;  B = #(own == +1), W = #(own == -1);  bw = ((float)B - ((float)W + komi)) > 0, bkt_area_score's
+ * expression, so the row wins here if and only if its score > 0 there;  d = B - W.
+ * Per record r, from zero:
+ *   black[r * 81 + s] += (own[s] == +1),   white[r * 81 + s] += (own[s] == -1),
+ *   agree[r * 81 + s] += (own[s] == +1 && bw) || (own[s] == -1 && !bw)     the point ended up with the row's winner,
+ *   hist[r * 163 + d + 81] += 1            the margin before komi, d in -81 .. 81,
+ *   black_wins[r] += bw.
+ * Every entry of black, white, agree [records, 81], hist [records, 163] and black_wins [records] is written, zeros
+ * included.  Integers only: the counts do not depend on any order.
+ * No pointer but stream may be NULL; records >= 1, playouts >= 1, records * playouts <= BKT_MAX_SAMPLE_ROWS; komi must be
+ * finite; else BKT_ERR_ARG, nothing is launched and nothing written. */
+int bkt_owner_counts(const void *pos, int records, int playouts, float komi, int32_t *black, int32_t *white,
+                     int32_t *agree, int32_t *hist, int32_t *black_wins, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
