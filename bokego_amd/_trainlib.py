@@ -52,6 +52,7 @@ SYMBOLS = {
     "bkt_amaf_counts": (_I, [_P, _I, _P, _I, _I, _P, _P, _P]),
     "bkt_amaf_counts_sides": (_I, [_P, _I, _P, _I, _I, _P, _P, _P]),
     "bkt_owner_counts": (_I, [_P, _I, _I, _F, _P, _P, _P, _P, _P, _P]),
+    "bkt_move_weights": (_I, [_P, _I, _P, _P, _P, _P]),
 }
 MAX_BATCH = 65536          # BKT_MAX_BATCH
 PRECISIONS = ("fp32", "bf16")
@@ -496,3 +497,20 @@ def owner_counts(pos, records, playouts, komi=5.5):
                                    _dev(agree, "agree", dtype=torch.int32), _dev(hist, "hist", dtype=torch.int32),
                                    _dev(black_wins, "black_wins", dtype=torch.int32), _stream(pos)), "bkt_owner_counts")
     return black, white, agree, hist, black_wins
+
+
+def move_weights(pos, table=None, tactics=None):
+    """The move weights of every record in one launch (bkt_move_weights; include/bokego_train.h has the definition): pos
+    uint8 [B,192] (read only); table: None or pattern_playouts' table; tactics: None or tactical_playouts' table
+    -> int32 [B,81]: the weight tactical_playouts' draw gives the point at the first ply from the record (below 2^24), 0
+    where the point is not playable."""
+    B = _pos_batch(pos)
+    if (table is not None and (not isinstance(table, torch.Tensor) or table.device != pos.device)) or \
+            (tactics is not None and (not isinstance(tactics, torch.Tensor) or tactics.device != pos.device)):
+        raise ValueError("the pattern table and the tactics table must be on the device of pos")
+    weights = torch.empty((B, 81), dtype=torch.int32, device=pos.device)
+    _check(load().bkt_move_weights(_dev(pos, "pos", dtype=torch.uint8), B,
+                                   None if table is None else _dev(table, "table", (PATTERN_ENTRIES,), torch.int16),
+                                   None if tactics is None else _dev(tactics, "tactics", (TACTIC_ENTRIES,), torch.int16),
+                                   _dev(weights, "weights", dtype=torch.int32), _stream(pos)), "bkt_move_weights")
+    return weights

@@ -21,7 +21,8 @@ needs the HIP engine as `--rollout-score` does.  `--playout-patterns FILE` (with
 moves in proportion to the 3x3 pattern weights of a table fitted by `python -m bokego_amd.patterns fit` (DESIGN 17);
 `--playout-tactics FILE` (with `--playout-value`) multiplies them by the capture / escape / atari weights of a table fitted
 by `python -m bokego_amd.tactics fit`.  `--playout-criticality GAMMA` (with `--playout-prior`) adds Coulom's
-criticality to the playout prior.  With `--playout-value`, `--rollout-score N` scores by N playouts of the
+criticality to the playout prior.  `--playout-pattern-prior MU [--prior-patterns FILE]
+[--prior-tactics FILE]` (with `--playout-prior`) adds MU times the log of the playouts' move weights to it.  With `--playout-value`, `--rollout-score N` scores by N playouts of the
 search's own kind (rollout.ownership_score): the engine without any network scores its own games.
 """
 import argparse
@@ -486,6 +487,14 @@ def build_parser():
     ap.add_argument("--playout-criticality", type=float, default=0.0, metavar="GAMMA",
                     help="with --playout-prior: add GAMMA times Coulom's criticality of each point, from the final boards of the "
                          "same playouts, to the AMAF win rates the prior is made of (untuned; default 0: off, DESIGN 21)")
+    ap.add_argument("--playout-pattern-prior", type=float, default=0.0, metavar="MU",
+                    help="with --playout-prior: add MU times the log of each point's move weight -- the playouts' pattern and "
+                         "tactical tables, or --prior-patterns / --prior-tactics -- to the prior's logits (untuned; default 0: "
+                         "off, DESIGN 22)")
+    ap.add_argument("--prior-patterns", default=None, metavar="FILE",
+                    help="with --playout-pattern-prior: the pattern table of that term (default: --playout-patterns)")
+    ap.add_argument("--prior-tactics", default=None, metavar="FILE",
+                    help="with --playout-pattern-prior: the tactics table of that term (default: --playout-tactics)")
     ap.add_argument("--python-tree", action="store_true", help="search with the Python tree instead of the native one")
     ap.set_defaults(v_given=False)
     return ap
@@ -527,6 +536,17 @@ def parse_args(argv=None):
         ap.error("--playout-criticality must be a finite number, 0 or more")
     if args.playout_criticality and not args.playout_prior:
         ap.error("--playout-criticality is a term of the playout prior: it needs --playout-prior")
+    if not 0.0 <= args.playout_pattern_prior < float("inf"):
+        ap.error("--playout-pattern-prior must be a finite number, 0 or more")
+    if args.playout_pattern_prior and not args.playout_prior:
+        ap.error("--playout-pattern-prior is a term of the playout prior: it needs --playout-prior")
+    for flag, given in (("--prior-patterns", args.prior_patterns), ("--prior-tactics", args.prior_tactics)):
+        if given is not None and not args.playout_pattern_prior:
+            ap.error(f"{flag} is the table of --playout-pattern-prior: it needs --playout-pattern-prior MU")
+    if args.playout_pattern_prior and all(t is None for t in (args.playout_patterns, args.playout_tactics,
+                                                              args.prior_patterns, args.prior_tactics)):
+        ap.error("--playout-pattern-prior needs a table: --playout-patterns, --playout-tactics, --prior-patterns or "
+                 "--prior-tactics")
     return args
 
 
@@ -555,6 +575,9 @@ def main(argv=None):
         more["playout_rave"] = args.playout_rave
     if args.playout_criticality:
         more["playout_criticality"] = args.playout_criticality
+    if args.playout_pattern_prior:
+        more.update(playout_pattern_prior=args.playout_pattern_prior, prior_patterns=args.prior_patterns,
+                    prior_tactics=args.prior_tactics)
     gtp = cls(root, pi, val, no_sim=not args.simulate, time_lim=None if args.r else args.t, n_rollouts=args.r, pondering=args.ponder,
               rollout_score=args.rollout_score, **more)
     gtp.start()

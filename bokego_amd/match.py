@@ -243,6 +243,14 @@ def parse_args(argv=None):
     ap.add_argument("--playout-criticality", type=float, default=0.0, metavar="GAMMA",
                     help="with --playout-prior: GAMMA times Coulom's criticality of each point is added to the AMAF win rates of its "
                          "prior (untuned; default 0: off, DESIGN 21)")
+    ap.add_argument("--playout-pattern-prior", type=float, default=0.0, metavar="MU",
+                    help="with --playout-prior: add MU times the log of each point's move weight -- the playouts' pattern and "
+                         "tactical tables, or --prior-patterns / --prior-tactics -- to the prior's logits (untuned; default 0: "
+                         "off, DESIGN 22)")
+    ap.add_argument("--prior-patterns", default=None, metavar="FILE",
+                    help="with --playout-pattern-prior: the pattern table of that term (default: --playout-patterns)")
+    ap.add_argument("--prior-tactics", default=None, metavar="FILE",
+                    help="with --playout-pattern-prior: the tactics table of that term (default: --playout-tactics)")
     ap.add_argument("--opponent", default="policy", help='"policy" (raw policy, no search) or a GTP command line')
     ap.add_argument("--komi", type=float, default=5.5)
     ap.add_argument("--sgf", default=None, help="prefix for SGF records")
@@ -275,6 +283,17 @@ def parse_args(argv=None):
         ap.error("--playout-criticality must be a finite number, 0 or more")
     if args.playout_criticality and not args.playout_prior:
         ap.error("--playout-criticality is a term of the playout prior: it needs --playout-prior")
+    if not 0.0 <= args.playout_pattern_prior < float("inf"):
+        ap.error("--playout-pattern-prior must be a finite number, 0 or more")
+    if args.playout_pattern_prior and not args.playout_prior:
+        ap.error("--playout-pattern-prior is a term of the playout prior: it needs --playout-prior")
+    for flag, given in (("--prior-patterns", args.prior_patterns), ("--prior-tactics", args.prior_tactics)):
+        if given is not None and not args.playout_pattern_prior:
+            ap.error(f"{flag} is the table of --playout-pattern-prior: it needs --playout-pattern-prior MU")
+    if args.playout_pattern_prior and all(t is None for t in (args.playout_patterns, args.playout_tactics,
+                                                              args.prior_patterns, args.prior_tactics)):
+        ap.error("--playout-pattern-prior needs a table: --playout-patterns, --playout-tactics, --prior-patterns or "
+                 "--prior-tactics")
     return args
 
 
@@ -301,6 +320,10 @@ def main(argv=None):
         if args.playout_criticality:
             more["playout_criticality"] = args.playout_criticality
             name += f"-crit{args.playout_criticality:g}"
+        if args.playout_pattern_prior:
+            more.update(playout_pattern_prior=args.playout_pattern_prior, prior_patterns=args.prior_patterns,
+                        prior_tactics=args.prior_tactics)
+            name += f"-pp{args.playout_pattern_prior:g}"
         a = InProcessEngine(NativeGTP(Position(), None if args.playout_prior == 1.0 else pi, None, no_sim=True, time_lim=None,
                                       n_rollouts=args.r, playout_value=args.playout_value, **more),
                             name=args.engine_name or name)

@@ -140,7 +140,10 @@ class NativeMCTS:
     `playout_rave=k` (> 0, with playout_value): RAVE -- the playouts' two-sided AMAF counts are backed up into per-node tables
     and blended into the selection with the equivalence parameter k (bk_pool_set_rave; DESIGN 20); `rave(node)` reads a table;
     `playout_criticality=gamma` (> 0, with playout_prior): gamma times Coulom's criticality of each point, from the final
-    boards of the same playouts (bkt_owner_counts), is added to the AMAF win rates the prior is made of (untuned)."""
+    boards of the same playouts (bkt_owner_counts), is added to the AMAF win rates the prior is made of (DESIGN 21; untuned);
+    `playout_pattern_prior=mu` (> 0, with playout_prior): mu times the log of each point's move weight -- the playouts' own
+    pattern and tactical tables, or `prior_patterns=` / `prior_tactics=` in their place (bkt_move_weights) -- is added to the
+    prior's logits (untuned)."""
 
     def __init__(self, root=None, policy_net=None, value_net=None, **kwargs):
         self.playout_prior = float(kwargs.get("playout_prior") or 0.0)   # 0: the priors are the policy net's alone
@@ -156,6 +159,14 @@ class NativeMCTS:
             raise TypeError("playout_criticality is a term of playout_prior: it needs playout_prior")
         if not 0.0 <= self.playout_criticality < float("inf"):
             raise ValueError("playout_criticality must be a finite number >= 0")
+        self.playout_pattern_prior = float(kwargs.get("playout_pattern_prior") or 0.0)   # 0: no pattern term in the prior
+        self.prior_patterns, self.prior_tactics = kwargs.get("prior_patterns"), kwargs.get("prior_tactics")
+        if (self.playout_pattern_prior or self.prior_patterns is not None or self.prior_tactics is not None) \
+                and not self.playout_prior:
+            raise TypeError("playout_pattern_prior, prior_patterns and prior_tactics are terms of playout_prior: they need "
+                            "playout_prior")
+        if not 0.0 <= self.playout_pattern_prior < float("inf"):
+            raise ValueError("playout_pattern_prior must be a finite number >= 0")
         if policy_net is None and kwargs.get("evaluator") is None and self.playout_prior != 1.0:
             raise TypeError("Missing required keywork argument: 'policy_net'")
         self.no_sim = kwargs.get("no_sim", True)
@@ -268,6 +279,9 @@ class NativeMCTS:
             more["rave"] = True
         if getattr(self, "playout_criticality", 0.0):
             more["criticality"] = self.playout_criticality
+        if getattr(self, "playout_pattern_prior", 0.0):
+            more.update(pattern_prior=self.playout_pattern_prior, prior_patterns=self.prior_patterns,
+                        prior_tactics=self.prior_tactics)
         return rollout.PlayoutEvaluator(get(), self.playout_value, seed=self.playout_seed, rules=self.playout_rules, **more)
 
     def _evaluator_from_nets(self):

@@ -55,6 +55,13 @@ amaf_prior(criticality=, gamma=) and PlayoutEvaluator(criticality=gamma) can add
 
     python -m bokego_amd.rollout --sgf FILE [--move K] --random --ownership [-n 256]   # the owner board and the critical points
 
+move_weights asks the playouts' move predictor itself: the weight the tactical draw gives every point of a record at the
+first ply, in one launch (bkt_move_weights).  pattern_prior is that table's own prediction, and
+amaf_prior(weights=, mu=) and PlayoutEvaluator(pattern_prior=mu) add mu * ln(weight) to the prior's logits -- Coulom's
+pattern ratings, or progressive bias, seeding a new node (opt-in, untuned).
+
+    python -m bokego_amd.rollout --sgf FILE [--move K] --random --weights [--patterns FILE] [--tactics FILE]   # the ten heaviest points
+
 rules="host" is one loop (_playout_host) on the host rules with the same draws (lockstep's play_host, features_batch
 and area_score_host, bk_pos_is_legal, bk_pos_possible_eye, lockstep.sample_host in float64): the reference the tests
 compare the device with.  With engine=None it needs no GPU.
@@ -79,7 +86,8 @@ POS_BYTES = L.POS_BYTES
 
 __all__ = ["MAX_PLIES", "MOVE_NONE", "Amaf", "Finished", "Ownership", "PlayoutEvaluator", "RolloutScore", "amaf_counts_host",
            "amaf_counts_sides_host", "amaf_prior",
-           "default_counters", "finish_games", "format_score", "owner_board", "ownership_score", "owner_counts_host", "owner_host",
+           "default_counters", "finish_games", "format_score", "move_weights", "move_weights_host", "owner_board",
+           "ownership_score", "owner_counts_host", "owner_host", "pattern_prior",
            "playable_host", "playout_amaf", "playout_ownership",
            "playout_value", "random_playouts", "record_turns", "rollout_score", "sgf_position"]
 
@@ -706,7 +714,75 @@ def legal_host(recs):
     return out
 
 
-def amaf_prior(recs, amaf, k=PRIOR_K, temperature=PRIOR_TEMPERATURE, criticality=None, gamma=0.0):
+def move_weights_host(recs, patterns=None, tactics=None):
+    """bkt_move_weights in numpy (include/bokego_train.h has the definition): recs uint8 [R,192] (not modified); patterns,
+    tactics: as random_playouts, None for none -> int32 [R,81]: tactics.combine of the pattern table's entries at
+    patterns.codes_host and the tactics table's at tactics.codes_host on playable_host, 0 elsewhere."""
+    from . import patterns as PT
+    from . import tactics as TC
+    table, tactics = _table(patterns), _tactics(tactics)
+    recs = np.array(_numpy(recs), np.uint8, order="C")
+    _check_records(recs)
+    ok = playable_host(recs)
+    entries = None if table is None else table.entries(PT.codes_host(recs))
+    t = np.full(ok.shape, TC.NEUTRAL, np.uint16) if tactics is None else tactics.entries(TC.codes_host(recs))
+    return np.where(ok, TC.combine(entries, t), 0).astype(np.int32)
+
+
+def move_weights(recs, patterns=None, tactics=None, rules="device", device=None):
+    """The weight the playouts' draw gives every point of every record at the first ply, 0 where the point is not playable
+    -> int32 [R,81] (numpy).  rules="device": one bkt_move_weights launch per T.MAX_BATCH records; rules="host":
+    move_weights_host, the same integers without a GPU.  recs, patterns, tactics: as playout_value."""
+    L.check_rules(rules)
+    if rules == "host":
+        return move_weights_host(recs, patterns, tactics)
+    table, tactics = _table(patterns), _tactics(tactics)
+    _check_records(recs)
+    t = L.records_to_device(recs, _device(device, None, recs), clone=False)
+    return _move_weights_device(t, table, tactics).cpu().numpy()
+
+
+def _move_weights_device(recs, table, tactics):
+    """recs: a uint8 [R,192] tensor on the device -> int32 [R,81] on the device; nothing here waits for it."""
+    tables = (None if table is None else table.device(recs.device), None if tactics is None else tactics.device(recs.device))
+    parts = [T.move_weights(recs[s:s + T.MAX_BATCH], *tables) for s in range(0, len(recs), T.MAX_BATCH)]
+    return parts[0] if len(parts) == 1 else torch.cat(parts)
+
+
+def _check_mu(mu):
+    mu = float(mu)
+    if not 0.0 <= mu < float("inf"):
+        raise ValueError("mu must be finite and not negative")
+    return mu
+
+
+def _log_weights(weights, R):
+    """ln max(w, 1) of move weights [R,81], float64: a point off the playable set enters with the least weight, 1."""
+    w = np.asarray(_numpy(weights))
+    if w.shape != (R, 81):
+        raise ValueError(f"weights must be [{R}, 81], one row per record")
+    return np.log(np.maximum(w.astype(np.float64), 1.0))
+
+
+def pattern_prior(recs, weights, mu=1.0):
+    """The move predictor's own prediction -> float32 [R,81], in float64 on the host: with weights = move_weights(recs, ...),
+    p_s = exp(mu * (ln max(w_s, 1) - the maximum over the legal points)) on the legal points (bk_pos_legal_moves), 0
+    elsewhere, each row divided by its sum; a record without a legal point gets 1/81 everywhere.  mu = 1: in proportion to
+    the weights.  mu must be finite and not negative."""
+    mu = _check_mu(mu)
+    recs = np.array(_numpy(recs), np.uint8, order="C")
+    _check_records(recs)
+    lw = _log_weights(weights, len(recs))
+    legal = legal_host(recs)
+    top = np.where(legal, lw, -np.inf).max(1, keepdims=True)
+    some = legal.any(1)
+    top[~some] = 0.0
+    p = np.where(legal, np.exp(mu * (lw - top)), 0.0)
+    p[~some] = 1.0
+    return (p / p.sum(1, keepdims=True)).astype(np.float32)
+
+
+def amaf_prior(recs, amaf, k=PRIOR_K, temperature=PRIOR_TEMPERATURE, criticality=None, gamma=0.0, weights=None, mu=0.0):
     """A search prior from the counts of playout_amaf(recs, ...) -> float32 [R,81], computed on the host in float64 from the
     integers, so that device and host playouts give the same floats.  With wbar = wins / n, the win rate of all n playouts,
         q_s = (won_s + k * wbar) / (played_s + k)      the AMAF win rate of the point, k playouts' worth of wbar mixed in,
@@ -715,8 +791,12 @@ def amaf_prior(recs, amaf, k=PRIOR_K, temperature=PRIOR_TEMPERATURE, criticality
     defaults, 4.0 and 0.1, are plausible and untuned.  Two-sided counts ([R,2,81], playout_amaf(sides=2)) are read at side 0.
     criticality (float64 [R,81], Ownership.criticality()) with gamma > 0: q_s + gamma * criticality_s takes the place of q_s
     (gamma is untuned).  criticality=None or gamma == 0: the floats above, bit for bit.  gamma must be finite and
-    not negative."""
-    k, temperature, gamma = float(k), float(temperature), float(gamma)
+    not negative.
+    weights (int [R,81], move_weights(recs, ...)) with mu > 0: the logit of a legal point is
+    (q_s + gamma * criticality_s) / temperature + mu * ln(max(w_s, 1)), shifted by its maximum over the legal points before
+    exp (mu is untuned); a legal point off the playable set (an own eye) enters with the least weight, 1.
+    weights=None or mu == 0: the floats above, bit for bit.  mu must be finite and not negative."""
+    k, temperature, gamma, mu = float(k), float(temperature), float(gamma), _check_mu(mu)
     if not k > 0 or not temperature > 0:
         raise ValueError("k and temperature must be greater than 0")
     if not 0.0 <= gamma < float("inf"):
@@ -736,10 +816,16 @@ def amaf_prior(recs, amaf, k=PRIOR_K, temperature=PRIOR_TEMPERATURE, criticality
             raise ValueError(f"criticality must be [{len(recs)}, 81], one row per record")
         q = q + gamma * crit
     legal = legal_host(recs)
-    top = np.where(legal, q, -np.inf).max(1, keepdims=True)
     some = legal.any(1)
-    top[~some] = 0.0
-    p = np.where(legal, np.exp((q - top) / temperature), 0.0)
+    if weights is not None and mu > 0.0:
+        z = q / temperature + mu * _log_weights(weights, len(recs))
+        top = np.where(legal, z, -np.inf).max(1, keepdims=True)
+        top[~some] = 0.0
+        p = np.where(legal, np.exp(z - top), 0.0)
+    else:
+        top = np.where(legal, q, -np.inf).max(1, keepdims=True)
+        top[~some] = 0.0
+        p = np.where(legal, np.exp((q - top) / temperature), 0.0)
     p[~some] = 1.0
     return (p / p.sum(1, keepdims=True)).astype(np.float32)
 
@@ -763,12 +849,18 @@ class PlayoutEvaluator:
     final records, one bkt_owner_counts over the first n_policy rows gives their Ownership counts, and amaf_prior gets
     criticality = Coulom's criticality of every point and gamma (untuned).  The values of all rows and, with
     rave=True, the records are what they are without it.
+    pattern_prior (mu >= 0, default 0: exactly the above, the same launches; it needs prior > 0): one bkt_move_weights over
+    the first n_policy rows (the host mirror with rules="host") gives their move weights, and amaf_prior gets them and mu
+    (untuned).  The tables of that term are prior_patterns and prior_tactics, which default to the playouts' own
+    patterns and tactics -- so uniform playouts can run under a pattern prior; with no table at all every weight would be
+    equal: ValueError.  Values and records are what they are without it.
     The engine is kept as `policy_engine`, not `engine`: selfplay.run_pools_native hands an evaluator's `engine` to the C
     step loop as its own bk_evaluator, which would compute no playouts -- this class goes through callback_evaluator."""
     wants_positions = True
 
     def __init__(self, engine, playouts=64, seed=0, rules="device", komi=L.KOMI, patterns=None, tactics=None, prior=0.0,
-                 prior_k=PRIOR_K, prior_temperature=PRIOR_TEMPERATURE, rave=False, criticality=0.0):
+                 prior_k=PRIOR_K, prior_temperature=PRIOR_TEMPERATURE, rave=False, criticality=0.0, pattern_prior=0.0,
+                 prior_patterns=None, prior_tactics=None):
         L.check_rules(rules)
         self.rave = bool(rave)
         self.criticality = float(criticality)
@@ -778,6 +870,15 @@ class PlayoutEvaluator:
             raise ValueError("criticality is a term of the playout prior: it needs prior > 0")
         self.patterns = _table(patterns)                                  # None: uniformly random playouts
         self.tactics = _tactics(tactics)                                  # None: no tactical weights
+        self.pattern_prior = float(pattern_prior)
+        if not 0.0 <= self.pattern_prior < float("inf"):
+            raise ValueError("pattern_prior must be finite and not negative")
+        if self.pattern_prior > 0.0 and not float(prior) > 0.0:
+            raise ValueError("pattern_prior is a term of the playout prior: it needs prior > 0")
+        self.prior_patterns = self.patterns if prior_patterns is None else _table(prior_patterns)
+        self.prior_tactics = self.tactics if prior_tactics is None else _tactics(prior_tactics)
+        if self.pattern_prior > 0.0 and self.prior_patterns is None and self.prior_tactics is None:
+            raise ValueError("pattern_prior needs a table: patterns, tactics, prior_patterns or prior_tactics")
         self.prior = float(prior)
         if not 0.0 <= self.prior <= 1.0:
             raise ValueError("prior must be within 0..1")
@@ -805,6 +906,7 @@ class PlayoutEvaluator:
         more = dict(komi=self.komi, table=self.patterns, tactics=self.tactics)
         owned = n_policy if n_policy and self.criticality > 0.0 else 0   # rows whose final boards are counted (then prior > 0)
         final = ()                                                        # (the host's final records, when they are counted)
+        t = None                                                          # (the records on the device, with the device rules)
         if self.rave:                                                     # every row with its history, both sides counted
             if self.rules == "host":
                 values, w, moves, *final = _playout_host_wins(recs, self.playouts, self.seed, history=True,
@@ -817,6 +919,8 @@ class PlayoutEvaluator:
             counted = (recs[:n_policy], n_policy) if n_policy and self.prior > 0.0 else None
             if owned:
                 counted += (self._owned(final, counts, owned),)
+            if counted is not None and self.pattern_prior > 0.0:
+                counted += (self._weights(recs, t, n_policy),)
             return ticket, values, counted, (w, *counts[:2])
         if n_policy and self.prior > 0.0:                                 # the playouts with their history, and the counts
             if self.rules == "host":
@@ -828,7 +932,8 @@ class PlayoutEvaluator:
                 t = torch.from_numpy(recs).to(_device(None, self.policy_engine))
                 values, w, *counts = _playout_amaf_device(t, self.playouts, self.seed, counted=n_policy, owned=owned, **more)
             counted = (recs[:n_policy], w[:n_policy], *counts[:2])
-            return ticket, values, counted + ((self._owned(final, counts, owned),) if owned else ())
+            counted += (self._owned(final, counts, owned),) if owned else ()
+            return ticket, values, counted + ((self._weights(recs, t, n_policy),) if self.pattern_prior > 0.0 else ())
         if self.rules == "host":
             values = _playout_host_wins(recs, self.playouts, self.seed, history=False, **more)[0]
         else:
@@ -843,9 +948,18 @@ class PlayoutEvaluator:
             return owner_counts_host(final[0][:owned * self.playouts], owned, self.playouts, self.komi)
         return counts[2]
 
+    def _weights(self, recs, t, n_policy):
+        """The move weights of the first n_policy rows: the host mirror, or one bkt_move_weights on the records t already
+        on the device (nothing waits for it)."""
+        if self.rules == "host":
+            return move_weights_host(recs[:n_policy], self.prior_patterns, self.prior_tactics)
+        return _move_weights_device(t[:n_policy], self.prior_patterns, self.prior_tactics)
+
     def finish(self, handle, normalise=None):
         ticket, values, counted, *rave = handle
-        owned = None
+        owned = weights = None
+        if counted is not None and self.pattern_prior > 0.0:             # the last element: the move weights
+            counted, weights = counted[:-1], _numpy(counted[-1])
         if counted is not None and self.criticality > 0.0:               # the last element: the owner counts
             counted, owned = counted[:-1], [_numpy(x) for x in counted[-1]]
         if normalise is None:
@@ -861,7 +975,7 @@ class PlayoutEvaluator:
             recs, w, played, won = (_numpy(x) for x in counted)
             crit = None if owned is None else criticality_of(owned[0], owned[1], owned[2], owned[4], self.playouts)
             prior = amaf_prior(recs, Amaf(None, w, played, won, self.playouts), self.prior_k, self.prior_temperature,
-                               criticality=crit, gamma=self.criticality)
+                               criticality=crit, gamma=self.criticality, weights=weights, mu=self.pattern_prior)
             if ticket is not None:
                 prior = ((1.0 - self.prior) * probs.astype(np.float64) + self.prior * prior.astype(np.float64))
             probs = prior.astype(np.float32)
@@ -990,6 +1104,9 @@ def _parse(argv):
                     help="with --random: print the Monte-Carlo value and the ten heaviest moves of the AMAF prior instead of the score")
     ap.add_argument("--ownership", action="store_true",
                     help="with --random: print the ownership map, the mean margin and the ten most critical points instead of the score")
+    ap.add_argument("--weights", action="store_true",
+                    help="with --random: print the ten heaviest points of the position by the playouts' move weights "
+                         "(--patterns, --tactics) instead of the score; no playout runs")
     ap.add_argument("--sides", type=int, default=1, choices=(1, 2),
                     help="with --amaf: 2 also prints the opponent's heaviest points (the two-sided counts RAVE is fed with)")
     ap.add_argument("-n", dest="n", type=int, default=256, help="playouts")
@@ -1001,6 +1118,8 @@ def _parse(argv):
         ap.error("--amaf reads the one-launch playouts: it needs --random")
     if args.ownership and (not args.random or args.amaf):
         ap.error("--ownership reads the one-launch playouts: it needs --random, and not --amaf")
+    if args.weights and (not args.random or args.amaf or args.ownership):
+        ap.error("--weights reads the one-launch playouts' draw: it needs --random, and not --amaf or --ownership")
     if args.sides != 1 and not args.amaf:
         ap.error("--sides goes with --amaf")
     if args.n < 1:
@@ -1047,6 +1166,14 @@ def main(argv=None):
             out["opponent"] = [{"move": go.unsquash(s), "played": int(a.played[0, 1, s]), "won": int(a.won[0, 1, s])}
                                for s in np.argsort(-a.played[0, 1], kind="stable")[:10].tolist()]
         print(json.dumps(out))
+        return
+    if args.weights:
+        recs = _as_records(game)
+        w = move_weights(recs, args.patterns, args.tactics, device=torch.device("cuda", args.device))[0]
+        p = pattern_prior(recs, w[None])[0]
+        print(json.dumps({"playable": int((w > 0).sum()),
+                          "weights": [{"move": go.unsquash(s), "weight": int(w[s]), "share": float(p[s])}
+                                      for s in np.argsort(-w, kind="stable")[:10].tolist() if w[s] > 0]}))
         return
     if args.ownership:
         o = playout_ownership(_as_records(game), args.n, args.seed, komi=args.komi, device=torch.device("cuda", args.device),

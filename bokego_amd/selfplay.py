@@ -870,6 +870,14 @@ def parse_args(argv=None):
     ap.add_argument("--playout-criticality", type=float, default=0.0, metavar="GAMMA",
                     help="with --playout-prior: GAMMA times Coulom's criticality of each point is added to the AMAF win rates of the "
                          "prior (untuned; default 0: off)")
+    ap.add_argument("--playout-pattern-prior", type=float, default=0.0, metavar="MU",
+                    help="with --playout-prior: add MU times the log of each point's move weight -- the playouts' pattern and "
+                         "tactical tables, or --prior-patterns / --prior-tactics -- to the prior's logits (untuned; default 0: "
+                         "off, DESIGN 22)")
+    ap.add_argument("--prior-patterns", default=None, metavar="FILE",
+                    help="with --playout-pattern-prior: the pattern table of that term (default: --playout-patterns)")
+    ap.add_argument("--prior-tactics", default=None, metavar="FILE",
+                    help="with --playout-pattern-prior: the tactics table of that term (default: --playout-tactics)")
     args = ap.parse_args(argv)
     if args.playout_value < 0:
         ap.error("--playout-value must not be negative")
@@ -887,6 +895,17 @@ def parse_args(argv=None):
         ap.error("--playout-criticality must be a finite number, 0 or more")
     if args.playout_criticality and not args.playout_prior:
         ap.error("--playout-criticality is a term of the playout prior: it needs --playout-prior")
+    if not 0.0 <= args.playout_pattern_prior < float("inf"):
+        ap.error("--playout-pattern-prior must be a finite number, 0 or more")
+    if args.playout_pattern_prior and not args.playout_prior:
+        ap.error("--playout-pattern-prior is a term of the playout prior: it needs --playout-prior")
+    for flag, given in (("--prior-patterns", args.prior_patterns), ("--prior-tactics", args.prior_tactics)):
+        if given is not None and not args.playout_pattern_prior:
+            ap.error(f"{flag} is the table of --playout-pattern-prior: it needs --playout-pattern-prior MU")
+    if args.playout_pattern_prior and all(t is None for t in (args.playout_patterns, args.playout_tactics,
+                                                              args.prior_patterns, args.prior_tactics)):
+        ap.error("--playout-pattern-prior needs a table: --playout-patterns, --playout-tactics, --prior-patterns or "
+                 "--prior-tactics")
     if args.playout_prior == 1.0 and args.policy is not None:
         ap.error("--playout-prior 1 searches without a policy net: not allowed with --policy")
     return args
@@ -930,7 +949,9 @@ def main(argv=None):
             eng = LeafEngine(load(args.policy, "policy_19.bkw"), None, device_id=local_rank, max_batch=args.max_batch,
                              precision=args.precision)
         ev = PlayoutEvaluator(eng, args.playout_value, patterns=args.playout_patterns, tactics=args.playout_tactics,
-                              prior=args.playout_prior, criticality=args.playout_criticality)
+                              prior=args.playout_prior, criticality=args.playout_criticality,
+                              pattern_prior=args.playout_pattern_prior, prior_patterns=args.prior_patterns,
+                              prior_tactics=args.prior_tactics)
     else:
         eng = LeafEngine(load(args.policy, "policy_19.bkw"), load(args.value, "value_synth.bkw"), device_id=local_rank,
                          max_batch=args.max_batch, precision=args.precision)

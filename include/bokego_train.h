@@ -312,6 +312,22 @@ int bkt_amaf_counts_sides(const int16_t *moves, int max_plies, const uint8_t *wo
 int bkt_owner_counts(const void *pos, int records, int playouts, float komi, int32_t *black, int32_t *white,
                      int32_t *agree, int32_t *hist, int32_t *black_wins, void *stream);
 
+/* The move weights of every record, in ONE launch (bokego_amd/rollout.py move_weights, the pattern term of amaf_prior;
+ * DESIGN 22): weights[b*81 + s] is the weight bkt_tactical_playouts' draw gives point s at the first ply of a playout
+ * started from record b as it stands, and 0 where s is not in that ply's playable set.
+ *   Playable: plane 5 of the 27 planes bk_features_batch_u8(record, fresh = 0) gives is non-zero at s, and s is not the
+ *       mover's own one-point eye by bk_pos_possible_eye: the set bkt_playout_step leaves behind for an untouched record.
+ *   P = max(table[index], 1) with index exactly bkt_pattern_codes' index of s; P = 256 when table is NULL.
+ *   T = tactics[code] with code exactly bkt_tactical_codes' code of s; T = 256 when tactics is NULL.
+ *   w_s = max(1, (P * T) >> 8) on the playable set (a 32-bit product; w_s < 2^24), 0 off it.
+ * table: uint16 [BKT_PATTERN_ENTRIES] and tactics: uint16 [BKT_TACTIC_ENTRIES] on the device; both may be NULL, which
+ * gives 256 on the playable set.  Every entry of weights [batch, 81] is written.  The records are read only.  Integers
+ * only.
+ * 1 <= batch <= BKT_MAX_BATCH; pos and weights must not be NULL; else BKT_ERR_ARG, nothing is launched and nothing
+ * written. */
+int bkt_move_weights(const void *pos, int batch, const uint16_t *table, const uint16_t *tactics, uint32_t *weights,
+                     void *stream);
+
 #ifdef __cplusplus
 }
 #endif
