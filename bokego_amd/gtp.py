@@ -33,6 +33,7 @@ from timeit import default_timer
 
 from . import go
 from .mcts import MCTS, Go_MCTS
+from .playout_options import PlayoutOptions
 
 FLOWERS9 = (20, 60, 24, 56, 40)
 
@@ -469,32 +470,7 @@ def build_parser():
     ap.add_argument("--rollout-score", type=int, default=0, metavar="N",
                     help="N > 0: final_score and final_status_list from N policy playouts to the end of the game "
                          "(default 0: the score of the board as it stands)")
-    ap.add_argument("--playout-value", type=int, default=0, metavar="N",
-                    help="N > 0: no value net -- a leaf's value is the share of N uniformly random playouts its side to move "
-                         "wins (not with -v, --simulate or --python-tree)")
-    ap.add_argument("--playout-patterns", default=None, metavar="FILE",
-                    help="with --playout-value: draw the playouts' moves by the 3x3 pattern weights of this table "
-                         "(python -m bokego_amd.patterns fit)")
-    ap.add_argument("--playout-tactics", default=None, metavar="FILE",
-                    help="with --playout-value: multiply the playouts' weights by the tactical weights of this table "
-                         "(python -m bokego_amd.tactics fit)")
-    ap.add_argument("--playout-prior", type=float, default=0.0, metavar="LAMBDA",
-                    help="with --playout-value: that share (0..1) of the priors comes from the playouts' AMAF counts; with 1 "
-                         "no policy net is loaded")
-    ap.add_argument("--playout-rave", type=float, nargs="?", const=4.0, default=0.0, metavar="K",
-                    help="with --playout-value: RAVE -- the playouts' two-sided AMAF counts are backed up into per-node tables and "
-                         "blended into the selection with the equivalence parameter K (visits; 4 when no value is given: the one of 4, 16 and 64 that won its 100-game match, DESIGN 20)")
-    ap.add_argument("--playout-criticality", type=float, default=0.0, metavar="GAMMA",
-                    help="with --playout-prior: add GAMMA times Coulom's criticality of each point, from the final boards of the "
-                         "same playouts, to the AMAF win rates the prior is made of (untuned; default 0: off, DESIGN 21)")
-    ap.add_argument("--playout-pattern-prior", type=float, default=0.0, metavar="MU",
-                    help="with --playout-prior: add MU times the log of each point's move weight -- the playouts' pattern and "
-                         "tactical tables, or --prior-patterns / --prior-tactics -- to the prior's logits (untuned; default 0: "
-                         "off, DESIGN 22)")
-    ap.add_argument("--prior-patterns", default=None, metavar="FILE",
-                    help="with --playout-pattern-prior: the pattern table of that term (default: --playout-patterns)")
-    ap.add_argument("--prior-tactics", default=None, metavar="FILE",
-                    help="with --playout-pattern-prior: the tactics table of that term (default: --playout-tactics)")
+    PlayoutOptions.add_arguments(ap)                                 # --playout-value N: not with -v, --simulate or --python-tree
     ap.add_argument("--python-tree", action="store_true", help="search with the Python tree instead of the native one")
     ap.set_defaults(v_given=False)
     return ap
@@ -514,39 +490,11 @@ def parse_args(argv=None):
     args = ap.parse_args(argv)
     if args.rollout_score < 0:
         ap.error("--rollout-score must not be negative")
-    if args.playout_value < 0:
-        ap.error("--playout-value must not be negative")
+    args.playout = PlayoutOptions.from_args(ap, args)
     if args.playout_value:
         for flag, on in (("-v", args.v_given), ("--simulate", args.simulate), ("--python-tree", args.python_tree)):
             if on:
                 ap.error(f"--playout-value takes the place of a value net: not allowed with {flag}")
-    if args.playout_patterns is not None and not args.playout_value:
-        ap.error("--playout-patterns weights the playouts of --playout-value: it needs --playout-value N")
-    if args.playout_tactics is not None and not args.playout_value:
-        ap.error("--playout-tactics weights the playouts of --playout-value: it needs --playout-value N")
-    if not 0.0 <= args.playout_prior <= 1.0:
-        ap.error("--playout-prior must be within 0..1")
-    if args.playout_prior and not args.playout_value:
-        ap.error("--playout-prior reads the playouts of --playout-value: it needs --playout-value N")
-    if not 0.0 <= args.playout_rave < float("inf"):
-        ap.error("--playout-rave must be a finite number, 0 or more")
-    if args.playout_rave and not args.playout_value:
-        ap.error("--playout-rave reads the playouts of --playout-value: it needs --playout-value N")
-    if not 0.0 <= args.playout_criticality < float("inf"):
-        ap.error("--playout-criticality must be a finite number, 0 or more")
-    if args.playout_criticality and not args.playout_prior:
-        ap.error("--playout-criticality is a term of the playout prior: it needs --playout-prior")
-    if not 0.0 <= args.playout_pattern_prior < float("inf"):
-        ap.error("--playout-pattern-prior must be a finite number, 0 or more")
-    if args.playout_pattern_prior and not args.playout_prior:
-        ap.error("--playout-pattern-prior is a term of the playout prior: it needs --playout-prior")
-    for flag, given in (("--prior-patterns", args.prior_patterns), ("--prior-tactics", args.prior_tactics)):
-        if given is not None and not args.playout_pattern_prior:
-            ap.error(f"{flag} is the table of --playout-pattern-prior: it needs --playout-pattern-prior MU")
-    if args.playout_pattern_prior and all(t is None for t in (args.playout_patterns, args.playout_tactics,
-                                                              args.prior_patterns, args.prior_tactics)):
-        ap.error("--playout-pattern-prior needs a table: --playout-patterns, --playout-tactics, --prior-patterns or "
-                 "--prior-tactics")
     return args
 
 
@@ -564,22 +512,8 @@ def main(argv=None):
     if not args.playout_value:
         val = nnet.HipValueNet(load_state_dict(args.v), device_id=args.gpu, precision=args.precision)
     cls, root = (GTP, Go_MCTS()) if args.python_tree else (NativeGTP, Position())
-    more = {"playout_value": args.playout_value} if args.playout_value else {}
-    if args.playout_patterns is not None:
-        more["playout_patterns"] = args.playout_patterns
-    if args.playout_tactics is not None:
-        more["playout_tactics"] = args.playout_tactics
-    if args.playout_prior:
-        more["playout_prior"] = args.playout_prior
-    if args.playout_rave:
-        more["playout_rave"] = args.playout_rave
-    if args.playout_criticality:
-        more["playout_criticality"] = args.playout_criticality
-    if args.playout_pattern_prior:
-        more.update(playout_pattern_prior=args.playout_pattern_prior, prior_patterns=args.prior_patterns,
-                    prior_tactics=args.prior_tactics)
     gtp = cls(root, pi, val, no_sim=not args.simulate, time_lim=None if args.r else args.t, n_rollouts=args.r, pondering=args.ponder,
-              rollout_score=args.rollout_score, **more)
+              rollout_score=args.rollout_score, **args.playout.search_keywords())
     gtp.start()
 
 

@@ -21,6 +21,7 @@ import time
 import numpy as np
 
 from . import go
+from .playout_options import PlayoutOptions
 
 
 class InProcessEngine:
@@ -228,29 +229,7 @@ def parse_args(argv=None):
     ap.add_argument("-r", type=int, default=400, help="rollouts per move of the HIP engine")
     ap.add_argument("-p", default=os.path.join(golden, "policy_19.bkw"))
     ap.add_argument("-v", default=os.path.join(golden, "value_synth.bkw"))
-    ap.add_argument("--playout-value", type=int, default=0, metavar="N",
-                    help="N > 0: the in-process engine searches without a value net, on the Monte-Carlo value of N random "
-                         "playouts (-v is then not loaded; not with --engine)")
-    ap.add_argument("--playout-patterns", default=None, metavar="FILE",
-                    help="with --playout-value: the table of 3x3 pattern weights its playouts draw their moves by")
-    ap.add_argument("--playout-tactics", default=None, metavar="FILE",
-                    help="with --playout-value: the table of tactical weights that multiply its playouts' weights")
-    ap.add_argument("--playout-prior", type=float, default=0.0, metavar="LAMBDA",
-                    help="with --playout-value: that share (0..1) of its priors comes from the playouts' AMAF counts; with 1 "
-                         "the engine loads no policy net")
-    ap.add_argument("--playout-rave", type=float, nargs="?", const=4.0, default=0.0, metavar="K",
-                    help="with --playout-value: RAVE with the equivalence parameter K (visits; 4 when no value is given, DESIGN 20)")
-    ap.add_argument("--playout-criticality", type=float, default=0.0, metavar="GAMMA",
-                    help="with --playout-prior: GAMMA times Coulom's criticality of each point is added to the AMAF win rates of its "
-                         "prior (untuned; default 0: off, DESIGN 21)")
-    ap.add_argument("--playout-pattern-prior", type=float, default=0.0, metavar="MU",
-                    help="with --playout-prior: add MU times the log of each point's move weight -- the playouts' pattern and "
-                         "tactical tables, or --prior-patterns / --prior-tactics -- to the prior's logits (untuned; default 0: "
-                         "off, DESIGN 22)")
-    ap.add_argument("--prior-patterns", default=None, metavar="FILE",
-                    help="with --playout-pattern-prior: the pattern table of that term (default: --playout-patterns)")
-    ap.add_argument("--prior-tactics", default=None, metavar="FILE",
-                    help="with --playout-pattern-prior: the tactics table of that term (default: --playout-tactics)")
+    PlayoutOptions.add_arguments(ap)                                 # of the in-process engine (-v is then not loaded): not with --engine
     ap.add_argument("--opponent", default="policy", help='"policy" (raw policy, no search) or a GTP command line')
     ap.add_argument("--komi", type=float, default=5.5)
     ap.add_argument("--sgf", default=None, help="prefix for SGF records")
@@ -263,37 +242,9 @@ def parse_args(argv=None):
     ap.add_argument("--opponent-name", default=None)
     ap.add_argument("--json-out", default=None, help="also write the result (without the move records) to this file")
     args = ap.parse_args(argv)
-    if args.playout_value < 0:
-        ap.error("--playout-value must not be negative")
+    args.playout = PlayoutOptions.from_args(ap, args)
     if args.playout_value and args.engine is not None:
         ap.error("--playout-value configures the in-process engine: it does not go with --engine")
-    if args.playout_patterns is not None and not args.playout_value:
-        ap.error("--playout-patterns weights the playouts of --playout-value: it needs --playout-value N")
-    if args.playout_tactics is not None and not args.playout_value:
-        ap.error("--playout-tactics weights the playouts of --playout-value: it needs --playout-value N")
-    if not 0.0 <= args.playout_prior <= 1.0:
-        ap.error("--playout-prior must be within 0..1")
-    if args.playout_prior and not args.playout_value:
-        ap.error("--playout-prior reads the playouts of --playout-value: it needs --playout-value N")
-    if not 0.0 <= args.playout_rave < float("inf"):
-        ap.error("--playout-rave must be a finite number, 0 or more")
-    if args.playout_rave and not args.playout_value:
-        ap.error("--playout-rave reads the playouts of --playout-value: it needs --playout-value N")
-    if not 0.0 <= args.playout_criticality < float("inf"):
-        ap.error("--playout-criticality must be a finite number, 0 or more")
-    if args.playout_criticality and not args.playout_prior:
-        ap.error("--playout-criticality is a term of the playout prior: it needs --playout-prior")
-    if not 0.0 <= args.playout_pattern_prior < float("inf"):
-        ap.error("--playout-pattern-prior must be a finite number, 0 or more")
-    if args.playout_pattern_prior and not args.playout_prior:
-        ap.error("--playout-pattern-prior is a term of the playout prior: it needs --playout-prior")
-    for flag, given in (("--prior-patterns", args.prior_patterns), ("--prior-tactics", args.prior_tactics)):
-        if given is not None and not args.playout_pattern_prior:
-            ap.error(f"{flag} is the table of --playout-pattern-prior: it needs --playout-pattern-prior MU")
-    if args.playout_pattern_prior and all(t is None for t in (args.playout_patterns, args.playout_tactics,
-                                                              args.prior_patterns, args.prior_tactics)):
-        ap.error("--playout-pattern-prior needs a table: --playout-patterns, --playout-tactics, --prior-patterns or "
-                 "--prior-tactics")
     return args
 
 
@@ -307,26 +258,9 @@ def main(argv=None):
         if args.opponent == "policy" or args.engine is not None or args.playout_prior != 1.0:
             pi = nnet.HipPolicyNet(load_state_dict(args.p), precision=args.precision)
     if args.engine is None and args.playout_value > 0:
-        more = {} if args.playout_patterns is None else {"playout_patterns": args.playout_patterns}
-        if args.playout_tactics is not None:
-            more["playout_tactics"] = args.playout_tactics
-        name = f"boke-hip-r{args.r}-mc{args.playout_value}" + ("-pat" if more else "")
-        if args.playout_prior:
-            more["playout_prior"] = args.playout_prior
-            name += f"-amaf{args.playout_prior:g}"
-        if args.playout_rave:
-            more["playout_rave"] = args.playout_rave
-            name += f"-rave{args.playout_rave:g}"
-        if args.playout_criticality:
-            more["playout_criticality"] = args.playout_criticality
-            name += f"-crit{args.playout_criticality:g}"
-        if args.playout_pattern_prior:
-            more.update(playout_pattern_prior=args.playout_pattern_prior, prior_patterns=args.prior_patterns,
-                        prior_tactics=args.prior_tactics)
-            name += f"-pp{args.playout_pattern_prior:g}"
         a = InProcessEngine(NativeGTP(Position(), None if args.playout_prior == 1.0 else pi, None, no_sim=True, time_lim=None,
-                                      n_rollouts=args.r, playout_value=args.playout_value, **more),
-                            name=args.engine_name or name)
+                                      n_rollouts=args.r, **args.playout.search_keywords()),
+                            name=args.engine_name or f"boke-hip-r{args.r}" + args.playout.name_suffix())
     elif args.engine is None:
         val = nnet.HipValueNet(load_state_dict(args.v), precision=args.precision)
         a = InProcessEngine(NativeGTP(Position(), pi, val, no_sim=True, time_lim=None, n_rollouts=args.r),

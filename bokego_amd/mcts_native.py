@@ -20,6 +20,7 @@ from collections.abc import Mapping
 import numpy as np
 
 from . import go, nnet, selfplay
+from .playout_options import PlayoutOptions
 
 MAX_TURNS = 80
 # children evaluated at an expansion: 0 = every child.  One tree is latency-bound -- a request of 2 tasks and one of 64 cost the
@@ -146,44 +147,15 @@ class NativeMCTS:
     prior's logits (untuned)."""
 
     def __init__(self, root=None, policy_net=None, value_net=None, **kwargs):
-        self.playout_prior = float(kwargs.get("playout_prior") or 0.0)   # 0: the priors are the policy net's alone
-        if self.playout_prior and not kwargs.get("playout_value"):
-            raise TypeError("playout_prior reads the playouts of playout_value=N: it needs playout_value")
-        self.playout_rave = float(kwargs.get("playout_rave") or 0.0)     # 0: no RAVE
-        if self.playout_rave and not kwargs.get("playout_value"):
-            raise TypeError("playout_rave reads the playouts of playout_value=N: it needs playout_value")
-        if not 0.0 <= self.playout_rave < float("inf"):
-            raise ValueError("playout_rave must be a finite number >= 0")
-        self.playout_criticality = float(kwargs.get("playout_criticality") or 0.0)   # 0: the prior is AMAF's alone
-        if self.playout_criticality and not self.playout_prior:
-            raise TypeError("playout_criticality is a term of playout_prior: it needs playout_prior")
-        if not 0.0 <= self.playout_criticality < float("inf"):
-            raise ValueError("playout_criticality must be a finite number >= 0")
-        self.playout_pattern_prior = float(kwargs.get("playout_pattern_prior") or 0.0)   # 0: no pattern term in the prior
-        self.prior_patterns, self.prior_tactics = kwargs.get("prior_patterns"), kwargs.get("prior_tactics")
-        if (self.playout_pattern_prior or self.prior_patterns is not None or self.prior_tactics is not None) \
-                and not self.playout_prior:
-            raise TypeError("playout_pattern_prior, prior_patterns and prior_tactics are terms of playout_prior: they need "
-                            "playout_prior")
-        if not 0.0 <= self.playout_pattern_prior < float("inf"):
-            raise ValueError("playout_pattern_prior must be a finite number >= 0")
+        # OPT-IN, not the reference's search: playout_value=N > 0 -- no value net; a leaf's value is the share of N uniformly
+        # random playouts its side to move wins (rollout.PlayoutEvaluator on the policy net's engine; DESIGN 16).  Every
+        # playout_* and prior_* keyword becomes an attribute of the same name, checked (playout_options; DESIGN 23).
+        self._playout = PlayoutOptions.from_keywords(kwargs)
+        vars(self).update(vars(self._playout))
         if policy_net is None and kwargs.get("evaluator") is None and self.playout_prior != 1.0:
             raise TypeError("Missing required keywork argument: 'policy_net'")
         self.no_sim = kwargs.get("no_sim", True)
-        # OPT-IN, not the reference's search: playout_value=N > 0 -- no value net; a leaf's value is the share of N uniformly
-        # random playouts its side to move wins (rollout.PlayoutEvaluator on the policy net's engine; DESIGN 16).
-        self.playout_value = int(kwargs.get("playout_value") or 0)
-        self.playout_seed = int(kwargs.get("playout_seed", 0))
-        self.playout_rules = kwargs.get("playout_rules", "device")     # "host": the playouts on the host rules, the same bits
-        self.playout_patterns = kwargs.get("playout_patterns")         # None: uniformly random playouts (DESIGN 17)
-        if self.playout_patterns is not None and not self.playout_value:
-            raise TypeError("playout_patterns weights the playouts of playout_value=N: it needs playout_value")
-        self.playout_tactics = kwargs.get("playout_tactics")           # None: no tactical weights (DESIGN 18)
-        if self.playout_tactics is not None and not self.playout_value:
-            raise TypeError("playout_tactics weights the playouts of playout_value=N: it needs playout_value")
         if self.playout_value:
-            if self.playout_value < 0:
-                raise ValueError("playout_value must not be negative")
             if value_net is not None or not self.no_sim or kwargs.get("evaluator") is not None:
                 raise TypeError("playout_value=N goes with policy_net alone: no value_net, no evaluator, no_sim=True")
             kwargs = dict(kwargs, evaluator=self._playout_evaluator(policy_net))
@@ -270,19 +242,7 @@ class NativeMCTS:
                 raise RuntimeError(self.NO_HIP)
             get = lambda: None                                           # noqa: E731  (no network: every prior from the playouts)
         from . import rollout
-        more = {"prior": self.playout_prior} if self.playout_prior else {}
-        if self.playout_patterns is not None:
-            more["patterns"] = self.playout_patterns
-        if self.playout_tactics is not None:
-            more["tactics"] = self.playout_tactics
-        if getattr(self, "playout_rave", 0.0):
-            more["rave"] = True
-        if getattr(self, "playout_criticality", 0.0):
-            more["criticality"] = self.playout_criticality
-        if getattr(self, "playout_pattern_prior", 0.0):
-            more.update(pattern_prior=self.playout_pattern_prior, prior_patterns=self.prior_patterns,
-                        prior_tactics=self.prior_tactics)
-        return rollout.PlayoutEvaluator(get(), self.playout_value, seed=self.playout_seed, rules=self.playout_rules, **more)
+        return rollout.PlayoutEvaluator(get(), **self._playout.evaluator_keywords())
 
     def _evaluator_from_nets(self):
         policy_net, value_net = self.policy_net, self.value_net

@@ -69,6 +69,7 @@ compare the device with.  With engine=None it needs no GPU.
 import argparse
 import ctypes
 import json
+from types import SimpleNamespace
 
 import numpy as np
 import torch
@@ -451,20 +452,6 @@ def _check_playouts(n):
     return n
 
 
-def _playouts_won_device(recs, n, key, komi, max_plies, table, tactics, history):
-    """n playouts of each record of recs (a uint8 [R,192] tensor on the device) -> (won bool [R,n]: the side to move at the
-    record won the playout, moves int16 [R * n, max_plies] or None without history), on the device."""
-    return _playouts_final_device(recs, n, key, komi, max_plies, table, tactics, history)[:2]
-
-
-def _playouts_final_device(recs, n, key, komi, max_plies, table, tactics, history):
-    """_playouts_won_device that also hands on the final records -> (won, moves, pos uint8 [R * n, 192])."""
-    pos = recs.repeat_interleave(n, 0)                                     # a copy: the caller's records stay
-    moves = _play_random_device(pos, key, L.value_counters_device(recs, n), max_plies, history, table, tactics)[2]
-    black_wins = _area_score_device(pos, komi, False).view(len(recs), n) > 0
-    return black_wins == L.black_to_move(recs)[:, None], moves, pos
-
-
 def _value_of_wins(w, n):
     """(2 w - n) / n as the host mirror's float32, on the device.  The device's float32 division is not correctly rounded
     (3 / 7 comes out one ulp high), its float64 division is; and rounding twice changes nothing below n = 2^29: a quotient
@@ -473,26 +460,58 @@ def _value_of_wins(w, n):
     return ((2 * w - n).to(torch.float64) / n).to(torch.float32)
 
 
-def _playout_value_device(recs, n, key, komi, max_plies=MAX_PLIES, table=None, tactics=None):
-    """recs: a uint8 [R,192] tensor on the device -> float32 [R] on the device; nothing here waits for the device."""
-    won, _ = _playouts_won_device(recs, n, key, komi, max_plies, table, tactics, False)
-    return _value_of_wins(won.sum(1), n)
-
-
-def _playout_amaf_device(recs, n, key, komi, counted=None, max_plies=MAX_PLIES, table=None, tactics=None, sides=1,
-                         owned=0):
-    """_playout_value_device's games with their history, and one bkt_amaf_counts over the rows of the first `counted`
-    records (default: all) -> (value float32 [R], wins int64 [R], played int32 [counted,81], won int32 [counted,81]) on the
-    device; nothing here waits for it.  sides=2: one bkt_amaf_counts_sides instead, and the counts are [counted,2,81].
-    owned > 0: a fifth element, T.owner_counts of the final records of the first `owned` records (one bkt_owner_counts)."""
-    counted = len(recs) if counted is None else counted
-    won, moves, pos = _playouts_final_device(recs, n, key, komi, max_plies, table, tactics, True)
-    w = won.sum(1)
-    reduce = T.amaf_counts if sides == 1 else T.amaf_counts_sides
-    played, won_at = reduce(moves[:counted * n], won[:counted].to(torch.uint8).reshape(-1), counted, n)
+def _playouts(recs, n, key, rules, komi=L.KOMI, table=None, tactics=None, max_plies=MAX_PLIES, score=True, history=False,
+              final=False, counted=0, sides=1, owned=0):
+    """The one playout run: n playouts of each record of recs -- a uint8 [R,192] tensor on the device with
+    rules="device", where nothing here waits for it; an array with "host", the mirror -- and what is asked of them, as a
+    namespace whose fields are None when they were not asked for:
+    value   float32 [R], wins [R]   (2 wins - n) / n; wins = the playouts the side to move at the record won
+    won     bool [R,n]              which ones (score=True: from one bkt_area_score; score=False: no such launch, and wins
+                                    comes from the owner counts of owned=True)
+    moves   int16 [R * n, L]        history=True, or counted: the playout launch writes its history
+    final   uint8 [R * n, 192]      final=True: the final records
+    played, won_at                  counted=c (True: all): the AMAF counts of the first c records, int32 [c,81] from one
+                                    bkt_amaf_counts, or with sides=2 [c,2,81] from one bkt_amaf_counts_sides
+    owner                           owned=o (True: all): the five owner counts of the first o records, one bkt_owner_counts"""
+    R, host = len(recs), rules == "host"
+    counted, owned = (R if x is True else int(x) for x in (counted, owned))
+    if host:
+        recs = np.array(_numpy(recs), np.uint8, order="C")
+        fin = _random_host(np.repeat(recs, n, 0), key, value_counters(recs, n), max_plies, komi, history or counted > 0, table,
+                           tactics)
+        pos, moves, black_wins = fin.records, fin.moves, fin.score.reshape(R, n) > 0
+    else:
+        pos = recs.repeat_interleave(n, 0)                                 # a copy: the caller's records stay
+        moves = _play_random_device(pos, key, L.value_counters_device(recs, n), max_plies, history or counted > 0, table,
+                                    tactics)[2]
+        black_wins = _area_score_device(pos, komi, False).view(R, n) > 0 if score else None
+    run = SimpleNamespace(value=None, wins=None, won=None, moves=moves, final=pos if final else None, played=None, won_at=None,
+                          owner=None)
+    if score:
+        run.won = black_wins == L.black_to_move(recs)[:, None]
+        run.wins = run.won.sum(1)
+    if counted:
+        reduce = ((T.amaf_counts, T.amaf_counts_sides), (amaf_counts_host, amaf_counts_sides_host))[host][sides - 1]
+        won = run.won[:counted].reshape(-1)
+        run.played, run.won_at = reduce(moves[:counted * n], won if host else won.to(torch.uint8), counted, n)
     if owned:
-        return _value_of_wins(w, n), w, played, won_at, T.owner_counts(pos[:owned * n], owned, n, komi)
-    return _value_of_wins(w, n), w, played, won_at
+        run.owner = (owner_counts_host if host else T.owner_counts)(pos[:owned * n], owned, n, komi)
+    if not score:
+        bw = run.owner[4] if host else run.owner[4].to(torch.int64)
+        run.wins = (np.where if host else torch.where)(L.black_to_move(recs), bw, n - bw)
+    run.value = ((2 * run.wins - n).astype(np.float32) / np.float32(n)).astype(np.float32) if host else _value_of_wins(run.wins, n)
+    return run
+
+
+def _run(recs, n, seed, rules, komi, device, patterns, tactics, **ask):
+    """What playout_value, playout_amaf and playout_ownership share: the checks, the upload and _playouts(**ask)."""
+    L.check_rules(rules)
+    table, tactics = _table(patterns), _tactics(tactics)
+    n = _check_playouts(n)
+    _check_records(recs)
+    if rules == "device":
+        recs = L.records_to_device(recs, _device(device, None, recs), clone=False)
+    return _playouts(recs, n, L.seed_u64(seed), rules, komi, table, tactics, **ask)
 
 
 def playout_value(recs, n, seed, rules="device", komi=L.KOMI, device=None, patterns=None, tactics=None):
@@ -500,25 +519,7 @@ def playout_value(recs, n, seed, rules="device", komi=L.KOMI, device=None, patte
     eye-safe playouts (random_playouts, capped at MAX_PLIES and then scored as they stand) that the side to move wins --
     black wins iff the area score is > 0.  A pure function of the record, `seed` and `n` (value_counters): the row index
     and the rest of the batch do not enter.  recs: uint8 [R,192], numpy or a tensor.  patterns, tactics: as random_playouts."""
-    L.check_rules(rules)
-    table, tactics = _table(patterns), _tactics(tactics)
-    n = _check_playouts(n)
-    _check_records(recs)
-    key = L.seed_u64(seed)
-    if rules == "device":
-        t = L.records_to_device(recs, _device(device, None, recs), clone=False)
-        return _playout_value_device(t, n, key, komi, table=table, tactics=tactics).cpu().numpy()
-    return _playout_host_wins(recs, n, key, komi, table, tactics, False)[0]
-
-
-def _playout_host_wins(recs, n, key, komi, table, tactics, history, final=False):
-    """playout_value on the host mirror -> (value float32 [R], won bool [R,n], moves int16 [R * n, L] or None); final=True:
-    and the final records uint8 [R * n, 192]."""
-    recs = np.array(_numpy(recs), np.uint8, order="C")
-    fin = _random_host(np.repeat(recs, n, 0), key, value_counters(recs, n), MAX_PLIES, komi, history, table, tactics)
-    w = (fin.score.reshape(len(recs), n) > 0) == L.black_to_move(recs)[:, None]
-    value = ((2 * w.sum(1) - n).astype(np.float32) / np.float32(n)).astype(np.float32)
-    return (value, w, fin.moves, fin.records) if final else (value, w, fin.moves)
+    return _numpy(_run(recs, n, seed, rules, komi, device, patterns, tactics).value)
 
 
 class Amaf:
@@ -537,11 +538,9 @@ class Amaf:
         self.value, self.wins, self.played, self.won, self.n = value, wins, played, won, int(n)
 
 
-def amaf_counts_host(moves, won, records, playouts):
-    """bkt_amaf_counts in numpy: moves int16 [records * playouts, max_plies] (a point 0..80, -1 = pass, <= MOVE_NONE ends the
-    row, anything above 80 is ignored), won [records * playouts] (non-zero: the side to move at the record won the row's
-    playout) -> (played, won_at) int32 [records, 81].  A row counts for the point s when the smallest ply k with
-    moves[row, k] == s is even -- the side to move at the record plays the even plies: played += 1, won_at += the row's won."""
+def _first_plies(moves, won, records, playouts):
+    """The arguments of the two mirrors below, checked -> (first int64 [records * playouts, 81]: the smallest ply at which the
+    row plays the point, P = max_plies: never; P; won as bool [records * playouts]; records; playouts)."""
     records, playouts = int(records), int(playouts)
     moves, won = np.asarray(moves), np.asarray(won).reshape(-1) != 0
     if records < 1 or playouts < 1 or moves.ndim != 2 or len(moves) != records * playouts or len(won) != len(moves):
@@ -551,6 +550,15 @@ def amaf_counts_host(moves, won, records, playouts):
     row, ply = np.nonzero(use)
     first = np.full((G, 81), P, np.int64)                                  # P: never played
     np.minimum.at(first, (row, moves[row, ply].astype(np.int64)), ply)
+    return first, P, won, records, playouts
+
+
+def amaf_counts_host(moves, won, records, playouts):
+    """bkt_amaf_counts in numpy: moves int16 [records * playouts, max_plies] (a point 0..80, -1 = pass, <= MOVE_NONE ends the
+    row, anything above 80 is ignored), won [records * playouts] (non-zero: the side to move at the record won the row's
+    playout) -> (played, won_at) int32 [records, 81].  A row counts for the point s when the smallest ply k with
+    moves[row, k] == s is even -- the side to move at the record plays the even plies: played += 1, won_at += the row's won."""
+    first, P, won, records, playouts = _first_plies(moves, won, records, playouts)
     counts = (first < P) & (first % 2 == 0)
     played = counts.reshape(records, playouts, 81).sum(1)
     won_at = (counts & won[:, None]).reshape(records, playouts, 81).sum(1)
@@ -562,15 +570,7 @@ def amaf_counts_sides_host(moves, won, records, playouts):
     (played, won_at) int32 [records, 2, 81].  A row counts for the point s and the side k & 1, k the smallest ply with
     moves[row, k] == s: side 0 is the side to move at the record and wins the rows with won != 0, side 1 its opponent, who
     wins the others.  [:, 0] is amaf_counts_host's result."""
-    records, playouts = int(records), int(playouts)
-    moves, won = np.asarray(moves), np.asarray(won).reshape(-1) != 0
-    if records < 1 or playouts < 1 or moves.ndim != 2 or len(moves) != records * playouts or len(won) != len(moves):
-        raise ValueError(f"moves must be [{records} * {playouts}, max_plies] and won [{records} * {playouts}]")
-    G, P = moves.shape
-    use = (np.cumsum(moves <= MOVE_NONE, 1) == 0) & (moves >= 0) & (moves <= 80)
-    row, ply = np.nonzero(use)
-    first = np.full((G, 81), P, np.int64)                                  # P: never played
-    np.minimum.at(first, (row, moves[row, ply].astype(np.int64)), ply)
+    first, P, won, records, playouts = _first_plies(moves, won, records, playouts)
     played, won_at = np.zeros((2, records, 2, 81), np.int32)
     for side in (0, 1):
         counts = (first < P) & (first % 2 == side)
@@ -588,18 +588,8 @@ def playout_amaf(recs, n, seed, rules="device", komi=L.KOMI, device=None, patter
     same either way."""
     if sides not in (1, 2):
         raise ValueError("sides must be 1 or 2")
-    L.check_rules(rules)
-    table, tactics = _table(patterns), _tactics(tactics)
-    n = _check_playouts(n)
-    _check_records(recs)
-    key = L.seed_u64(seed)
-    if rules == "device":
-        t = L.records_to_device(recs, _device(device, None, recs), clone=False)
-        value, w, played, won_at = _playout_amaf_device(t, n, key, komi, table=table, tactics=tactics, sides=sides)
-        return Amaf(value.cpu().numpy(), w.cpu().numpy().astype(np.int32), played.cpu().numpy(), won_at.cpu().numpy(), n)
-    value, w, moves = _playout_host_wins(recs, n, key, komi, table, tactics, True)
-    played, won_at = (amaf_counts_host if sides == 1 else amaf_counts_sides_host)(moves, w.reshape(-1), len(w), n)
-    return Amaf(value, w.sum(1).astype(np.int32), played, won_at, n)
+    run = _run(recs, n, seed, rules, komi, device, patterns, tactics, counted=True, sides=sides)
+    return Amaf(_numpy(run.value), _numpy(run.wins).astype(np.int32), _numpy(run.played), _numpy(run.won_at), n)
 
 
 class Ownership:
@@ -666,37 +656,13 @@ def owner_counts_host(final_recs, records, playouts, komi=L.KOMI):
     return black, white, agree, hist, bw.reshape(records, playouts).sum(1).astype(np.int32)
 
 
-def _playout_ownership_device(recs, n, key, komi, max_plies=MAX_PLIES, table=None, tactics=None):
-    """recs: a uint8 [R,192] tensor on the device -> (value float32 [R], wins int64 [R], black, white, agree, hist,
-    black_wins) on the device: the playout launch without history and one bkt_owner_counts on the final records -- no
-    bkt_area_score, no owner array; nothing here waits for the device."""
-    pos = recs.repeat_interleave(n, 0)                                     # a copy: the caller's records stay
-    _play_random_device(pos, key, L.value_counters_device(recs, n), max_plies, False, table, tactics)
-    counts = T.owner_counts(pos, len(recs), n, komi)
-    bw = counts[4].to(torch.int64)
-    w = torch.where(L.black_to_move(recs), bw, n - bw)
-    return (_value_of_wins(w, n), w, *counts)
-
-
 def playout_ownership(recs, n, seed, rules="device", komi=L.KOMI, device=None, patterns=None, tactics=None):
     """playout_value's n playouts of each record -- the same counters, draws and cap -- with what their final boards tell
     -> Ownership: the value (the same bits), the wins, and the ownership, agreement and margin counts of every record
     (owner_counts_host has the definition).  rules="device": the playout launch without history and one bkt_owner_counts;
     rules="host": the mirror end to end, the same integers.  recs, patterns, tactics: as playout_value."""
-    L.check_rules(rules)
-    table, tactics = _table(patterns), _tactics(tactics)
-    n = _check_playouts(n)
-    _check_records(recs)
-    key = L.seed_u64(seed)
-    if rules == "device":
-        t = L.records_to_device(recs, _device(device, None, recs), clone=False)
-        value, w, *counts = _playout_ownership_device(t, n, key, komi, table=table, tactics=tactics)
-        return Ownership(value.cpu().numpy(), w.cpu().numpy().astype(np.int32), *(c.cpu().numpy() for c in counts), n)
-    recs = np.array(_numpy(recs), np.uint8, order="C")
-    final = _playout_host_wins(recs, n, key, komi, table, tactics, False, final=True)[3]
-    counts = owner_counts_host(final, len(recs), n, komi)
-    w = np.where(L.black_to_move(recs), counts[4], n - counts[4]).astype(np.int32)
-    return Ownership(((2 * w - n).astype(np.float32) / np.float32(n)).astype(np.float32), w, *counts, n)
+    run = _run(recs, n, seed, rules, komi, device, patterns, tactics, score=False, owned=True)
+    return Ownership(_numpy(run.value), _numpy(run.wins).astype(np.int32), *(_numpy(c) for c in run.owner), n)
 
 
 PRIOR_K = 4.0              # amaf_prior's defaults: plausible, and not tuned (DESIGN 19)
@@ -749,11 +715,11 @@ def _move_weights_device(recs, table, tactics):
     return parts[0] if len(parts) == 1 else torch.cat(parts)
 
 
-def _check_mu(mu):
-    mu = float(mu)
-    if not 0.0 <= mu < float("inf"):
-        raise ValueError("mu must be finite and not negative")
-    return mu
+def _not_negative(x, name):
+    x = float(x)
+    if not 0.0 <= x < float("inf"):
+        raise ValueError(f"{name} must be finite and not negative")
+    return x
 
 
 def _log_weights(weights, R):
@@ -764,22 +730,29 @@ def _log_weights(weights, R):
     return np.log(np.maximum(w.astype(np.float64), 1.0))
 
 
+def _over_legal(recs, x, shifted):
+    """What the priors below share: p = exp(shifted(top)) on the legal points (bk_pos_legal_moves), top = the maximum of x
+    [R,81] over them, 0 elsewhere, each row divided by its sum -> float32 [R,81]; 1/81 everywhere in a row without a legal
+    point.  The argument of exp stays with the caller: the three of them round differently."""
+    legal = legal_host(recs)
+    some = legal.any(1)
+    top = np.where(legal, x, -np.inf).max(1, keepdims=True)
+    top[~some] = 0.0
+    p = np.where(legal, np.exp(shifted(top)), 0.0)
+    p[~some] = 1.0
+    return (p / p.sum(1, keepdims=True)).astype(np.float32)
+
+
 def pattern_prior(recs, weights, mu=1.0):
     """The move predictor's own prediction -> float32 [R,81], in float64 on the host: with weights = move_weights(recs, ...),
     p_s = exp(mu * (ln max(w_s, 1) - the maximum over the legal points)) on the legal points (bk_pos_legal_moves), 0
     elsewhere, each row divided by its sum; a record without a legal point gets 1/81 everywhere.  mu = 1: in proportion to
     the weights.  mu must be finite and not negative."""
-    mu = _check_mu(mu)
+    mu = _not_negative(mu, "mu")
     recs = np.array(_numpy(recs), np.uint8, order="C")
     _check_records(recs)
     lw = _log_weights(weights, len(recs))
-    legal = legal_host(recs)
-    top = np.where(legal, lw, -np.inf).max(1, keepdims=True)
-    some = legal.any(1)
-    top[~some] = 0.0
-    p = np.where(legal, np.exp(mu * (lw - top)), 0.0)
-    p[~some] = 1.0
-    return (p / p.sum(1, keepdims=True)).astype(np.float32)
+    return _over_legal(recs, lw, lambda top: mu * (lw - top))
 
 
 def amaf_prior(recs, amaf, k=PRIOR_K, temperature=PRIOR_TEMPERATURE, criticality=None, gamma=0.0, weights=None, mu=0.0):
@@ -796,11 +769,10 @@ def amaf_prior(recs, amaf, k=PRIOR_K, temperature=PRIOR_TEMPERATURE, criticality
     (q_s + gamma * criticality_s) / temperature + mu * ln(max(w_s, 1)), shifted by its maximum over the legal points before
     exp (mu is untuned); a legal point off the playable set (an own eye) enters with the least weight, 1.
     weights=None or mu == 0: the floats above, bit for bit.  mu must be finite and not negative."""
-    k, temperature, gamma, mu = float(k), float(temperature), float(gamma), _check_mu(mu)
+    k, temperature, mu = float(k), float(temperature), _not_negative(mu, "mu")
     if not k > 0 or not temperature > 0:
         raise ValueError("k and temperature must be greater than 0")
-    if not 0.0 <= gamma < float("inf"):
-        raise ValueError("gamma must be finite and not negative")
+    gamma = _not_negative(gamma, "gamma")
     recs = np.array(_numpy(recs), np.uint8, order="C")
     _check_records(recs)
     played, won = np.asarray(amaf.played, np.float64), np.asarray(amaf.won, np.float64)
@@ -815,19 +787,10 @@ def amaf_prior(recs, amaf, k=PRIOR_K, temperature=PRIOR_TEMPERATURE, criticality
         if crit.shape != q.shape:
             raise ValueError(f"criticality must be [{len(recs)}, 81], one row per record")
         q = q + gamma * crit
-    legal = legal_host(recs)
-    some = legal.any(1)
     if weights is not None and mu > 0.0:
         z = q / temperature + mu * _log_weights(weights, len(recs))
-        top = np.where(legal, z, -np.inf).max(1, keepdims=True)
-        top[~some] = 0.0
-        p = np.where(legal, np.exp(z - top), 0.0)
-    else:
-        top = np.where(legal, q, -np.inf).max(1, keepdims=True)
-        top[~some] = 0.0
-        p = np.where(legal, np.exp((q - top) / temperature), 0.0)
-    p[~some] = 1.0
-    return (p / p.sum(1, keepdims=True)).astype(np.float32)
+        return _over_legal(recs, z, lambda top: z - top)
+    return _over_legal(recs, q, lambda top: (q - top) / temperature)
 
 
 class PlayoutEvaluator:
@@ -863,16 +826,12 @@ class PlayoutEvaluator:
                  prior_patterns=None, prior_tactics=None):
         L.check_rules(rules)
         self.rave = bool(rave)
-        self.criticality = float(criticality)
-        if not 0.0 <= self.criticality < float("inf"):
-            raise ValueError("criticality must be finite and not negative")
+        self.criticality = _not_negative(criticality, "criticality")
         if self.criticality > 0.0 and not float(prior) > 0.0:
             raise ValueError("criticality is a term of the playout prior: it needs prior > 0")
         self.patterns = _table(patterns)                                  # None: uniformly random playouts
         self.tactics = _tactics(tactics)                                  # None: no tactical weights
-        self.pattern_prior = float(pattern_prior)
-        if not 0.0 <= self.pattern_prior < float("inf"):
-            raise ValueError("pattern_prior must be finite and not negative")
+        self.pattern_prior = _not_negative(pattern_prior, "pattern_prior")
         if self.pattern_prior > 0.0 and not float(prior) > 0.0:
             raise ValueError("pattern_prior is a term of the playout prior: it needs prior > 0")
         self.prior_patterns = self.patterns if prior_patterns is None else _table(prior_patterns)
@@ -903,86 +862,42 @@ class PlayoutEvaluator:
         if n_policy and self.prior < 1.0:
             ticket = self.policy_engine.submit_positions(recs[:n_policy], logits=False, probs=True, value=False,
                                                          n_policy=n_policy)
-        more = dict(komi=self.komi, table=self.patterns, tactics=self.tactics)
-        owned = n_policy if n_policy and self.criticality > 0.0 else 0   # rows whose final boards are counted (then prior > 0)
-        final = ()                                                        # (the host's final records, when they are counted)
-        t = None                                                          # (the records on the device, with the device rules)
-        if self.rave:                                                     # every row with its history, both sides counted
-            if self.rules == "host":
-                values, w, moves, *final = _playout_host_wins(recs, self.playouts, self.seed, history=True,
-                                                              final=bool(owned), **more)
-                counts = amaf_counts_sides_host(moves, w.reshape(-1), len(recs), self.playouts)
-                w = w.sum(1)
-            else:
-                t = torch.from_numpy(recs).to(_device(None, self.policy_engine))
-                values, w, *counts = _playout_amaf_device(t, self.playouts, self.seed, sides=2, owned=owned, **more)
-            counted = (recs[:n_policy], n_policy) if n_policy and self.prior > 0.0 else None
-            if owned:
-                counted += (self._owned(final, counts, owned),)
-            if counted is not None and self.pattern_prior > 0.0:
-                counted += (self._weights(recs, t, n_policy),)
-            return ticket, values, counted, (w, *counts[:2])
-        if n_policy and self.prior > 0.0:                                 # the playouts with their history, and the counts
-            if self.rules == "host":
-                values, w, moves, *final = _playout_host_wins(recs, self.playouts, self.seed, history=True,
-                                                              final=bool(owned), **more)
-                counts = amaf_counts_host(moves[:n_policy * self.playouts], w[:n_policy].reshape(-1), n_policy, self.playouts)
-                w = w.sum(1)
-            else:
-                t = torch.from_numpy(recs).to(_device(None, self.policy_engine))
-                values, w, *counts = _playout_amaf_device(t, self.playouts, self.seed, counted=n_policy, owned=owned, **more)
-            counted = (recs[:n_policy], w[:n_policy], *counts[:2])
-            counted += (self._owned(final, counts, owned),) if owned else ()
-            return ticket, values, counted + ((self._weights(recs, t, n_policy),) if self.pattern_prior > 0.0 else ())
-        if self.rules == "host":
-            values = _playout_host_wins(recs, self.playouts, self.seed, history=False, **more)[0]
-        else:
-            values = _playout_value_device(torch.from_numpy(recs).to(_device(None, self.policy_engine)), self.playouts,
-                                           self.seed, **more)
-        return ticket, values, None
-
-    def _owned(self, final, counts, owned):
-        """The owner counts of the first `owned` rows: from the host's final records, or the fifth element of
-        _playout_amaf_device's result."""
-        if self.rules == "host":
-            return owner_counts_host(final[0][:owned * self.playouts], owned, self.playouts, self.komi)
-        return counts[2]
-
-    def _weights(self, recs, t, n_policy):
-        """The move weights of the first n_policy rows: the host mirror, or one bkt_move_weights on the records t already
-        on the device (nothing waits for it)."""
-        if self.rules == "host":
-            return move_weights_host(recs[:n_policy], self.prior_patterns, self.prior_tactics)
-        return _move_weights_device(t[:n_policy], self.prior_patterns, self.prior_tactics)
+        counted = n_policy if n_policy and self.prior > 0.0 else 0        # the rows whose prior the playouts have a share in
+        weights, host = None, self.rules == "host"
+        t = recs if host else torch.from_numpy(recs).to(_device(None, self.policy_engine))
+        # rave: every row with its history, both sides counted, and the prior reads side 0 of the first rows of those counts
+        run = _playouts(t, self.playouts, self.seed, self.rules, self.komi, self.patterns, self.tactics,
+                        counted=len(recs) if self.rave else counted, sides=2 if self.rave else 1,
+                        owned=counted if self.criticality > 0.0 else 0)
+        if counted and self.pattern_prior > 0.0:                          # (the device's launch: nothing waits for it)
+            weights = (move_weights_host if host else _move_weights_device)(t[:counted], self.prior_patterns, self.prior_tactics)
+        return SimpleNamespace(ticket=ticket, run=run, n_policy=counted, weights=weights, recs=recs[:counted])
 
     def finish(self, handle, normalise=None):
-        ticket, values, counted, *rave = handle
-        owned = weights = None
-        if counted is not None and self.pattern_prior > 0.0:             # the last element: the move weights
-            counted, weights = counted[:-1], _numpy(counted[-1])
-        if counted is not None and self.criticality > 0.0:               # the last element: the owner counts
-            counted, owned = counted[:-1], [_numpy(x) for x in counted[-1]]
+        run, n = handle.run, handle.n_policy
         if normalise is None:
             from .selfplay import normalise_like_categorical as normalise
-        probs = np.zeros((0, 81), np.float32) if ticket is None else self.policy_engine.wait(ticket)["probs"]
+        probs = np.zeros((0, 81), np.float32) if handle.ticket is None else self.policy_engine.wait(handle.ticket)["probs"]
         records = None
-        if rave:                                                          # (w, played, won_at) of every row, two-sided
-            w, played, won = (np.ascontiguousarray(_numpy(x), np.int32) for x in rave[0])
+        if self.rave or n:
+            w, played, won = (_numpy(x) for x in (run.wins, run.played, run.won_at))
+        if self.rave:                                                     # (w, played, won_at) of every row, two-sided
+            w, played, won = (np.ascontiguousarray(x, np.int32) for x in (w, played, won))
             records = (self.playouts, w, played, won)
-            if counted is not None:
-                counted = (counted[0], w[:counted[1]], played[:counted[1]], won[:counted[1]])
-        if counted is not None:
-            recs, w, played, won = (_numpy(x) for x in counted)
-            crit = None if owned is None else criticality_of(owned[0], owned[1], owned[2], owned[4], self.playouts)
-            prior = amaf_prior(recs, Amaf(None, w, played, won, self.playouts), self.prior_k, self.prior_temperature,
-                               criticality=crit, gamma=self.criticality, weights=weights, mu=self.pattern_prior)
-            if ticket is not None:
+        if n:
+            crit = None
+            if run.owner is not None:
+                black, white, agree, _, black_wins = (_numpy(x) for x in run.owner)
+                crit = criticality_of(black, white, agree, black_wins, self.playouts)
+            prior = amaf_prior(handle.recs, Amaf(None, w[:n], played[:n], won[:n], self.playouts), self.prior_k,
+                               self.prior_temperature, criticality=crit, gamma=self.criticality, weights=_numpy(handle.weights),
+                               mu=self.pattern_prior)
+            if handle.ticket is not None:
                 prior = ((1.0 - self.prior) * probs.astype(np.float64) + self.prior * prior.astype(np.float64))
             probs = prior.astype(np.float32)
         if len(probs):
             probs = normalise(probs)
-        values = values if isinstance(values, np.ndarray) else values.cpu().numpy()
-        return (probs, values, records) if records is not None else (probs, values)
+        return (probs, _numpy(run.value), records) if records is not None else (probs, _numpy(run.value))
 
     def __call__(self, recs, n_policy):
         return self.finish(self.submit(recs, n_policy))

@@ -21,6 +21,7 @@ import time
 import numpy as np
 
 from . import go
+from .playout_options import PlayoutOptions
 
 # ---- ctypes view of include/bokego_tree.h ------------------------------------------------------------
 
@@ -857,55 +858,13 @@ def parse_args(argv=None):
     ap.add_argument("--task-cap", type=int, default=None, help="soft limit of a batch in network tasks (default: whole rounds of workgroups for fp32, none for f16x2; 0: none)")
     ap.add_argument("--replay-shard", metavar="RANK/WORLD", default=None,
                     help="re-play the games a failed rank owned (e.g. 3/8: the gids with gid %% 8 == 3) in this process")
-    ap.add_argument("--playout-value", type=int, default=0, metavar="N",
-                    help="N > 0: no value net is loaded -- a leaf's value is the share of N random playouts its side to move wins "
-                         "(rollout.PlayoutEvaluator; not with --value or --host-encode)")
-    ap.add_argument("--playout-prior", type=float, default=0.0, metavar="LAMBDA",
-                    help="with --playout-value: that share (0..1) of the priors comes from the playouts' AMAF counts; with 1 no "
-                         "policy net is loaded either (not with --policy): self-play from no network at all")
-    ap.add_argument("--playout-patterns", default=None, metavar="FILE",
-                    help="with --playout-value: the table of 3x3 pattern weights its playouts draw their moves by")
-    ap.add_argument("--playout-tactics", default=None, metavar="FILE",
-                    help="with --playout-value: the table of tactical weights that multiply its playouts' weights")
-    ap.add_argument("--playout-criticality", type=float, default=0.0, metavar="GAMMA",
-                    help="with --playout-prior: GAMMA times Coulom's criticality of each point is added to the AMAF win rates of the "
-                         "prior (untuned; default 0: off)")
-    ap.add_argument("--playout-pattern-prior", type=float, default=0.0, metavar="MU",
-                    help="with --playout-prior: add MU times the log of each point's move weight -- the playouts' pattern and "
-                         "tactical tables, or --prior-patterns / --prior-tactics -- to the prior's logits (untuned; default 0: "
-                         "off, DESIGN 22)")
-    ap.add_argument("--prior-patterns", default=None, metavar="FILE",
-                    help="with --playout-pattern-prior: the pattern table of that term (default: --playout-patterns)")
-    ap.add_argument("--prior-tactics", default=None, metavar="FILE",
-                    help="with --playout-pattern-prior: the tactics table of that term (default: --playout-tactics)")
+    PlayoutOptions.add_arguments(ap, rave=False)                      # --playout-value N: not with --value or --host-encode
     args = ap.parse_args(argv)
-    if args.playout_value < 0:
-        ap.error("--playout-value must not be negative")
+    args.playout = PlayoutOptions.from_args(ap, args)
     if args.playout_value:
         for flag, on in (("--value", args.value is not None), ("--host-encode", args.host_encode)):
             if on:
                 ap.error(f"--playout-value takes the place of a value net on position records: not allowed with {flag}")
-    if not 0.0 <= args.playout_prior <= 1.0:
-        ap.error("--playout-prior must be within 0..1")
-    for flag, given in (("--playout-prior", args.playout_prior), ("--playout-patterns", args.playout_patterns is not None),
-                        ("--playout-tactics", args.playout_tactics is not None)):
-        if given and not args.playout_value:
-            ap.error(f"{flag} goes with the playouts of --playout-value: it needs --playout-value N")
-    if not 0.0 <= args.playout_criticality < float("inf"):
-        ap.error("--playout-criticality must be a finite number, 0 or more")
-    if args.playout_criticality and not args.playout_prior:
-        ap.error("--playout-criticality is a term of the playout prior: it needs --playout-prior")
-    if not 0.0 <= args.playout_pattern_prior < float("inf"):
-        ap.error("--playout-pattern-prior must be a finite number, 0 or more")
-    if args.playout_pattern_prior and not args.playout_prior:
-        ap.error("--playout-pattern-prior is a term of the playout prior: it needs --playout-prior")
-    for flag, given in (("--prior-patterns", args.prior_patterns), ("--prior-tactics", args.prior_tactics)):
-        if given is not None and not args.playout_pattern_prior:
-            ap.error(f"{flag} is the table of --playout-pattern-prior: it needs --playout-pattern-prior MU")
-    if args.playout_pattern_prior and all(t is None for t in (args.playout_patterns, args.playout_tactics,
-                                                              args.prior_patterns, args.prior_tactics)):
-        ap.error("--playout-pattern-prior needs a table: --playout-patterns, --playout-tactics, --prior-patterns or "
-                 "--prior-tactics")
     if args.playout_prior == 1.0 and args.policy is not None:
         ap.error("--playout-prior 1 searches without a policy net: not allowed with --policy")
     return args
@@ -948,10 +907,7 @@ def main(argv=None):
         if args.playout_prior != 1.0:
             eng = LeafEngine(load(args.policy, "policy_19.bkw"), None, device_id=local_rank, max_batch=args.max_batch,
                              precision=args.precision)
-        ev = PlayoutEvaluator(eng, args.playout_value, patterns=args.playout_patterns, tactics=args.playout_tactics,
-                              prior=args.playout_prior, criticality=args.playout_criticality,
-                              pattern_prior=args.playout_pattern_prior, prior_patterns=args.prior_patterns,
-                              prior_tactics=args.prior_tactics)
+        ev = PlayoutEvaluator(eng, **args.playout.evaluator_keywords())
     else:
         eng = LeafEngine(load(args.policy, "policy_19.bkw"), load(args.value, "value_synth.bkw"), device_id=local_rank,
                          max_batch=args.max_batch, precision=args.precision)

@@ -102,7 +102,7 @@ def five_by_seven():
     late = [i for i in range(len(gold)) if (gold[i, :81] != 0).sum() > 45]
     recs = gold[late[::max(1, len(late) // 5)][:5]]
     assert len(recs) == 5 and len(set(L.black_to_move(recs).tolist())) == 2
-    final = RO._playout_host_wins(recs, 7, L.seed_u64(11), L.KOMI, None, None, False, final=True)[3]
+    final = RO._playouts(recs, 7, L.seed_u64(11), rules="host", final=True).final
     return recs, final
 
 

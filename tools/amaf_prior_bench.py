@@ -64,8 +64,8 @@ def bench_time(recs, playouts, reps, seed):
             best[name] = min(dt, best.get(name, dt))
     assert np.array_equal(last["amaf"].value, last["value"])
     # the reduction alone, on the history of these playouts
-    won, moves = rollout._playouts_won_device(recs, playouts, L.seed_u64(seed), L.KOMI, rollout.MAX_PLIES, None, None, True)
-    won = won.to(torch.uint8).reshape(-1)
+    run = rollout._playouts(recs, playouts, L.seed_u64(seed), rules="device", history=True)
+    won, moves = run.won.to(torch.uint8).reshape(-1), run.moves
     ms = []
     for _ in range(reps + 1):                                        # the first is the warm-up
         a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)

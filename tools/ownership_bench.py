@@ -94,7 +94,7 @@ def composed(pos, records, playouts, komi):
 
 
 def bench_kernel(recs, playouts, reps, seed):
-    pos = rollout._playouts_final_device(recs, playouts, L.seed_u64(seed), L.KOMI, rollout.MAX_PLIES, None, None, False)[2]
+    pos = rollout._playouts(recs, playouts, L.seed_u64(seed), rules="device", final=True).final
     R = len(recs)
     paths = {"fused": lambda: T.owner_counts(pos, R, playouts, L.KOMI), "composed": lambda: composed(pos, R, playouts, L.KOMI)}
     f, c = paths["fused"](), paths["composed"]()                       # warm-up, and the same integers

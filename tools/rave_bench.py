@@ -53,8 +53,8 @@ def _event_ms(fn):
 
 
 def bench_kernel(recs, playouts, reps, seed):
-    won, moves = rollout._playouts_won_device(recs, playouts, L.seed_u64(seed), L.KOMI, rollout.MAX_PLIES, None, None, True)
-    won = won.to(torch.uint8).reshape(-1)
+    run = rollout._playouts(recs, playouts, L.seed_u64(seed), rules="device", history=True)
+    won, moves = run.won.to(torch.uint8).reshape(-1), run.moves
     paths = {"sides": lambda: T.amaf_counts_sides(moves, won, len(recs), playouts),
              "one_side": lambda: T.amaf_counts(moves, won, len(recs), playouts)}
     two, one = paths["sides"](), paths["one_side"]()                  # warm-up, and the same integers
