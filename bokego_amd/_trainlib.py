@@ -53,6 +53,9 @@ SYMBOLS = {
     "bkt_amaf_counts_sides": (_I, [_P, _I, _P, _I, _I, _P, _P, _P]),
     "bkt_owner_counts": (_I, [_P, _I, _I, _F, _P, _P, _P, _P, _P, _P]),
     "bkt_move_weights": (_I, [_P, _I, _P, _P, _P, _P]),
+    "bkt_reply_playouts": (_I, [_P, _I, _U64, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P]),
+    "bkt_reply_scratch_bytes": (_Z, [_I]),
+    "bkt_reply_update": (_I, [_P, _P, _I, _P, _I, _I, _P, _P, _P]),
 }
 MAX_BATCH = 65536          # BKT_MAX_BATCH
 PRECISIONS = ("fp32", "bf16")
@@ -62,6 +65,7 @@ MAX_PLAYOUT_PLIES = 1024   # BKT_MAX_PLAYOUT_PLIES
 PATTERN_ENTRIES = 131072   # BKT_PATTERN_ENTRIES
 TACTIC_ENTRIES = 64        # BKT_TACTIC_ENTRIES
 MAX_SAMPLE_ROWS = 1 << 24  # BKT_MAX_SAMPLE_ROWS
+REPLY_NONE = 255           # BKT_REPLY_NONE: a reply table's entry for "no reply"
 
 _lib = None
 
@@ -514,3 +518,38 @@ def move_weights(pos, table=None, tactics=None):
                                    None if tactics is None else _dev(tactics, "tactics", (TACTIC_ENTRIES,), torch.int16),
                                    _dev(weights, "weights", dtype=torch.int32), _stream(pos)), "bkt_move_weights")
     return weights
+
+
+def reply_playouts(pos, seed, counters, table, tactics, replies, max_plies, over=None, history=True):
+    """tactical_playouts whose draw asks a last-good-reply table first (bkt_reply_playouts; include/bokego_train.h has the
+    rule): replies uint8 [2,81] on the device of pos, read only; table and tactics: tactical_playouts' tables, each of which
+    may be None here (neither: the uniform draw)."""
+    for t in (table, tactics, replies):
+        if t is not None and (not isinstance(t, torch.Tensor) or t.device != pos.device):
+            raise ValueError("the pattern table, the tactics table and the reply table must be on the device of pos")
+    return _playouts("bkt_reply_playouts", pos, seed, counters,
+                     (None if table is None else _dev(table, "table", (PATTERN_ENTRIES,), torch.int16),
+                      None if tactics is None else _dev(tactics, "tactics", (TACTIC_ENTRIES,), torch.int16),
+                      _dev(replies, "replies", (2, 81), torch.uint8)), max_plies, over, history)
+
+
+def reply_update(pos, moves, won, records, playouts, replies, scratch=None):
+    """Fold a batch of playouts into a last-good-reply table, in place (bkt_reply_update; include/bokego_train.h has the
+    rule): pos uint8 [records,192], the starting records (read only); moves and won as amaf_counts_sides takes them; replies
+    uint8 [2,81].  scratch: None (allocated here) or a uint8 tensor of at least bkt_reply_scratch_bytes(records) bytes.  Two
+    launches on the current stream; nothing waits.  -> replies."""
+    records, playouts, max_plies = _amaf_args(moves, won, records, playouts)
+    if not isinstance(pos, torch.Tensor) or tuple(pos.shape) != (records, POS_BYTES) or pos.device != moves.device:
+        raise ValueError(f"pos must be [{records}, {POS_BYTES}] on the device of moves")
+    if not isinstance(replies, torch.Tensor) or replies.device != moves.device:
+        raise ValueError("replies must be on the device of moves")
+    need = load().bkt_reply_scratch_bytes(records)
+    if scratch is None:
+        scratch = torch.empty((need,), dtype=torch.uint8, device=moves.device)
+    elif not isinstance(scratch, torch.Tensor) or scratch.device != moves.device or scratch.dim() != 1 or scratch.numel() < need:
+        raise ValueError(f"scratch must be uint8 [>= {need}] on the device of moves")
+    _check(load().bkt_reply_update(_dev(pos, "pos", dtype=torch.uint8), _dev(moves, "moves", dtype=torch.int16), max_plies,
+                                   _dev(won, "won", (records * playouts,), torch.uint8), records, playouts,
+                                   _dev(replies, "replies", (2, 81), torch.uint8), _dev(scratch, "scratch", dtype=torch.uint8),
+                                   _stream(moves)), "bkt_reply_update")
+    return replies

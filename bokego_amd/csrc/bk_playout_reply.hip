@@ -1,0 +1,236 @@
+// bk_playout_reply.hip -- included as text at the end of bk_playout_pat.hip, after bk_playout_tac.hip (it is no translation
+// unit of its own): the last-good-reply playouts of bokego_amd/rollout.py (include/bokego_train.h has the two rules; DESIGN
+// 24).  bkt_reply_playouts is bkt_tactical_playouts whose draw asks a reply table first (ReplyDraw around WeightedDraw, or
+// around the uniform draw when there is no table to weigh with); bkt_reply_update folds the histories of a batch of playouts
+// and their winners back into that table, in two launches: reply_summaries_kernel, one workgroup per record, and
+// reply_apply_kernel, one workgroup in all.
+
+namespace {
+
+constexpr int REPLY_ENTRIES = 2 * NN;                                // replies[colour][previous move]
+constexpr int REPLY_WORDS = 4;                                       // a summary: three words of F, then set << 8 | value
+
+// The tactical weight with either table optional: a NULL tactics table is 256 everywhere, which with a pattern table gives
+// bkt_pattern_playouts' weights and without one a constant, bkt_random_playouts' draw (bk_playout_tac.hip).  Its LDS and its
+// two __noinline__ helpers are TacticalWeight's.
+struct OptionalTacticalWeight {
+    const uint16_t* __restrict__ table;
+    const uint16_t* __restrict__ tactics;
+    __device__ __forceinline__ void stage(int tid) const {
+        if (tid < BKT_TACTIC_ENTRIES) TacticalWeight::lds()->tactics[tid] = tactics ? tactics[tid] : (uint16_t)256;
+    }
+    __device__ __forceinline__ void play(unsigned char* pos, int B, unsigned char* over, PlyLds* L) const {
+        play_one_ply_planes(pos, B, over, L, TacticalWeight::lds());
+    }
+    __device__ __forceinline__ unsigned operator()(const PatLds* W, int pp, int q, int lm, bool white_to_move) const {
+        return tactical_weight(W, TacticalWeight::lds(), table, pp, q, lm, white_to_move);
+    }
+};
+
+// The uniform draw with what the reply draw asks of its inner draw: the last move and the turn on entry, carried in registers
+// as WeightedDraw carries them (L.mv still holds the move the body has just played when publish() begins, and is written
+// again only behind publish()'s barrier).
+struct TrackedUniformDraw {
+    UniformDraw inner;
+    int lm, turn0;
+    __device__ __forceinline__ void start(Seat s, int last_move, int turn) {
+        lm = last_move, turn0 = turn;
+        inner.start(s, last_move, turn);
+    }
+    __device__ __forceinline__ void play(unsigned char* pos, int B, unsigned char* over, PlyLds* L) const {
+        inner.play(pos, B, over, L);
+    }
+    __device__ __forceinline__ void publish(Seat s, const PlyLds& L, bool mine, int played) {
+        const int just = L.mv[s.pp];
+        if (just > BKT_MOVE_NONE) lm = just;
+        inner.publish(s, L, mine, played);
+    }
+    __device__ __forceinline__ unsigned total(Seat s) { return inner.total(s); }
+    __device__ __forceinline__ bool picks(uint32_t r24, unsigned n) const { return inner.picks(r24, n); }
+};
+
+// The fourth draw: the inner draw, overruled by the reply table.  start() stages the 162 bytes in LDS, published by the ply
+// loop's first barrier.  publish() is the inner one's -- its last barrier is already behind the thread when the reply is
+// looked up, so no barrier is added: the side to move and the last move are the registers the inner draw carries, the entry
+// is one LDS byte every thread of a row reads at the same address, and whether it is playable is one byte of the set
+// play_body left in L.playable, which nothing writes before the next play().  An entry is compared (<= 80) before it
+// indexes.  Every branch here is per thread and reaches no barrier.  A row that is over, or has no playable point, never
+// gets here with a reply: the loop asks picks() only when total() > 0, and a reply in P makes the total positive.
+template <class Inner>
+struct ReplyDraw {
+    Inner inner;
+    const uint8_t* __restrict__ replies;
+    int q, reply;
+    static __device__ __forceinline__ uint8_t* lds() {
+        __shared__ uint8_t table[REPLY_ENTRIES + 2];
+        return table;
+    }
+    __device__ __forceinline__ void start(Seat s, int last_move, int turn) {
+        if (s.tid < REPLY_ENTRIES) lds()[s.tid] = replies[s.tid];
+        q = s.q;
+        inner.start(s, last_move, turn);
+    }
+    __device__ __forceinline__ void play(unsigned char* pos, int B, unsigned char* over, PlyLds* L) const {
+        inner.play(pos, B, over, L);
+    }
+    __device__ __forceinline__ void publish(Seat s, const PlyLds& L, bool mine, int played) {
+        inner.publish(s, L, mine, played);
+        const int lm = inner.lm;                                     // the move before this ply: the inner draw keeps it
+        reply = -1;
+        if (lm >= 0 && lm < NN) {
+            const int r = lds()[(((inner.turn0 + played) & 1) ? NN : 0) + lm];
+            if (r < NN && L.playable[NN * s.pp + r] != 0) reply = r;
+        }
+    }
+    __device__ __forceinline__ unsigned total(Seat s) { return inner.total(s); }
+    __device__ __forceinline__ bool picks(uint32_t r24, unsigned S) const {
+        return reply >= 0 ? q == reply : inner.picks(r24, S);
+    }
+};
+
+__global__ void __launch_bounds__(256) reply_playouts_kernel(unsigned char* pos, int B, uint32_t k0, uint32_t k1,
+                                                             const uint32_t* __restrict__ counters,
+                                                             const uint16_t* __restrict__ table,
+                                                             const uint16_t* __restrict__ tactics,
+                                                             const uint8_t* __restrict__ replies, int max_plies,
+                                                             unsigned char* over, int32_t* __restrict__ plies,
+                                                             int16_t* __restrict__ hist, int32_t* __restrict__ status) {
+    playouts(pos, B, k0, k1, counters, max_plies, over, plies, hist, status,
+             ReplyDraw<WeightedDraw<OptionalTacticalWeight>>{{{table, tactics}}, replies});
+}
+
+// With neither table the inner draw is the uniform one: bkt_random_playouts' kernel and its cost, not the tactical kernel's
+// with two neutral tables (the same games either way; DESIGN 24 has the times).
+__global__ void __launch_bounds__(256) reply_uniform_playouts_kernel(unsigned char* pos, int B, uint32_t k0, uint32_t k1,
+                                                                     const uint32_t* __restrict__ counters,
+                                                                     const uint8_t* __restrict__ replies, int max_plies,
+                                                                     unsigned char* over, int32_t* __restrict__ plies,
+                                                                     int16_t* __restrict__ hist, int32_t* __restrict__ status) {
+    __shared__ unsigned sel[8];
+    playouts(pos, B, k0, k1, counters, max_plies, over, plies, hist, status,
+             ReplyDraw<TrackedUniformDraw>{{UniformDraw{sel}, 0, 0}, replies});
+}
+
+constexpr int REPLY_WAVES = 4;                                       // rows staged per barrier round
+constexpr int REPLY_ROW = BKT_MAX_PLAYOUT_PLIES;
+
+// The first launch of bkt_reply_update.  One workgroup per record r; thread e < 162 owns the table entry e = 81 c + prev
+// and scans ALL of the record's rows in ascending order -- the fold is sequential in the rows, so unlike
+// amaf_counts_sides_kernel, whose staging this is, a row is not one wave's: the rows of a round are staged by the whole
+// workgroup (coalesced 2-byte loads, padded with BKT_MOVE_NONE to a multiple of 4 entries), and after ONE barrier every
+// thread walks them one after the other by 8-byte LDS reads at the same address in all lanes (a broadcast), so the walk and
+// its end at the first entry <= BKT_MOVE_NONE or at max_plies are workgroup-uniform.  Two buffers alternate: a round costs
+// one barrier.  What the segment of events of these rows does to the entry is kept in registers as a summary:
+//   F      the points m "forgotten" (a loser's reply m) before the first "set" of the segment, an 81-bit mask;
+//   set, v whether a winner's reply was stored, and the value after the segment if so (a point, or 255 when forgotten again).
+// Applied to an entry x: x = (x in F ? 255 : x), then x = v if set.  The summary of events A followed by events B is
+// (A.set ? A.F : A.F | B.F;  A.set | B.set;  B.set ? B.v : A.v in B.F ? 255 : A.v): associative, which is what lets the
+// records be scanned by different workgroups and composed in order by the second launch.  The four words of entry e go to
+// scratch[(r * 4 + j) * 162 + e] with plain stores.  Integers only, no atomics, nothing waits on another workgroup; loop
+// bounds and barriers depend on `playouts` and `max_plies` alone.  An entry of `moves` is only compared, never an index.
+__global__ void __launch_bounds__(64 * REPLY_WAVES) reply_summaries_kernel(const unsigned char* __restrict__ pos,
+                                                                          const int16_t* __restrict__ moves, int max_plies,
+                                                                          const uint8_t* __restrict__ won, int playouts,
+                                                                          uint32_t* __restrict__ scratch) {
+    __shared__ __attribute__((aligned(8))) int16_t rows[2][REPLY_WAVES][REPLY_ROW];
+    const int tid = threadIdx.x;
+    const size_t row0 = (size_t)blockIdx.x * playouts;                 // the record's first row
+    const int padded = (max_plies + 3) & ~3;                           // <= REPLY_ROW
+    const unsigned char* rec = pos + (size_t)blockIdx.x * BK_POS_BYTES;
+    const int lm0 = (short)(*reinterpret_cast<const unsigned*>(rec + OFF_KO) >> 16);
+    const int c0 = *reinterpret_cast<const int*>(rec + OFF_TURN) & 1;  // the colour to move at the record: 0 black, 1 white
+    const int my_c = tid / NN, my_prev = tid < REPLY_ENTRIES ? tid - NN * my_c : -100;   // -100: equals no previous move
+    uint32_t f0 = 0, f1 = 0, f2 = 0;
+    bool set = false;
+    int v = BKT_REPLY_NONE;
+    int buf = 0;
+    for (int j0 = 0; j0 < playouts; j0 += REPLY_WAVES, buf ^= 1) {
+        const int here = min(REPLY_WAVES, playouts - j0);
+        const int16_t* src = moves + (row0 + j0) * max_plies;
+        for (int i = tid; i < padded; i += 64 * REPLY_WAVES) {          // the round's loads first: REPLY_WAVES in flight per thread
+            int16_t e[REPLY_WAVES];
+#pragma unroll
+            for (int w = 0; w < REPLY_WAVES; ++w)
+                e[w] = w < here && i < max_plies ? src[(size_t)w * max_plies + i] : (int16_t)BKT_MOVE_NONE;
+#pragma unroll
+            for (int w = 0; w < REPLY_WAVES; ++w) rows[buf][w][i] = e[w];
+        }
+        __syncthreads();
+        for (int w = 0; w < here; ++w) {                               // in row order: uniform in the workgroup
+            const bool win = won[row0 + j0 + w] != 0;                  // the side to move at the record won the row
+            const int16_t* row = rows[buf][w];
+            int prev = lm0;
+            bool live = true;
+            for (int k = 0; k < padded && live; k += 4) {
+                const uint2 x = *reinterpret_cast<const uint2*>(row + k);
+                const int m[4] = {(int16_t)(x.x & 0xFFFFu), (int16_t)(x.x >> 16), (int16_t)(x.y & 0xFFFFu), (int16_t)(x.y >> 16)};
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    live = live && m[e] > BKT_MOVE_NONE;
+                    // ply k + e has the parity of e (k is a multiple of 4): its mover's colour, and whether the mover won
+                    const bool event = live && m[e] >= 0 && m[e] < NN && prev == my_prev && (c0 ^ (e & 1)) == my_c;
+                    const bool mover_won = win == ((e & 1) == 0);
+                    if (event && mover_won) set = true, v = m[e];
+                    else if (event && set) v = v == m[e] ? BKT_REPLY_NONE : v;
+                    else if (event) {
+                        const uint32_t bit = 1u << (m[e] & 31);
+                        f0 |= m[e] < 32 ? bit : 0u, f1 |= m[e] >= 32 && m[e] < 64 ? bit : 0u, f2 |= m[e] >= 64 ? bit : 0u;
+                    }
+                    prev = m[e];
+                }
+            }
+        }
+    }
+    if (tid < REPLY_ENTRIES) {
+        uint32_t* out = scratch + (size_t)blockIdx.x * REPLY_WORDS * REPLY_ENTRIES + tid;
+        out[0] = f0, out[REPLY_ENTRIES] = f1, out[2 * REPLY_ENTRIES] = f2;
+        out[3 * REPLY_ENTRIES] = (set ? 256u : 0u) | (uint32_t)(v & 255);
+    }
+}
+
+// The second launch: one workgroup; thread e < 162 applies the records' summaries of entry e to replies[e] in record order.
+// The loads do not depend on the entry's value, so they run ahead of the chain of selects.  A value above 80 is in no F.
+__global__ void __launch_bounds__(256) reply_apply_kernel(const uint32_t* __restrict__ scratch, int records,
+                                                          uint8_t* __restrict__ replies) {
+    const int tid = threadIdx.x;
+    if (tid >= REPLY_ENTRIES) return;
+    unsigned x = replies[tid];
+    const uint32_t* in = scratch + tid;
+    for (int r = 0; r < records; ++r, in += REPLY_WORDS * REPLY_ENTRIES) {
+        const uint32_t f0 = in[0], f1 = in[REPLY_ENTRIES], f2 = in[2 * REPLY_ENTRIES], sv = in[3 * REPLY_ENTRIES];
+        const uint32_t word = x < 32u ? f0 : x < 64u ? f1 : f2;
+        if (x < (unsigned)NN && (word >> (x & 31u) & 1u)) x = BKT_REPLY_NONE;
+        if (sv & 256u) x = sv & 255u;
+    }
+    replies[tid] = (uint8_t)x;
+}
+
+}  // namespace
+
+extern "C" int bkt_reply_playouts(void* pos, int batch, uint64_t seed, const uint32_t* counters, const uint16_t* table,
+                                  const uint16_t* tactics, const uint8_t* replies, int max_plies, uint8_t* over,
+                                  int32_t* plies, int16_t* moves, int32_t* status, void* stream) {
+    if (!replies) return BKT_ERR_ARG;
+    if (!table && !tactics)
+        return launch_playouts(reply_uniform_playouts_kernel, pos, batch, seed, counters, max_plies, over, plies, moves, status,
+                               stream, replies);
+    return launch_playouts(reply_playouts_kernel, pos, batch, seed, counters, max_plies, over, plies, moves, status, stream,
+                           table, tactics, replies);
+}
+
+extern "C" size_t bkt_reply_scratch_bytes(int records) {
+    return records < 1 ? 0 : (size_t)records * REPLY_WORDS * REPLY_ENTRIES * sizeof(uint32_t);
+}
+
+extern "C" int bkt_reply_update(const void* pos, const int16_t* moves, int max_plies, const uint8_t* won, int records,
+                                int playouts, uint8_t* replies, void* scratch, void* stream) {
+    if (!pos || !moves || !won || !replies || !scratch || records < 1 || playouts < 1 ||
+        (int64_t)records * playouts > BKT_MAX_SAMPLE_ROWS || max_plies < 1 || max_plies > BKT_MAX_PLAYOUT_PLIES)
+        return BKT_ERR_ARG;
+    hipLaunchKernelGGL(reply_summaries_kernel, dim3(records), dim3(64 * REPLY_WAVES), 0, (hipStream_t)stream,
+                       static_cast<const unsigned char*>(pos), moves, max_plies, won, playouts, static_cast<uint32_t*>(scratch));
+    if (hipGetLastError() != hipSuccess) return BKT_ERR_HIP;
+    hipLaunchKernelGGL(reply_apply_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream,
+                       static_cast<const uint32_t*>(scratch), records, replies);
+    return hipGetLastError() == hipSuccess ? BKT_OK : BKT_ERR_HIP;
+}

@@ -190,6 +190,9 @@ class _GTPProtocol:
 
     def _c_clear_board(self, args, turn):
         self._install_root(self._node(), keep_komi=False)
+        replies = getattr(getattr(self, "evaluator", None), "replies", None)
+        if replies is not None:                                      # --playout-replies: a new game learns its own replies
+            replies.clear()
         return True, ""
 
     def _c_komi(self, args, turn):

@@ -144,7 +144,12 @@ class NativeMCTS:
     boards of the same playouts (bkt_owner_counts), is added to the AMAF win rates the prior is made of (DESIGN 21; untuned);
     `playout_pattern_prior=mu` (> 0, with playout_prior): mu times the log of each point's move weight -- the playouts' own
     pattern and tactical tables, or `prior_patterns=` / `prior_tactics=` in their place (bkt_move_weights) -- is added to the
-    prior's logits (untuned)."""
+    prior's logits (DESIGN 22; untuned);
+    `playout_replies=True` (with playout_value): the evaluator keeps a last-good-reply table that the playouts of this
+    search's requests read and update in submit order, `evaluator.replies` (untuned).  The search stays
+    deterministic per seed.  The table is no part of the search state that travels: a deepcopy gets an evaluator of its own
+    with an empty table (the two searches do not write into one table), and an unpickled tree rebuilds its evaluator, and
+    with it an empty table, on first use."""
 
     def __init__(self, root=None, policy_net=None, value_net=None, **kwargs):
         # OPT-IN, not the reference's search: playout_value=N > 0 -- no value net; a leaf's value is the share of N uniformly
@@ -298,6 +303,9 @@ class NativeMCTS:
             if k not in self._NOT_STATE:
                 setattr(new, k, copy.deepcopy(v, memo))
         new.policy_net, new.value_net, new.evaluator = self.policy_net, self.value_net, self.evaluator
+        if getattr(self, "playout_replies", False):                    # a reply table of its own, empty (class docstring)
+            new.evaluator = new._playout_evaluator(self.policy_net)
+            new.evaluator.komi = self.evaluator.komi
         new._adopt(self._pool.snapshot(0), self._cap)
         return new
 

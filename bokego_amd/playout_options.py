@@ -6,7 +6,7 @@ and NativeMCTS as keywords, declared once, checked once, and turned into the key
     PlayoutOptions.from_keywords(kwargs)        the record of NativeMCTS's keywords; TypeError / ValueError
     .search_keywords()                          the keywords of NativeMCTS / NativeGTP: only the options that are set
     .evaluator_keywords()                       the keywords of rollout.PlayoutEvaluator
-    .name_suffix()                              what match calls such an engine: -mc64-pat-amaf1-rave4
+    .name_suffix()                              what match calls such an engine: -mc64-pat-amaf1-rave4-lgr
 
 Nothing here imports torch or rollout: a front end parses its command line before it loads either.
 """
@@ -40,6 +40,9 @@ FLAGS = {  # field -> (flag, what argparse needs, help)
                        "with --playout-pattern-prior: the pattern table of that term (default: --playout-patterns)"),
     "prior_tactics": ("--prior-tactics", dict(default=None, metavar="FILE"),
                       "with --playout-pattern-prior: the tactics table of that term (default: --playout-tactics)"),
+    "playout_replies": ("--playout-replies", dict(action="store_true"),
+                        "with --playout-value: the playouts of a search learn a last-good-reply table from each other and play "
+                        "its replies where they are playable (untuned; default off, DESIGN 24)"),
 }
 
 
@@ -56,6 +59,10 @@ class PlayoutOptions:
     playout_pattern_prior: float = 0.0  # 0: no pattern term in the prior
     prior_patterns: object = None       # the tables of that term; None: the playouts' own
     prior_tactics: object = None
+    # False: no reply table.  The last field, and none of the constructor's: its default lives on the class, so a
+    # record built without it has the instance attributes (vars()) it had before the option existed, which NativeMCTS copies
+    # onto itself; from_args and from_keywords set it, and so may a caller (opts.playout_replies = True).
+    playout_replies: bool = dataclasses.field(default=False, init=False)
 
     TABLES = ("playout_patterns", "playout_tactics", "prior_patterns", "prior_tactics")
 
@@ -65,15 +72,19 @@ class PlayoutOptions:
         return x is not None if field in self.TABLES else bool(x)
 
     @staticmethod
-    def add_arguments(parser, rave=True):
+    def add_arguments(parser, rave=True, replies=True):
+        """rave=False, replies=False: a front end whose one evaluator serves many games at once (selfplay) takes neither --
+        there are no per-game RAVE records there, and the games would mix their reply tables."""
         for field, (flag, kw, text) in FLAGS.items():
-            if rave or field != "playout_rave":
+            if (rave or field != "playout_rave") and (replies or field != "playout_replies"):
                 parser.add_argument(flag, help=text, **kw)
 
     @classmethod
     def from_args(cls, parser, args):
         """The record of a parsed command line; a refused combination ends in parser.error, which names the flag."""
-        self = cls(**{f: getattr(args, f) for f in FLAGS if hasattr(args, f)})
+        self = cls(**{f: getattr(args, f) for f in FLAGS if hasattr(args, f) and f != "playout_replies"})
+        if hasattr(args, "playout_replies"):
+            self.playout_replies = bool(args.playout_replies)
         self.check(lambda field: FLAGS[field][0], lambda kind, text: parser.error(text), command_line=True)
         return self
 
@@ -89,6 +100,7 @@ class PlayoutOptions:
                    *(float(kwargs.get(f) or 0.0) for f in ("playout_prior", "playout_rave", "playout_criticality",
                                                             "playout_pattern_prior")),
                    kwargs.get("prior_patterns"), kwargs.get("prior_tactics"))
+        self.playout_replies = bool(kwargs.get("playout_replies"))
         self.check(str, fail)
         return self
 
@@ -98,7 +110,7 @@ class PlayoutOptions:
         value, prior = name("playout_value"), name("playout_prior")
         if self.playout_value < 0:
             fail(ValueError, f"{value} must not be negative")
-        for field in ("playout_patterns", "playout_tactics", "playout_prior", "playout_rave"):
+        for field in ("playout_patterns", "playout_tactics", "playout_prior", "playout_rave", "playout_replies"):
             if self.given(field) and not self.playout_value:
                 fail(TypeError, f"{name(field)} goes with the playouts of {value}: it needs {value}")
         if not 0.0 <= self.playout_prior <= 1.0:
@@ -122,7 +134,7 @@ class PlayoutOptions:
     def search_keywords(self):
         """The keywords of NativeMCTS / NativeGTP: the options that are set, and no others."""
         more = {f: getattr(self, f) for f in ("playout_value", "playout_patterns", "playout_tactics", "playout_prior",
-                                              "playout_rave", "playout_criticality") if self.given(f)}
+                                              "playout_rave", "playout_criticality", "playout_replies") if self.given(f)}
         if self.playout_pattern_prior:
             more.update(playout_pattern_prior=self.playout_pattern_prior, prior_patterns=self.prior_patterns,
                         prior_tactics=self.prior_tactics)
@@ -135,15 +147,18 @@ class PlayoutOptions:
                 if self.given(f)}
         if self.playout_rave:
             more["rave"] = True
+        if self.playout_replies:
+            more["replies"] = True
         if self.playout_pattern_prior:
             more.update(pattern_prior=self.playout_pattern_prior, prior_patterns=self.prior_patterns,
                         prior_tactics=self.prior_tactics)
         return dict(playouts=self.playout_value, seed=self.playout_seed, rules=self.playout_rules, **more)
 
     def name_suffix(self):
-        """-mc64, then -pat with a playout table and -amaf, -rave, -crit, -pp with their parameters, for the terms that are on."""
+        """-mc64, then -pat with a playout table, -amaf, -rave, -crit, -pp with their parameters for the terms that are on, and
+        -lgr with the reply table."""
         name = f"-mc{self.playout_value}" + ("-pat" if self.given("playout_patterns") or self.given("playout_tactics") else "")
         for tag, x in (("amaf", self.playout_prior), ("rave", self.playout_rave), ("crit", self.playout_criticality),
                        ("pp", self.playout_pattern_prior)):
             name += f"-{tag}{x:g}" if x else ""
-        return name
+        return name + ("-lgr" if self.playout_replies else "")

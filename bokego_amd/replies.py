@@ -1,0 +1,153 @@
+"""The last-good-reply table of the playouts (LGRF-1: Drake 2009, Baier & Drake 2010), its host mirror and the
+two rules in numpy.  include/bokego_train.h has the definition the kernels, this module and the docs share:
+
+    replies uint8 [2,81]    replies[c, prev]: the reply of colour c (0 black, 1 white) to the opponent's move on the board
+                            point prev; 0..80 a point, NONE = 255 none, any other value above 80 treated as none
+    use       (reply_moves)        in a playout, the side to move plays replies[c, last move] when that is a point of the
+                                   playable set; otherwise the playout's own draw decides
+    update    (reply_update_host)  after a batch of playouts, rows and plies in ascending order: the winner's replies are
+                                   stored, the loser's are taken out where the table still holds them
+
+rollout.py's playouts take a ReplyTable as replies= and update it in place; with rules="device" the live copy is a tensor
+on the device (bkt_reply_playouts reads it, bkt_reply_update writes it) and `.array` downloads it when asked.
+"""
+import numpy as np
+
+from . import lockstep as L
+
+NONE = 255                 # BKT_REPLY_NONE
+MOVE_NONE = -2             # BKT_MOVE_NONE
+
+__all__ = ["NONE", "ReplyTable", "reply_moves", "reply_update_host"]
+
+
+class ReplyTable:
+    """uint8 [2,81] replies (module docstring).  `.array` is the table on the host; device(dev) is a cached tensor on dev
+    that the device playouts read and update in place -- whichever was written last is the table, and the other is brought
+    up to date when it is asked for (`.array` after a device update waits for that device)."""
+
+    def __init__(self, array):
+        array = np.asarray(array)
+        if array.shape != (2, 81) or array.dtype != np.uint8:
+            raise ValueError(f"a reply table is uint8 [2, 81], got {array.dtype} {array.shape}")
+        self._array = np.array(array, np.uint8, order="C")
+        self._device = {}
+        self._live = None                                             # the device whose tensor is newer than _array
+
+    @classmethod
+    def empty(cls):
+        return cls(np.full((2, 81), NONE, np.uint8))
+
+    @property
+    def array(self):
+        if self._live is not None:
+            self._array[...] = self._device[self._live].cpu().numpy()
+            self._live = None                                         # the caller may write to the array: upload it next time
+        return self._array
+
+    def copy(self):
+        return ReplyTable(self.array)
+
+    def clear(self):
+        """Every entry NONE, in place."""
+        self.array[...] = NONE
+
+    def occupancy(self):
+        """The number of entries that hold a point."""
+        return int((self.array <= 80).sum())
+
+    def device(self, dev):
+        """uint8 [2,81] on dev, the table itself from here on: what _trainlib.reply_playouts reads and reply_update writes."""
+        import torch
+        dev = torch.device(dev)
+        if dev.type == "cuda" and dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        if self._live != dev:
+            host = torch.from_numpy(self.array.copy())                # (.array: first down from another device, if any)
+            if dev in self._device:
+                self._device[dev].copy_(host)
+            else:
+                self._device[dev] = host.to(dev)
+            self._live = dev
+        return self._device[dev]
+
+    def __deepcopy__(self, memo):
+        return self.copy()
+
+    def __getstate__(self):
+        return {"array": self.array.copy()}
+
+    def __setstate__(self, state):
+        self.__init__(state["array"])
+
+
+def _host_array(table):
+    return table.array if isinstance(table, ReplyTable) else np.asarray(table)
+
+
+def reply_moves(table, recs, playable):
+    """The use rule for rows: recs uint8 [R,192], playable bool [R,81] -> int64 [R]: the reply the table makes the side to
+    move play, or -1 where it decides nothing (the last move is no board point, the entry is no point, or the point is
+    not playable).  An entry is compared before it indexes."""
+    t = _host_array(table)
+    lm = L.record_last_move(recs).astype(np.int64)
+    c = (L.record_turns(recs) & 1).astype(np.int64)
+    on_board = (lm >= 0) & (lm <= 80)
+    r = np.where(on_board, t[c, np.where(on_board, lm, 0)], NONE).astype(np.int64)
+    ok = (r <= 80) & np.asarray(playable)[np.arange(len(recs)), np.minimum(r, 80)]
+    return np.where(ok, r, -1)
+
+
+def reply_plies_of(table, recs, moves, playouts):
+    """The plies of finished playouts that `table` (as it stood while they ran) decided, counted from their history: recs
+    uint8 [records,192] the starting records, moves int16 [records * playouts, L].  A playable reply is always played and
+    a played move was playable, so the table decided ply t exactly when moves[row, t] is its reply to the move before."""
+    t = _host_array(table)
+    moves = np.asarray(moves).astype(np.int64)
+    lm0 = np.repeat(L.record_last_move(recs).astype(np.int64), playouts)
+    c0 = np.repeat((L.record_turns(recs) & 1).astype(np.int64), playouts)
+    prev = np.concatenate([lm0[:, None], moves[:, :-1]], 1)
+    live = np.cumsum(moves <= MOVE_NONE, 1) == 0
+    c = c0[:, None] ^ (np.arange(moves.shape[1]) & 1)[None, :]
+    ok = live & (moves >= 0) & (moves <= 80) & (prev >= 0) & (prev <= 80)
+    return int((ok & (t[c, np.clip(prev, 0, 80)] == moves)).sum())
+
+
+def reply_update_host(table, recs, moves, won, records, playouts):
+    """bkt_reply_update on the host, the sequential fold itself: table a ReplyTable (or a uint8 [2,81] array), updated in
+    place; recs uint8 [records,192], the starting records; moves int16 [records * playouts, max_plies] and won
+    [records * playouts] as amaf_counts_sides_host takes them.  Rows ascending, plies ascending up to the first entry
+    <= MOVE_NONE: with c the mover's colour ((turn of the record + t) & 1), prev the record's last move at t = 0 and
+    moves[row, t - 1] after it, m = moves[row, t] -- when both are board points, a mover who won the row stores
+    table[c, prev] = m, and one who lost clears the entry if it holds m.
+    -> (set, cleared, nothing): the events that stored, that cleared, and that did neither."""
+    t = _host_array(table)
+    records, playouts = int(records), int(playouts)
+    recs, moves, won = np.asarray(recs), np.asarray(moves), np.asarray(won).reshape(-1) != 0
+    if records < 1 or playouts < 1 or moves.ndim != 2 or len(moves) != records * playouts or len(won) != len(moves) \
+            or recs.shape != (records, L.POS_BYTES):
+        raise ValueError(f"recs must be [{records}, {L.POS_BYTES}], moves [{records} * {playouts}, max_plies] and won "
+                         f"[{records} * {playouts}]")
+    if t.shape != (2, 81) or t.dtype != np.uint8:
+        raise ValueError("a reply table is uint8 [2, 81]")
+    lm0 = L.record_last_move(recs).astype(np.int64)
+    c0 = (L.record_turns(recs) & 1).astype(np.int64)
+    n_set = n_cleared = n_nothing = 0
+    for row in range(len(moves)):
+        r = row // playouts
+        prev, win = int(lm0[r]), bool(won[row])
+        for k, m in enumerate(moves[row].tolist()):
+            if m <= MOVE_NONE:
+                break
+            if 0 <= m <= 80 and 0 <= prev <= 80:
+                c = int(c0[r]) ^ (k & 1)
+                if win == (k % 2 == 0):
+                    t[c, prev] = m
+                    n_set += 1
+                elif t[c, prev] == m:
+                    t[c, prev] = NONE
+                    n_cleared += 1
+                else:
+                    n_nothing += 1
+            prev = m
+    return n_set, n_cleared, n_nothing

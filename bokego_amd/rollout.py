@@ -62,6 +62,14 @@ pattern ratings, or progressive bias, seeding a new node (opt-in, untuned).
 
     python -m bokego_amd.rollout --sgf FILE [--move K] --random --weights [--patterns FILE] [--tactics FILE]   # the ten heaviest points
 
+replies= (a ReplyTable, bokego_amd/replies.py) lets those playouts learn from each other: the last-good-reply policy with
+forgetting.  The table holds, per colour and previous move, the reply that last won a playout; a playout plays
+it where it is playable (bkt_reply_playouts), and after the score one bkt_reply_update stores the winners' replies of the
+batch and takes the losers' out.  playout_value, playout_amaf and random_playouts update the table they are given in place;
+PlayoutEvaluator(replies=True) keeps one across the requests of a search (opt-in, untuned).
+
+    python -m bokego_amd.rollout --sgf FILE [--move K] --random --replies [-n 256] [--chunk 16]   # the share of plies the table decided
+
 rules="host" is one loop (_playout_host) on the host rules with the same draws (lockstep's play_host, features_batch
 and area_score_host, bk_pos_is_legal, bk_pos_possible_eye, lockstep.sample_host in float64): the reference the tests
 compare the device with.  With engine=None it needs no GPU.
@@ -78,6 +86,7 @@ from . import _trainlib as T
 from . import go
 from . import lockstep as L
 from .lockstep import record_turns  # noqa: F401  (public here: see __all__)
+from .replies import ReplyTable, reply_moves, reply_plies_of, reply_update_host
 
 MAX_PLIES = 400            # default cap of finish_games: 2.8x the longest playout measured (142 plies)
 CHECK_EVERY = 16           # plies between two looks at `over`
@@ -85,10 +94,11 @@ MOVE_NONE = -2             # BKT_MOVE_NONE; in the history: the game was over be
 SEKI_THRESHOLD = 0.5       # |mean ownership| of a stone's point below this: the stone is in seki (rollout_score)
 POS_BYTES = L.POS_BYTES
 
-__all__ = ["MAX_PLIES", "MOVE_NONE", "Amaf", "Finished", "Ownership", "PlayoutEvaluator", "RolloutScore", "amaf_counts_host",
+__all__ = ["MAX_PLIES", "MOVE_NONE", "Amaf", "Finished", "Ownership", "PlayoutEvaluator", "ReplyTable", "RolloutScore",
+           "amaf_counts_host", "reply_update_host",
            "amaf_counts_sides_host", "amaf_prior",
            "default_counters", "finish_games", "format_score", "move_weights", "move_weights_host", "owner_board",
-           "ownership_score", "owner_counts_host", "owner_host", "pattern_prior",
+           "ownership_score", "reply_report", "owner_counts_host", "owner_host", "pattern_prior",
            "playable_host", "playout_amaf", "playout_ownership",
            "playout_value", "random_playouts", "record_turns", "rollout_score", "sgf_position"]
 
@@ -105,6 +115,7 @@ class Finished:
     owner       int8 [G,81]     +1 black stone or black-only region, -1 white, 0 neither
     unfinished  int             rows not over at the cap
     min_margin  float64 [G]     rules="host" only: the smallest lockstep.cdf_margin among the game's draws
+    reply_plies int or None     random_playouts(replies=): the plies the reply table decided (rules="host"; None on the device)
     """
 
 
@@ -336,10 +347,13 @@ def select_index(x0, n):
 
 
 
-def _random_host(pos, key, ctr, max_plies, komi, history, table=None, tactics=None):
+def _random_host(pos, key, ctr, max_plies, komi, history, table=None, tactics=None, replies=None):
     """random_playouts on the host: the select_index-th playable point in ascending order, a pass when there is none; with
     a table (a patterns.PatternTable), patterns.select_weighted on the entries of the points' pattern indices; with tactics
-    (a tactics.TacticTable), tactics.select_tactical on those entries (or none) and the entries of the tactical codes."""
+    (a tactics.TacticTable), tactics.select_tactical on those entries (or none) and the entries of the tactical codes.
+    replies (a ReplyTable or uint8 [2,81], read only here): the use rule of replies.py goes first -- where the table's reply
+    to a row's last move is playable it is the move, whatever the draw above says; the Finished then carries reply_plies,
+    the number of plies the table decided."""
     def choose(k, recs, live, ok, x0):
         n = ok.sum(1)
         pick = np.argmax(np.cumsum(ok, 1) > select_index(x0, n).astype(np.int64)[:, None], 1)
@@ -360,7 +374,18 @@ def _random_host(pos, key, ctr, max_plies, komi, history, table=None, tactics=No
         choose = choose_tactical
     elif table is not None:
         choose = choose_weighted
-    return _playout_host(pos, key, ctr, max_plies, komi, choose, "selected", history)
+    if replies is None:
+        return _playout_host(pos, key, ctr, max_plies, komi, choose, "selected", history)
+    decided, draw = [0], choose
+
+    def choose(k, recs, live, ok, x0):                                    # noqa: F811  (the draw, overruled by the table)
+        r = reply_moves(replies, recs[live], ok)
+        decided[0] += int((r >= 0).sum())
+        return np.where(r >= 0, r, draw(k, recs, live, ok, x0))
+
+    fin = _playout_host(pos, key, ctr, max_plies, komi, choose, "selected", history)
+    fin.reply_plies = decided[0]
+    return fin
 
 
 def _table(patterns):
@@ -380,7 +405,7 @@ def _tactics(tactics):
 
 
 def random_playouts(pos, seed, counters=None, max_plies=MAX_PLIES, rules="device", komi=L.KOMI, history=True, device=None,
-                    patterns=None, tactics=None):
+                    patterns=None, tactics=None, replies=None):
     """Play the records pos (uint8 [G,192], numpy or a tensor; not modified) to the end of the game with uniformly random
     eye-safe moves -> Finished, the fields finish_games returns (moves is None with history=False; no min_margin: nothing
     is rounded).  rules="device": one bkt_random_playouts launch per T.MAX_BATCH rows, then bkt_area_score.  rules="host":
@@ -391,9 +416,14 @@ def random_playouts(pos, seed, counters=None, max_plies=MAX_PLIES, rules="device
     patterns: None, or a table of 3x3 pattern weights (patterns.PatternTable, or what patterns.as_table takes): the move is
     then drawn in proportion to the weights of the playable points (bkt_pattern_playouts), on the same words.
     tactics: None, or a table of tactical weights (tactics.TacticTable, or what tactics.as_tactics takes) that multiply the
-    pattern weights, or a constant without patterns (bkt_tactical_playouts)."""
+    pattern weights, or a constant without patterns (bkt_tactical_playouts).
+    replies: None, or a ReplyTable, which every game here reads as it stands (bkt_reply_playouts: where its reply to the
+    last move is playable, that is the move) and which is then updated in place with all G games, rows ascending, each
+    game a record of its own (bkt_reply_update).  The history is written whatever `history` says; black wins a
+    game whose score is > 0.  The games then depend on the table too."""
     L.check_rules(rules)
     table, tactics = _table(patterns), _tactics(tactics)
+    _check_replies(replies)
     max_plies = int(max_plies)
     if not 1 <= max_plies <= 1024:
         raise ValueError("max_plies must be 1..1024 (BKT_MAX_PLAYOUT_PLIES)")
@@ -403,23 +433,43 @@ def random_playouts(pos, seed, counters=None, max_plies=MAX_PLIES, rules="device
         counters = default_counters(G, record_turns(_numpy(pos)))
     key = L.seed_u64(seed)
     if rules == "host":
-        return _random_host(pos, key, L.counters_to_host(counters, G), max_plies, komi, history, table, tactics)
+        fin = _random_host(pos, key, L.counters_to_host(counters, G), max_plies, komi, history or replies is not None, table,
+                           tactics, replies)
+        if replies is not None:
+            start = np.asarray(_numpy(pos))                               # (moves is cut to the longest game: the same fold)
+            reply_update_host(replies, start, fin.moves, (fin.score > 0) == L.black_to_move(start), G, 1)
+            fin.moves = fin.moves if history else None
+        return fin
     dev = _device(device, None, pos)
-    pos = L.records_to_device(pos, dev)
+    start = L.records_to_device(pos, dev, clone=False)
+    pos = start.clone()
     ctr = L.counters_to_device(counters, G, dev, clone=False)
-    over, plies, moves, status = _play_random_device(pos, key, ctr, max_plies, history, table, tactics)
+    over, plies, moves, status = _play_random_device(pos, key, ctr, max_plies, history or replies is not None, table, tactics,
+                                                     replies)
     score, owner = _area_score_device(pos, komi, True)
+    if replies is not None:
+        T.reply_update(start, moves, ((score > 0) == L.black_to_move(start)).to(torch.uint8), G, 1, replies.device(dev))
     _check_status(status, "selected")
-    return _finished(pos, moves, plies.cpu().numpy().astype(np.int64), over.cpu().numpy() != 0, score.cpu().numpy(),
-                     owner.cpu().numpy())
+    fin = _finished(pos, moves if history else None, plies.cpu().numpy().astype(np.int64), over.cpu().numpy() != 0,
+                    score.cpu().numpy(), owner.cpu().numpy())
+    fin.reply_plies = None
+    return fin
 
 
-def _play_random_device(pos, key, ctr, max_plies, history, table=None, tactics=None):
+def _check_replies(replies):
+    if replies is not None and not isinstance(replies, ReplyTable):
+        raise TypeError("replies must be a ReplyTable (it is updated in place) or None")
+
+
+def _play_random_device(pos, key, ctr, max_plies, history, table=None, tactics=None, replies=None):
     """pos uint8 [G,192] and ctr int32 [G,4] on the device; pos is played on in place; table: None or a PatternTable;
-    tactics: None or a TacticTable.
+    tactics: None or a TacticTable; replies: None or a ReplyTable, which every launch reads as it stands.
     -> (over uint8 [G], plies int32 [G], moves int16 [G,max_plies] or None, status int32 [G]), T.MAX_BATCH rows per launch."""
     w = None if table is None else table.device(pos.device)
-    if tactics is not None:
+    if replies is not None:
+        play = T.reply_playouts
+        tables = (w, None if tactics is None else tactics.device(pos.device), replies.device(pos.device))
+    elif tactics is not None:
         play, tables = T.tactical_playouts, (w, tactics.device(pos.device))
     elif table is None:
         play, tables = T.random_playouts, ()
@@ -461,7 +511,7 @@ def _value_of_wins(w, n):
 
 
 def _playouts(recs, n, key, rules, komi=L.KOMI, table=None, tactics=None, max_plies=MAX_PLIES, score=True, history=False,
-              final=False, counted=0, sides=1, owned=0):
+              final=False, counted=0, sides=1, owned=0, replies=None):
     """The one playout run: n playouts of each record of recs -- a uint8 [R,192] tensor on the device with
     rules="device", where nothing here waits for it; an array with "host", the mirror -- and what is asked of them, as a
     namespace whose fields are None when they were not asked for:
@@ -472,24 +522,37 @@ def _playouts(recs, n, key, rules, komi=L.KOMI, table=None, tactics=None, max_pl
     final   uint8 [R * n, 192]      final=True: the final records
     played, won_at                  counted=c (True: all): the AMAF counts of the first c records, int32 [c,81] from one
                                     bkt_amaf_counts, or with sides=2 [c,2,81] from one bkt_amaf_counts_sides
-    owner                           owned=o (True: all): the five owner counts of the first o records, one bkt_owner_counts"""
+    owner                           owned=o (True: all): the five owner counts of the first o records, one bkt_owner_counts
+    reply_plies                     replies= (a ReplyTable): every playout reads the table as it stands
+                                    (bkt_reply_playouts, with history), and after the score one bkt_reply_update folds all
+                                    R * n of them into it, in place and on the same stream; the plies the table decided on
+                                    the host, None on the device, where nothing counts them.  It needs score=True: the
+                                    update reads `won`."""
     R, host = len(recs), rules == "host"
     counted, owned = (R if x is True else int(x) for x in (counted, owned))
+    _check_replies(replies)
+    if replies is not None and not score:
+        raise ValueError("a reply table learns from who won each playout: it needs the scored run (not playout_ownership's)")
+    history = history or counted > 0 or replies is not None
     if host:
         recs = np.array(_numpy(recs), np.uint8, order="C")
-        fin = _random_host(np.repeat(recs, n, 0), key, value_counters(recs, n), max_plies, komi, history or counted > 0, table,
-                           tactics)
+        fin = _random_host(np.repeat(recs, n, 0), key, value_counters(recs, n), max_plies, komi, history, table, tactics, replies)
         pos, moves, black_wins = fin.records, fin.moves, fin.score.reshape(R, n) > 0
     else:
         pos = recs.repeat_interleave(n, 0)                                 # a copy: the caller's records stay
-        moves = _play_random_device(pos, key, L.value_counters_device(recs, n), max_plies, history or counted > 0, table,
-                                    tactics)[2]
+        moves = _play_random_device(pos, key, L.value_counters_device(recs, n), max_plies, history, table, tactics, replies)[2]
         black_wins = _area_score_device(pos, komi, False).view(R, n) > 0 if score else None
     run = SimpleNamespace(value=None, wins=None, won=None, moves=moves, final=pos if final else None, played=None, won_at=None,
-                          owner=None)
+                          owner=None, reply_plies=None)
     if score:
         run.won = black_wins == L.black_to_move(recs)[:, None]
         run.wins = run.won.sum(1)
+    if replies is not None:                                                # playouts, then score, then update: submit order
+        if host:
+            run.reply_plies = fin.reply_plies
+            reply_update_host(replies, recs, moves, run.won.reshape(-1), R, n)
+        else:
+            T.reply_update(recs, moves, run.won.reshape(-1).to(torch.uint8), R, n, replies.device(recs.device))
     if counted:
         reduce = ((T.amaf_counts, T.amaf_counts_sides), (amaf_counts_host, amaf_counts_sides_host))[host][sides - 1]
         won = run.won[:counted].reshape(-1)
@@ -503,7 +566,7 @@ def _playouts(recs, n, key, rules, komi=L.KOMI, table=None, tactics=None, max_pl
     return run
 
 
-def _run(recs, n, seed, rules, komi, device, patterns, tactics, **ask):
+def _run(recs, n, seed, rules, komi, device, patterns, tactics, replies=None, **ask):
     """What playout_value, playout_amaf and playout_ownership share: the checks, the upload and _playouts(**ask)."""
     L.check_rules(rules)
     table, tactics = _table(patterns), _tactics(tactics)
@@ -511,15 +574,17 @@ def _run(recs, n, seed, rules, komi, device, patterns, tactics, **ask):
     _check_records(recs)
     if rules == "device":
         recs = L.records_to_device(recs, _device(device, None, recs), clone=False)
-    return _playouts(recs, n, L.seed_u64(seed), rules, komi, table, tactics, **ask)
+    return _playouts(recs, n, L.seed_u64(seed), rules, komi, table, tactics, replies=replies, **ask)
 
 
-def playout_value(recs, n, seed, rules="device", komi=L.KOMI, device=None, patterns=None, tactics=None):
+def playout_value(recs, n, seed, rules="device", komi=L.KOMI, device=None, patterns=None, tactics=None, replies=None):
     """The Monte-Carlo value of each record, float32 [R] (numpy): (2 w - n) / n, w = the number of n uniformly random
     eye-safe playouts (random_playouts, capped at MAX_PLIES and then scored as they stand) that the side to move wins --
     black wins iff the area score is > 0.  A pure function of the record, `seed` and `n` (value_counters): the row index
-    and the rest of the batch do not enter.  recs: uint8 [R,192], numpy or a tensor.  patterns, tactics: as random_playouts."""
-    return _numpy(_run(recs, n, seed, rules, komi, device, patterns, tactics).value)
+    and the rest of the batch do not enter.  recs: uint8 [R,192], numpy or a tensor.  patterns, tactics: as random_playouts.
+    replies: None, or a ReplyTable the playouts read and this call then updates in place with all R * n of them:
+    the value is then a function of the table as well."""
+    return _numpy(_run(recs, n, seed, rules, komi, device, patterns, tactics, replies).value)
 
 
 class Amaf:
@@ -579,16 +644,16 @@ def amaf_counts_sides_host(moves, won, records, playouts):
     return played, won_at
 
 
-def playout_amaf(recs, n, seed, rules="device", komi=L.KOMI, device=None, patterns=None, tactics=None, sides=1):
+def playout_amaf(recs, n, seed, rules="device", komi=L.KOMI, device=None, patterns=None, tactics=None, sides=1, replies=None):
     """playout_value's n playouts of each record with what else they tell -> Amaf: the value (the history does not enter a
     game: the same bits), the wins, and the all-moves-as-first counts of every point (amaf_counts_host has the definition).
     rules="device": the playout launches with their history, `won` built in torch, one bkt_amaf_counts; rules="host": the
     mirror end to end, the same integers.  recs, patterns, tactics: as playout_value.
     sides=2: the counts of both sides, [R,2,81] (one bkt_amaf_counts_sides; amaf_counts_sides_host); value and wins are the
-    same either way."""
+    same either way.  replies: as playout_value."""
     if sides not in (1, 2):
         raise ValueError("sides must be 1 or 2")
-    run = _run(recs, n, seed, rules, komi, device, patterns, tactics, counted=True, sides=sides)
+    run = _run(recs, n, seed, rules, komi, device, patterns, tactics, replies, counted=True, sides=sides)
     return Amaf(_numpy(run.value), _numpy(run.wins).astype(np.int32), _numpy(run.played), _numpy(run.won_at), n)
 
 
@@ -656,12 +721,13 @@ def owner_counts_host(final_recs, records, playouts, komi=L.KOMI):
     return black, white, agree, hist, bw.reshape(records, playouts).sum(1).astype(np.int32)
 
 
-def playout_ownership(recs, n, seed, rules="device", komi=L.KOMI, device=None, patterns=None, tactics=None):
+def playout_ownership(recs, n, seed, rules="device", komi=L.KOMI, device=None, patterns=None, tactics=None, replies=None):
     """playout_value's n playouts of each record -- the same counters, draws and cap -- with what their final boards tell
     -> Ownership: the value (the same bits), the wins, and the ownership, agreement and margin counts of every record
     (owner_counts_host has the definition).  rules="device": the playout launch without history and one bkt_owner_counts;
-    rules="host": the mirror end to end, the same integers.  recs, patterns, tactics: as playout_value."""
-    run = _run(recs, n, seed, rules, komi, device, patterns, tactics, score=False, owned=True)
+    rules="host": the mirror end to end, the same integers.  recs, patterns, tactics: as playout_value.
+    replies must be None: this run launches no score, and a reply table learns from who won (ValueError)."""
+    run = _run(recs, n, seed, rules, komi, device, patterns, tactics, replies, score=False, owned=True)
     return Ownership(_numpy(run.value), _numpy(run.wins).astype(np.int32), *(_numpy(c) for c in run.owner), n)
 
 
@@ -817,14 +883,22 @@ class PlayoutEvaluator:
     (untuned).  The tables of that term are prior_patterns and prior_tactics, which default to the playouts' own
     patterns and tactics -- so uniform playouts can run under a pattern prior; with no table at all every weight would be
     equal: ValueError.  Values and records are what they are without it.
+    replies=True (default False: exactly the above, the same launches): the evaluator owns one ReplyTable, created empty,
+    `.replies`, which reset_replies() clears.  The playouts of every request read it (bkt_reply_playouts: the last good reply
+    to the move before, where it is playable, instead of the draw) and are folded into it after their score (one
+    bkt_reply_update), all on one stream: playouts, then score, then update, so two requests in flight see the table in
+    submit order.  Values, priors, RAVE records and criticality are computed as before from that run.  With replies=True a
+    value is no longer a function of (record, seed, N) alone: it is a function of those and the requests submitted before
+    it.  A given tree search is still deterministic per seed, and device rules and host rules give the same bits.
     The engine is kept as `policy_engine`, not `engine`: selfplay.run_pools_native hands an evaluator's `engine` to the C
     step loop as its own bk_evaluator, which would compute no playouts -- this class goes through callback_evaluator."""
     wants_positions = True
 
     def __init__(self, engine, playouts=64, seed=0, rules="device", komi=L.KOMI, patterns=None, tactics=None, prior=0.0,
                  prior_k=PRIOR_K, prior_temperature=PRIOR_TEMPERATURE, rave=False, criticality=0.0, pattern_prior=0.0,
-                 prior_patterns=None, prior_tactics=None):
+                 prior_patterns=None, prior_tactics=None, replies=False):
         L.check_rules(rules)
+        self.replies = ReplyTable.empty() if replies else None
         self.rave = bool(rave)
         self.criticality = _not_negative(criticality, "criticality")
         if self.criticality > 0.0 and not float(prior) > 0.0:
@@ -868,10 +942,16 @@ class PlayoutEvaluator:
         # rave: every row with its history, both sides counted, and the prior reads side 0 of the first rows of those counts
         run = _playouts(t, self.playouts, self.seed, self.rules, self.komi, self.patterns, self.tactics,
                         counted=len(recs) if self.rave else counted, sides=2 if self.rave else 1,
-                        owned=counted if self.criticality > 0.0 else 0)
+                        owned=counted if self.criticality > 0.0 else 0, replies=self.replies)
         if counted and self.pattern_prior > 0.0:                          # (the device's launch: nothing waits for it)
             weights = (move_weights_host if host else _move_weights_device)(t[:counted], self.prior_patterns, self.prior_tactics)
         return SimpleNamespace(ticket=ticket, run=run, n_policy=counted, weights=weights, recs=recs[:counted])
+
+    def reset_replies(self):
+        """An empty reply table again (replies=True): what a new game starts with."""
+        if self.replies is None:
+            raise TypeError("this evaluator keeps no reply table: replies=True")
+        self.replies.clear()
 
     def finish(self, handle, normalise=None):
         run, n = handle.run, handle.n_policy
@@ -1022,6 +1102,10 @@ def _parse(argv):
     ap.add_argument("--weights", action="store_true",
                     help="with --random: print the ten heaviest points of the position by the playouts' move weights "
                          "(--patterns, --tactics) instead of the score; no playout runs")
+    ap.add_argument("--replies", action="store_true",
+                    help="with --random: play the playouts in chunks that learn a last-good-reply table from each other, and "
+                         "print the share of plies the table decided and its occupancy instead of the score")
+    ap.add_argument("--chunk", type=int, default=16, metavar="C", help="with --replies: playouts per chunk")
     ap.add_argument("--sides", type=int, default=1, choices=(1, 2),
                     help="with --amaf: 2 also prints the opponent's heaviest points (the two-sided counts RAVE is fed with)")
     ap.add_argument("-n", dest="n", type=int, default=256, help="playouts")
@@ -1035,6 +1119,10 @@ def _parse(argv):
         ap.error("--ownership reads the one-launch playouts: it needs --random, and not --amaf")
     if args.weights and (not args.random or args.amaf or args.ownership):
         ap.error("--weights reads the one-launch playouts' draw: it needs --random, and not --amaf or --ownership")
+    if args.replies and (not args.random or args.amaf or args.ownership or args.weights):
+        ap.error("--replies reads the one-launch playouts: it needs --random, and not --amaf, --ownership or --weights")
+    if args.chunk < 1:
+        ap.error("--chunk must be at least 1")
     if args.sides != 1 and not args.amaf:
         ap.error("--sides goes with --amaf")
     if args.n < 1:
@@ -1064,6 +1152,24 @@ def sgf_position(path, move=None):
     return g
 
 
+def reply_report(recs, n, seed, chunk, rules="device", komi=L.KOMI, **kw):
+    """n playouts of the one record recs [1,192] in chunks of `chunk`, each chunk reading the reply table the chunks before
+    it left (random_playouts(replies=); game g of the n keeps default_counters' words, so the chunking changes the table a
+    game sees and nothing else) -> a dict: the plies played, those the table decided, their share, the table's occupancy
+    at the end and black's share of the wins.  kw: random_playouts' patterns, tactics and device."""
+    table, plies, decided, black = ReplyTable.empty(), 0, 0, 0
+    ctr = default_counters(n, np.repeat(record_turns(recs), n))
+    for s in range(0, n, chunk):
+        c = min(chunk, n - s)
+        before = table.copy()
+        fin = random_playouts(np.repeat(recs, c, 0), seed, counters=ctr[s:s + c], rules=rules, komi=komi, replies=table, **kw)
+        plies += int(fin.plies.sum())
+        decided += reply_plies_of(before, np.repeat(recs, c, 0), fin.moves, 1)
+        black += int((fin.score > 0).sum())
+    return {"playouts": n, "chunk": chunk, "plies": plies, "reply_plies": decided, "share": decided / max(plies, 1),
+            "occupancy": table.occupancy(), "black_win": black / n}
+
+
 def main(argv=None):
     args = _parse(argv)
     game = sgf_position(args.sgf, args.move)
@@ -1089,6 +1195,10 @@ def main(argv=None):
         print(json.dumps({"playable": int((w > 0).sum()),
                           "weights": [{"move": go.unsquash(s), "weight": int(w[s]), "share": float(p[s])}
                                       for s in np.argsort(-w, kind="stable")[:10].tolist() if w[s] > 0]}))
+        return
+    if args.replies:
+        print(json.dumps(reply_report(_as_records(game), args.n, args.seed, args.chunk, komi=args.komi, patterns=args.patterns,
+                                      tactics=args.tactics, device=torch.device("cuda", args.device))))
         return
     if args.ownership:
         o = playout_ownership(_as_records(game), args.n, args.seed, komi=args.komi, device=torch.device("cuda", args.device),

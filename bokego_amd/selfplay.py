@@ -858,7 +858,7 @@ def parse_args(argv=None):
     ap.add_argument("--task-cap", type=int, default=None, help="soft limit of a batch in network tasks (default: whole rounds of workgroups for fp32, none for f16x2; 0: none)")
     ap.add_argument("--replay-shard", metavar="RANK/WORLD", default=None,
                     help="re-play the games a failed rank owned (e.g. 3/8: the gids with gid %% 8 == 3) in this process")
-    PlayoutOptions.add_arguments(ap, rave=False)                      # --playout-value N: not with --value or --host-encode
+    PlayoutOptions.add_arguments(ap, rave=False, replies=False)       # --playout-value N: not with --value or --host-encode
     args = ap.parse_args(argv)
     args.playout = PlayoutOptions.from_args(ap, args)
     if args.playout_value:

@@ -328,6 +328,48 @@ int bkt_owner_counts(const void *pos, int records, int playouts, float komi, int
 int bkt_move_weights(const void *pos, int batch, const uint16_t *table, const uint16_t *tactics, uint32_t *weights,
                      void *stream);
 
+/* Last-good-reply playouts with forgetting (LGRF-1; bokego_amd/rollout.py ReplyTable): a reply table the
+ * playouts of a search learn.  replies is uint8 [2][81], 162 bytes: replies[c][prev] is the reply of colour c (0 black,
+ * 1 white) to the opponent's move on board point prev.  A value 0..80 is a point; BKT_REPLY_NONE = 255 means none; a value
+ * above 80 other than 255 is treated as none.  A previous move that is a pass or "no move" has no entry.  Entries are
+ * compared or bounds-checked before they index anything.
+ *
+ * Use (in a playout).  At a ply, take the side to move c, the last move lm and the playable set P that the ply body left
+ * behind (legal, not an own one-point eye).  If lm is a board point, r = replies[c][lm] is a point and r is in P, the move
+ * is r.  Otherwise the move is whatever the underlying draw picks: tactical, pattern, or uniform when both tables are NULL.
+ * The Philox word of a ply is indexed by the ply, so skipping the draw shifts nothing.
+ *
+ * bkt_reply_playouts is bkt_tactical_playouts' contract with `replies` put in, read only, on the device.  table and tactics
+ * may each be NULL, and both may be NULL; replies == NULL returns BKT_ERR_ARG and nothing is launched.  With every entry
+ * 255 the records, histories, plies, over and status are byte for byte those of bkt_tactical_playouts (both tables, or
+ * tactics alone), bkt_pattern_playouts (table alone) or bkt_random_playouts (neither). */
+#define BKT_REPLY_NONE 255
+int bkt_reply_playouts(void *pos, int batch, uint64_t seed, const uint32_t *counters, const uint16_t *table,
+                       const uint16_t *tactics, const uint8_t *replies, int max_plies, uint8_t *over, int32_t *plies,
+                       int16_t *moves, int32_t *status, void *stream);
+
+/* Update (after a batch of playouts).  pos [records, 192]: the starting records, read only; the side to move and the last
+ * move of ply 0 come from them.  moves [records * playouts, max_plies] and won[row], exactly as bkt_amaf_counts_sides takes
+ * them.  The result is defined as a sequential fold: rows ascending, plies ascending within a row, up to the first entry
+ * <= BKT_MOVE_NONE or max_plies.  For ply t of a row:
+ *   the mover's colour is c = (colour to move at the record) xor (t & 1);
+ *   prev is the record's last move for t = 0, else moves[row, t - 1];   m = moves[row, t];
+ *   if m or prev is not a board point, nothing happens;
+ *   if the mover won the row, (won[row] != 0) == (t even), then replies[c][prev] = m;
+ *   otherwise, if replies[c][prev] == m, then replies[c][prev] = 255.
+ * The table is updated in place.  Entries with no event keep their value, whatever it is.
+ * Two launches on `stream`, nothing waits on the host: the first, one workgroup per record, writes for every table entry a
+ * summary of what the record's rows do to it (the points forgotten before the first store, and the value after the last
+ * one) to scratch; the second composes the records' summaries in order and applies them to replies.  Integers only, no
+ * atomics, no workgroup waits on another: the result is the fold's for every input, whatever the scheduling.
+ * scratch: bkt_reply_scratch_bytes(records) = records * 2592 bytes on the device, 4-byte aligned; its contents on entry do
+ * not matter, and all of it is written.
+ * No pointer but stream may be NULL; records >= 1, playouts >= 1, records * playouts <= BKT_MAX_SAMPLE_ROWS,
+ * 1 <= max_plies <= BKT_MAX_PLAYOUT_PLIES; else BKT_ERR_ARG, nothing is launched and nothing written. */
+size_t bkt_reply_scratch_bytes(int records);
+int bkt_reply_update(const void *pos, const int16_t *moves, int max_plies, const uint8_t *won, int records, int playouts,
+                     uint8_t *replies, void *scratch, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
