@@ -56,6 +56,8 @@ SYMBOLS = {
     "bkt_reply_playouts": (_I, [_P, _I, _U64, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P]),
     "bkt_reply_scratch_bytes": (_Z, [_I]),
     "bkt_reply_update": (_I, [_P, _P, _I, _P, _I, _I, _P, _P, _P]),
+    "bkt_reply_playouts_tables": (_I, [_P, _I, _U64, _P, _P, _P, _P, _I, _P, _I, _P, _P, _P, _P, _P]),
+    "bkt_reply_update_tables": (_I, [_P, _P, _I, _P, _I, _I, _P, _I, _P, _P, _P]),
 }
 MAX_BATCH = 65536          # BKT_MAX_BATCH
 PRECISIONS = ("fp32", "bf16")
@@ -552,4 +554,51 @@ def reply_update(pos, moves, won, records, playouts, replies, scratch=None):
                                    _dev(won, "won", (records * playouts,), torch.uint8), records, playouts,
                                    _dev(replies, "replies", (2, 81), torch.uint8), _dev(scratch, "scratch", dtype=torch.uint8),
                                    _stream(moves)), "bkt_reply_update")
+    return replies
+
+
+def _reply_tables(replies, slots, n, dev, what):
+    """The checks reply_playouts_tables and reply_update_tables share -> (tables, replies pointer, slots pointer)."""
+    if not isinstance(replies, torch.Tensor) or replies.device != dev or replies.dim() != 3:
+        raise ValueError(f"replies must be uint8 [tables, 2, 81] on the device of {what}")
+    tables = int(replies.shape[0])
+    if not 1 <= tables <= MAX_BATCH:
+        raise ValueError(f"the number of reply tables must be 1..{MAX_BATCH}, got {tables}")
+    if not isinstance(slots, torch.Tensor) or slots.device != dev:
+        raise ValueError(f"slots must be int32 [{n}] on the device of {what}")
+    return tables, _dev(replies, "replies", (tables, 2, 81), torch.uint8), _dev(slots, "slots", (n,), torch.int32)
+
+
+def reply_playouts_tables(pos, seed, counters, table, tactics, replies, slots, max_plies, over=None, history=True):
+    """reply_playouts over many tables in one launch (bkt_reply_playouts_tables): replies uint8 [tables,2,81] and slots int32
+    [B] on the device of pos, both read only; row i asks table slots[i], and a slot outside 0..tables-1 plays as an empty
+    table."""
+    for t in (table, tactics):
+        if t is not None and (not isinstance(t, torch.Tensor) or t.device != pos.device):
+            raise ValueError("the pattern table and the tactics table must be on the device of pos")
+    tables, r, sl = _reply_tables(replies, slots, _pos_batch(pos), pos.device, "pos")
+    return _playouts("bkt_reply_playouts_tables", pos, seed, counters,
+                     (None if table is None else _dev(table, "table", (PATTERN_ENTRIES,), torch.int16),
+                      None if tactics is None else _dev(tactics, "tactics", (TACTIC_ENTRIES,), torch.int16), r, tables, sl),
+                     max_plies, over, history)
+
+
+def reply_update_tables(pos, moves, won, records, playouts, replies, slots, scratch=None):
+    """reply_update over many tables (bkt_reply_update_tables): replies uint8 [tables,2,81], updated in place; slots int32
+    [records], the table of every record -- table t is folded with the records whose slot is t, in ascending order; a slot
+    outside 0..tables-1 updates nothing.  scratch as reply_update.  Two launches on the current stream; nothing waits.
+    -> replies."""
+    records, playouts, max_plies = _amaf_args(moves, won, records, playouts)
+    if not isinstance(pos, torch.Tensor) or tuple(pos.shape) != (records, POS_BYTES) or pos.device != moves.device:
+        raise ValueError(f"pos must be [{records}, {POS_BYTES}] on the device of moves")
+    tables, r, sl = _reply_tables(replies, slots, records, moves.device, "moves")
+    need = load().bkt_reply_scratch_bytes(records)
+    if scratch is None:
+        scratch = torch.empty((need,), dtype=torch.uint8, device=moves.device)
+    elif not isinstance(scratch, torch.Tensor) or scratch.device != moves.device or scratch.dim() != 1 or scratch.numel() < need:
+        raise ValueError(f"scratch must be uint8 [>= {need}] on the device of moves")
+    _check(load().bkt_reply_update_tables(_dev(pos, "pos", dtype=torch.uint8), _dev(moves, "moves", dtype=torch.int16), max_plies,
+                                          _dev(won, "won", (records * playouts,), torch.uint8), records, playouts, r, tables, sl,
+                                          _dev(scratch, "scratch", dtype=torch.uint8), _stream(moves)),
+           "bkt_reply_update_tables")
     return replies

@@ -1629,6 +1629,24 @@ void bk_pool_deliver_rave(bk_pool* p, const float* probs, const float* values, i
     deliver_impl(p, probs, values, rr);
 }
 
+// The game behind every row of the batch now out (between a collect and its deliver; either collect flavour): the layout
+// of collect_impl read back.  Not for a batch laid out by collect_dedup, where a row may belong to several games.
+int bk_pool_batch_games(const bk_pool* p, int32_t* games, int cap) {
+    if (!p || !games || p->active.empty() || p->mapped) return -1;
+    int npol = 0, nval = 0;
+    for (int g : p->active) {
+        npol += (int)p->games[g].req_policy.size();
+        nval += (int)p->games[g].req_value.size();
+    }
+    if (npol + nval > cap) return -1;
+    for (size_t a = 0; a < p->active.size(); ++a) {
+        const Game& gm = p->games[p->active[a]];
+        for (size_t i = 0; i < gm.req_policy.size(); ++i) games[p->pol_off[a] + (int)i] = p->active[a];
+        for (size_t i = 0; i < gm.req_value.size(); ++i) games[npol + p->val_off[a] + (int)i] = p->active[a];
+    }
+    return npol + nval;
+}
+
 int bk_pool_set_rave(bk_pool* p, double equiv) {
     if (!p || !(equiv >= 0.0) || !std::isfinite(equiv)) return -1;
     for (const auto& g : p->games)                                   // RAVE lives in the fast branch of backprop() only

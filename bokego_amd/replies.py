@@ -10,6 +10,10 @@ two rules in numpy.  include/bokego_train.h has the definition the kernels, this
 
 rollout.py's playouts take a ReplyTable as replies= and update it in place; with rules="device" the live copy is a tensor
 on the device (bkt_reply_playouts reads it, bkt_reply_update writes it) and `.array` downloads it when asked.
+
+ReplyTables(count) is `count` such tables in one array, a table per game of a self-play batch: the playouts and
+the update then take `slots`, the table of every row (of every record): the single-table rules applied, per slot, to that
+slot's rows in order.  A slot outside 0..count-1 plays as an empty table and updates nothing.
 """
 import numpy as np
 
@@ -18,7 +22,7 @@ from . import lockstep as L
 NONE = 255                 # BKT_REPLY_NONE
 MOVE_NONE = -2             # BKT_MOVE_NONE
 
-__all__ = ["NONE", "ReplyTable", "reply_moves", "reply_update_host"]
+__all__ = ["NONE", "ReplyTable", "ReplyTables", "reply_moves", "reply_update_host"]
 
 
 class ReplyTable:
@@ -81,18 +85,77 @@ class ReplyTable:
         self.__init__(state["array"])
 
 
+class ReplyTables(ReplyTable):
+    """uint8 [count,2,81]: `count` reply tables, table i for the rows whose slot is i.  `.array`, device(dev), clear() and
+    the caching contract are ReplyTable's; occupancy() is per table, and table(i) a ReplyTable copy of table i."""
+
+    def __init__(self, count, array=None):
+        count = int(count)
+        if not 1 <= count <= 65536:
+            raise ValueError("the number of reply tables must be 1..65536 (BKT_MAX_BATCH)")
+        array = np.full((count, 2, 81), NONE, np.uint8) if array is None else np.asarray(array)
+        if array.shape != (count, 2, 81) or array.dtype != np.uint8:
+            raise ValueError(f"{count} reply tables are uint8 [{count}, 2, 81], got {array.dtype} {array.shape}")
+        self.count = count
+        self._array = np.array(array, np.uint8, order="C")
+        self._device = {}
+        self._live = None
+
+    @classmethod
+    def empty(cls, count=1):
+        return cls(count)
+
+    def copy(self):
+        return ReplyTables(self.count, self.array)
+
+    def occupancy(self):
+        """int64 [count]: the number of entries of each table that hold a point."""
+        return (self.array <= 80).sum((1, 2)).astype(np.int64)
+
+    def table(self, i):
+        return ReplyTable(self.array[int(i)])
+
+    def __getstate__(self):
+        return {"count": self.count, "array": self.array.copy()}
+
+    def __setstate__(self, state):
+        self.__init__(state["count"], state["array"])
+
+
 def _host_array(table):
     return table.array if isinstance(table, ReplyTable) else np.asarray(table)
 
 
-def reply_moves(table, recs, playable):
+def _slots_of(t, slots, n, what):
+    """slots for n rows (records) of tables t [count,2,81] -> int64 [n]; None with a single table [2,81]."""
+    if t.ndim == 2:
+        if slots is not None:
+            raise TypeError("slots name one of many tables: a single reply table takes none")
+        return None
+    if slots is None:
+        raise TypeError(f"reply tables need slots: the table of every {what}")
+    slots = np.asarray(slots)
+    if slots.shape != (n,) or slots.dtype.kind not in "iu":
+        raise ValueError(f"slots must be an int array of one entry per {what}, [{n}]")
+    return slots.astype(np.int64)
+
+
+def reply_moves(table, recs, playable, slots=None):
     """The use rule for rows: recs uint8 [R,192], playable bool [R,81] -> int64 [R]: the reply the table makes the side to
     move play, or -1 where it decides nothing (the last move is no board point, the entry is no point, or the point is
-    not playable).  An entry is compared before it indexes."""
+    not playable).  An entry is compared before it indexes.  With tables [count,2,81], slots [R] names each row's table;
+    a slot outside 0..count-1 is compared before it indexes, and such a row has no reply."""
     t = _host_array(table)
     lm = L.record_last_move(recs).astype(np.int64)
     c = (L.record_turns(recs) & 1).astype(np.int64)
     on_board = (lm >= 0) & (lm <= 80)
+    slots = _slots_of(t, slots, len(recs), "row")
+    if slots is not None:
+        on_board = on_board & (slots >= 0) & (slots < len(t))
+        t = t[np.where(on_board, slots, 0)]                           # [R,2,81]: each row's table
+        r = np.where(on_board, t[np.arange(len(recs)), c, np.where(on_board, lm, 0)], NONE).astype(np.int64)
+        ok = (r <= 80) & np.asarray(playable)[np.arange(len(recs)), np.minimum(r, 80)]
+        return np.where(ok, r, -1)
     r = np.where(on_board, t[c, np.where(on_board, lm, 0)], NONE).astype(np.int64)
     ok = (r <= 80) & np.asarray(playable)[np.arange(len(recs)), np.minimum(r, 80)]
     return np.where(ok, r, -1)
@@ -113,28 +176,36 @@ def reply_plies_of(table, recs, moves, playouts):
     return int((ok & (t[c, np.clip(prev, 0, 80)] == moves)).sum())
 
 
-def reply_update_host(table, recs, moves, won, records, playouts):
+def reply_update_host(table, recs, moves, won, records, playouts, slots=None):
     """bkt_reply_update on the host, the sequential fold itself: table a ReplyTable (or a uint8 [2,81] array), updated in
     place; recs uint8 [records,192], the starting records; moves int16 [records * playouts, max_plies] and won
     [records * playouts] as amaf_counts_sides_host takes them.  Rows ascending, plies ascending up to the first entry
     <= MOVE_NONE: with c the mover's colour ((turn of the record + t) & 1), prev the record's last move at t = 0 and
     moves[row, t - 1] after it, m = moves[row, t] -- when both are board points, a mover who won the row stores
     table[c, prev] = m, and one who lost clears the entry if it holds m.
+    With tables [count,2,81] (a ReplyTables), slots [records] names each record's table: table i is folded with the records
+    whose slot is i, in ascending order; a record whose slot is outside 0..count-1 updates nothing (and counts no event).
     -> (set, cleared, nothing): the events that stored, that cleared, and that did neither."""
-    t = _host_array(table)
+    tables = _host_array(table)
     records, playouts = int(records), int(playouts)
     recs, moves, won = np.asarray(recs), np.asarray(moves), np.asarray(won).reshape(-1) != 0
     if records < 1 or playouts < 1 or moves.ndim != 2 or len(moves) != records * playouts or len(won) != len(moves) \
             or recs.shape != (records, L.POS_BYTES):
         raise ValueError(f"recs must be [{records}, {L.POS_BYTES}], moves [{records} * {playouts}, max_plies] and won "
                          f"[{records} * {playouts}]")
-    if t.shape != (2, 81) or t.dtype != np.uint8:
-        raise ValueError("a reply table is uint8 [2, 81]")
+    if tables.shape[-2:] != (2, 81) or tables.ndim not in (2, 3) or tables.dtype != np.uint8:
+        raise ValueError("a reply table is uint8 [2, 81], reply tables uint8 [count, 2, 81]")
+    slots = _slots_of(tables, slots, records, "record")
+    t = tables
     lm0 = L.record_last_move(recs).astype(np.int64)
     c0 = (L.record_turns(recs) & 1).astype(np.int64)
     n_set = n_cleared = n_nothing = 0
     for row in range(len(moves)):
         r = row // playouts
+        if slots is not None:
+            if not 0 <= slots[r] < len(tables):
+                continue
+            t = tables[slots[r]]
         prev, win = int(lm0[r]), bool(won[row])
         for k, m in enumerate(moves[row].tolist()):
             if m <= MOVE_NONE:

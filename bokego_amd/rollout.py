@@ -86,7 +86,7 @@ from . import _trainlib as T
 from . import go
 from . import lockstep as L
 from .lockstep import record_turns  # noqa: F401  (public here: see __all__)
-from .replies import ReplyTable, reply_moves, reply_plies_of, reply_update_host
+from .replies import ReplyTable, ReplyTables, reply_moves, reply_plies_of, reply_update_host
 
 MAX_PLIES = 400            # default cap of finish_games: 2.8x the longest playout measured (142 plies)
 CHECK_EVERY = 16           # plies between two looks at `over`
@@ -94,7 +94,7 @@ MOVE_NONE = -2             # BKT_MOVE_NONE; in the history: the game was over be
 SEKI_THRESHOLD = 0.5       # |mean ownership| of a stone's point below this: the stone is in seki (rollout_score)
 POS_BYTES = L.POS_BYTES
 
-__all__ = ["MAX_PLIES", "MOVE_NONE", "Amaf", "Finished", "Ownership", "PlayoutEvaluator", "ReplyTable", "RolloutScore",
+__all__ = ["MAX_PLIES", "MOVE_NONE", "Amaf", "Finished", "Ownership", "PlayoutEvaluator", "ReplyTable", "ReplyTables", "RolloutScore",
            "amaf_counts_host", "reply_update_host",
            "amaf_counts_sides_host", "amaf_prior",
            "default_counters", "finish_games", "format_score", "move_weights", "move_weights_host", "owner_board",
@@ -347,13 +347,13 @@ def select_index(x0, n):
 
 
 
-def _random_host(pos, key, ctr, max_plies, komi, history, table=None, tactics=None, replies=None):
+def _random_host(pos, key, ctr, max_plies, komi, history, table=None, tactics=None, replies=None, slots=None):
     """random_playouts on the host: the select_index-th playable point in ascending order, a pass when there is none; with
     a table (a patterns.PatternTable), patterns.select_weighted on the entries of the points' pattern indices; with tactics
     (a tactics.TacticTable), tactics.select_tactical on those entries (or none) and the entries of the tactical codes.
     replies (a ReplyTable or uint8 [2,81], read only here): the use rule of replies.py goes first -- where the table's reply
     to a row's last move is playable it is the move, whatever the draw above says; the Finished then carries reply_plies,
-    the number of plies the table decided."""
+    the number of plies the table decided.  slots: with tables [count,2,81] (a ReplyTables), the table of every row."""
     def choose(k, recs, live, ok, x0):
         n = ok.sum(1)
         pick = np.argmax(np.cumsum(ok, 1) > select_index(x0, n).astype(np.int64)[:, None], 1)
@@ -379,7 +379,7 @@ def _random_host(pos, key, ctr, max_plies, komi, history, table=None, tactics=No
     decided, draw = [0], choose
 
     def choose(k, recs, live, ok, x0):                                    # noqa: F811  (the draw, overruled by the table)
-        r = reply_moves(replies, recs[live], ok)
+        r = reply_moves(replies, recs[live], ok, None if slots is None else np.asarray(slots)[live])
         decided[0] += int((r >= 0).sum())
         return np.where(r >= 0, r, draw(k, recs, live, ok, x0))
 
@@ -405,7 +405,7 @@ def _tactics(tactics):
 
 
 def random_playouts(pos, seed, counters=None, max_plies=MAX_PLIES, rules="device", komi=L.KOMI, history=True, device=None,
-                    patterns=None, tactics=None, replies=None):
+                    patterns=None, tactics=None, replies=None, slots=None):
     """Play the records pos (uint8 [G,192], numpy or a tensor; not modified) to the end of the game with uniformly random
     eye-safe moves -> Finished, the fields finish_games returns (moves is None with history=False; no min_margin: nothing
     is rounded).  rules="device": one bkt_random_playouts launch per T.MAX_BATCH rows, then bkt_area_score.  rules="host":
@@ -420,10 +420,12 @@ def random_playouts(pos, seed, counters=None, max_plies=MAX_PLIES, rules="device
     replies: None, or a ReplyTable, which every game here reads as it stands (bkt_reply_playouts: where its reply to the
     last move is playable, that is the move) and which is then updated in place with all G games, rows ascending, each
     game a record of its own (bkt_reply_update).  The history is written whatever `history` says; black wins a
-    game whose score is > 0.  The games then depend on the table too."""
+    game whose score is > 0.  The games then depend on the table too.
+    slots: with a ReplyTables (a table per game of a batch), an int array [G], the table of every game: required
+    with a ReplyTables and refused with a ReplyTable."""
     L.check_rules(rules)
     table, tactics = _table(patterns), _tactics(tactics)
-    _check_replies(replies)
+    slots = _check_replies(replies, slots, len(pos))
     max_plies = int(max_plies)
     if not 1 <= max_plies <= 1024:
         raise ValueError("max_plies must be 1..1024 (BKT_MAX_PLAYOUT_PLIES)")
@@ -434,21 +436,23 @@ def random_playouts(pos, seed, counters=None, max_plies=MAX_PLIES, rules="device
     key = L.seed_u64(seed)
     if rules == "host":
         fin = _random_host(pos, key, L.counters_to_host(counters, G), max_plies, komi, history or replies is not None, table,
-                           tactics, replies)
+                           tactics, replies, slots)
         if replies is not None:
             start = np.asarray(_numpy(pos))                               # (moves is cut to the longest game: the same fold)
-            reply_update_host(replies, start, fin.moves, (fin.score > 0) == L.black_to_move(start), G, 1)
+            reply_update_host(replies, start, fin.moves, (fin.score > 0) == L.black_to_move(start), G, 1, slots)
             fin.moves = fin.moves if history else None
         return fin
     dev = _device(device, None, pos)
     start = L.records_to_device(pos, dev, clone=False)
     pos = start.clone()
     ctr = L.counters_to_device(counters, G, dev, clone=False)
+    if slots is not None:
+        slots = torch.from_numpy(slots.astype(np.int32)).to(dev)
     over, plies, moves, status = _play_random_device(pos, key, ctr, max_plies, history or replies is not None, table, tactics,
-                                                     replies)
+                                                     replies, slots)
     score, owner = _area_score_device(pos, komi, True)
     if replies is not None:
-        T.reply_update(start, moves, ((score > 0) == L.black_to_move(start)).to(torch.uint8), G, 1, replies.device(dev))
+        _reply_update_device(start, moves, ((score > 0) == L.black_to_move(start)).to(torch.uint8), G, 1, replies, slots)
     _check_status(status, "selected")
     fin = _finished(pos, moves if history else None, plies.cpu().numpy().astype(np.int64), over.cpu().numpy() != 0,
                     score.cpu().numpy(), owner.cpu().numpy())
@@ -456,16 +460,42 @@ def random_playouts(pos, seed, counters=None, max_plies=MAX_PLIES, rules="device
     return fin
 
 
-def _check_replies(replies):
+def _check_replies(replies, slots=None, records=None):
+    """-> slots as an int64 array [records], or None without tables."""
     if replies is not None and not isinstance(replies, ReplyTable):
-        raise TypeError("replies must be a ReplyTable (it is updated in place) or None")
+        raise TypeError("replies must be a ReplyTable or a ReplyTables (it is updated in place) or None")
+    if not isinstance(replies, ReplyTables):
+        if slots is not None:
+            raise TypeError("slots name the table of every record among a ReplyTables: not with a ReplyTable or without one")
+        return None
+    if slots is None:
+        raise TypeError("a ReplyTables needs slots: the table of every record")
+    slots = np.asarray(_numpy(slots))
+    if slots.shape != (records,) or slots.dtype.kind not in "iu":
+        raise ValueError(f"slots must be an int array of one entry per record, [{records}]")
+    return slots.astype(np.int64)
 
 
-def _play_random_device(pos, key, ctr, max_plies, history, table=None, tactics=None, replies=None):
+def _reply_update_device(recs, moves, won, records, playouts, replies, slots):
+    """bkt_reply_update, or bkt_reply_update_tables with slots (int32 [records] on the device)."""
+    if slots is None:
+        T.reply_update(recs, moves, won, records, playouts, replies.device(recs.device))
+    else:
+        T.reply_update_tables(recs, moves, won, records, playouts, replies.device(recs.device), slots)
+
+
+def _play_random_device(pos, key, ctr, max_plies, history, table=None, tactics=None, replies=None, slots=None):
     """pos uint8 [G,192] and ctr int32 [G,4] on the device; pos is played on in place; table: None or a PatternTable;
-    tactics: None or a TacticTable; replies: None or a ReplyTable, which every launch reads as it stands.
+    tactics: None or a TacticTable; replies: None or a ReplyTable, which every launch reads as it stands, or a ReplyTables with
+    slots int32 [G] on the device, the table of every row (bkt_reply_playouts_tables).
     -> (over uint8 [G], plies int32 [G], moves int16 [G,max_plies] or None, status int32 [G]), T.MAX_BATCH rows per launch."""
     w = None if table is None else table.device(pos.device)
+    if slots is not None:
+        tac, rep = None if tactics is None else tactics.device(pos.device), replies.device(pos.device)
+        parts = [T.reply_playouts_tables(pos[s:s + T.MAX_BATCH], key, ctr[s:s + T.MAX_BATCH], w, tac, rep,
+                                         slots[s:s + T.MAX_BATCH], max_plies, history=history)
+                 for s in range(0, len(pos), T.MAX_BATCH)]
+        return parts[0] if len(parts) == 1 else tuple(None if col[0] is None else torch.cat(col) for col in zip(*parts))
     if replies is not None:
         play = T.reply_playouts
         tables = (w, None if tactics is None else tactics.device(pos.device), replies.device(pos.device))
@@ -511,7 +541,7 @@ def _value_of_wins(w, n):
 
 
 def _playouts(recs, n, key, rules, komi=L.KOMI, table=None, tactics=None, max_plies=MAX_PLIES, score=True, history=False,
-              final=False, counted=0, sides=1, owned=0, replies=None):
+              final=False, counted=0, sides=1, owned=0, replies=None, slots=None):
     """The one playout run: n playouts of each record of recs -- a uint8 [R,192] tensor on the device with
     rules="device", where nothing here waits for it; an array with "host", the mirror -- and what is asked of them, as a
     namespace whose fields are None when they were not asked for:
@@ -527,20 +557,26 @@ def _playouts(recs, n, key, rules, komi=L.KOMI, table=None, tactics=None, max_pl
                                     (bkt_reply_playouts, with history), and after the score one bkt_reply_update folds all
                                     R * n of them into it, in place and on the same stream; the plies the table decided on
                                     the host, None on the device, where nothing counts them.  It needs score=True: the
-                                    update reads `won`."""
+                                    update reads `won`.  With a ReplyTables, slots (an int array [R], required) is the
+                                    table of every record, repeated per playout for the launch
+                                    (bkt_reply_playouts_tables, bkt_reply_update_tables)."""
     R, host = len(recs), rules == "host"
     counted, owned = (R if x is True else int(x) for x in (counted, owned))
-    _check_replies(replies)
+    slots = _check_replies(replies, slots, R)
     if replies is not None and not score:
         raise ValueError("a reply table learns from who won each playout: it needs the scored run (not playout_ownership's)")
     history = history or counted > 0 or replies is not None
     if host:
         recs = np.array(_numpy(recs), np.uint8, order="C")
-        fin = _random_host(np.repeat(recs, n, 0), key, value_counters(recs, n), max_plies, komi, history, table, tactics, replies)
+        fin = _random_host(np.repeat(recs, n, 0), key, value_counters(recs, n), max_plies, komi, history, table, tactics, replies,
+                           None if slots is None else np.repeat(slots, n))
         pos, moves, black_wins = fin.records, fin.moves, fin.score.reshape(R, n) > 0
     else:
         pos = recs.repeat_interleave(n, 0)                                 # a copy: the caller's records stay
-        moves = _play_random_device(pos, key, L.value_counters_device(recs, n), max_plies, history, table, tactics, replies)[2]
+        if slots is not None:
+            slots = torch.from_numpy(slots.astype(np.int32)).to(recs.device)
+        moves = _play_random_device(pos, key, L.value_counters_device(recs, n), max_plies, history, table, tactics, replies,
+                                    None if slots is None else slots.repeat_interleave(n))[2]
         black_wins = _area_score_device(pos, komi, False).view(R, n) > 0 if score else None
     run = SimpleNamespace(value=None, wins=None, won=None, moves=moves, final=pos if final else None, played=None, won_at=None,
                           owner=None, reply_plies=None)
@@ -550,9 +586,9 @@ def _playouts(recs, n, key, rules, komi=L.KOMI, table=None, tactics=None, max_pl
     if replies is not None:                                                # playouts, then score, then update: submit order
         if host:
             run.reply_plies = fin.reply_plies
-            reply_update_host(replies, recs, moves, run.won.reshape(-1), R, n)
+            reply_update_host(replies, recs, moves, run.won.reshape(-1), R, n, slots)
         else:
-            T.reply_update(recs, moves, run.won.reshape(-1).to(torch.uint8), R, n, replies.device(recs.device))
+            _reply_update_device(recs, moves, run.won.reshape(-1).to(torch.uint8), R, n, replies, slots)
     if counted:
         reduce = ((T.amaf_counts, T.amaf_counts_sides), (amaf_counts_host, amaf_counts_sides_host))[host][sides - 1]
         won = run.won[:counted].reshape(-1)
@@ -566,7 +602,7 @@ def _playouts(recs, n, key, rules, komi=L.KOMI, table=None, tactics=None, max_pl
     return run
 
 
-def _run(recs, n, seed, rules, komi, device, patterns, tactics, replies=None, **ask):
+def _run(recs, n, seed, rules, komi, device, patterns, tactics, replies=None, slots=None, **ask):
     """What playout_value, playout_amaf and playout_ownership share: the checks, the upload and _playouts(**ask)."""
     L.check_rules(rules)
     table, tactics = _table(patterns), _tactics(tactics)
@@ -574,17 +610,18 @@ def _run(recs, n, seed, rules, komi, device, patterns, tactics, replies=None, **
     _check_records(recs)
     if rules == "device":
         recs = L.records_to_device(recs, _device(device, None, recs), clone=False)
-    return _playouts(recs, n, L.seed_u64(seed), rules, komi, table, tactics, replies=replies, **ask)
+    return _playouts(recs, n, L.seed_u64(seed), rules, komi, table, tactics, replies=replies, slots=slots, **ask)
 
 
-def playout_value(recs, n, seed, rules="device", komi=L.KOMI, device=None, patterns=None, tactics=None, replies=None):
+def playout_value(recs, n, seed, rules="device", komi=L.KOMI, device=None, patterns=None, tactics=None, replies=None,
+                  slots=None):
     """The Monte-Carlo value of each record, float32 [R] (numpy): (2 w - n) / n, w = the number of n uniformly random
     eye-safe playouts (random_playouts, capped at MAX_PLIES and then scored as they stand) that the side to move wins --
     black wins iff the area score is > 0.  A pure function of the record, `seed` and `n` (value_counters): the row index
     and the rest of the batch do not enter.  recs: uint8 [R,192], numpy or a tensor.  patterns, tactics: as random_playouts.
     replies: None, or a ReplyTable the playouts read and this call then updates in place with all R * n of them:
-    the value is then a function of the table as well."""
-    return _numpy(_run(recs, n, seed, rules, komi, device, patterns, tactics, replies).value)
+    the value is then a function of the table as well.  slots: with a ReplyTables, the table of every record (random_playouts)."""
+    return _numpy(_run(recs, n, seed, rules, komi, device, patterns, tactics, replies, slots).value)
 
 
 class Amaf:
@@ -644,16 +681,17 @@ def amaf_counts_sides_host(moves, won, records, playouts):
     return played, won_at
 
 
-def playout_amaf(recs, n, seed, rules="device", komi=L.KOMI, device=None, patterns=None, tactics=None, sides=1, replies=None):
+def playout_amaf(recs, n, seed, rules="device", komi=L.KOMI, device=None, patterns=None, tactics=None, sides=1, replies=None,
+                 slots=None):
     """playout_value's n playouts of each record with what else they tell -> Amaf: the value (the history does not enter a
     game: the same bits), the wins, and the all-moves-as-first counts of every point (amaf_counts_host has the definition).
     rules="device": the playout launches with their history, `won` built in torch, one bkt_amaf_counts; rules="host": the
     mirror end to end, the same integers.  recs, patterns, tactics: as playout_value.
     sides=2: the counts of both sides, [R,2,81] (one bkt_amaf_counts_sides; amaf_counts_sides_host); value and wins are the
-    same either way.  replies: as playout_value."""
+    same either way.  replies, slots: as playout_value."""
     if sides not in (1, 2):
         raise ValueError("sides must be 1 or 2")
-    run = _run(recs, n, seed, rules, komi, device, patterns, tactics, replies, counted=True, sides=sides)
+    run = _run(recs, n, seed, rules, komi, device, patterns, tactics, replies, slots, counted=True, sides=sides)
     return Amaf(_numpy(run.value), _numpy(run.wins).astype(np.int32), _numpy(run.played), _numpy(run.won_at), n)
 
 
@@ -890,15 +928,24 @@ class PlayoutEvaluator:
     submit order.  Values, priors, RAVE records and criticality are computed as before from that run.  With replies=True a
     value is no longer a function of (record, seed, N) alone: it is a function of those and the requests submitted before
     it.  A given tree search is still deterministic per seed, and device rules and host rules give the same bits.
+    games=G (with replies=True; default None: the one table above, the same launches): `.replies` is a ReplyTables(G), a table
+    per game of a self-play batch, and submit takes games=, the table of every row (selfplay.run_pools passes them); one
+    bkt_reply_playouts_tables and one bkt_reply_update_tables serve all games of a request.  `wants_games` says
+    which of the two an instance is.
     The engine is kept as `policy_engine`, not `engine`: selfplay.run_pools_native hands an evaluator's `engine` to the C
     step loop as its own bk_evaluator, which would compute no playouts -- this class goes through callback_evaluator."""
     wants_positions = True
+    wants_games = False                                                   # True: submit needs games=, a table per game
 
     def __init__(self, engine, playouts=64, seed=0, rules="device", komi=L.KOMI, patterns=None, tactics=None, prior=0.0,
                  prior_k=PRIOR_K, prior_temperature=PRIOR_TEMPERATURE, rave=False, criticality=0.0, pattern_prior=0.0,
-                 prior_patterns=None, prior_tactics=None, replies=False):
+                 prior_patterns=None, prior_tactics=None, replies=False, games=None):
         L.check_rules(rules)
-        self.replies = ReplyTable.empty() if replies else None
+        if games is not None and not replies:
+            raise TypeError("games= is the number of reply tables: it needs replies=True")
+        self.replies = (ReplyTable.empty() if games is None else ReplyTables(games)) if replies else None
+        if games is not None:
+            self.wants_games = True
         self.rave = bool(rave)
         self.criticality = _not_negative(criticality, "criticality")
         if self.criticality > 0.0 and not float(prior) > 0.0:
@@ -926,10 +973,14 @@ class PlayoutEvaluator:
         self.rules, self.komi = rules, komi
         self.positions = self.batches = 0
 
-    def submit(self, recs, n_policy):
+    def submit(self, recs, n_policy, games=None):
         recs = np.ascontiguousarray(recs, np.uint8)
         if recs.ndim != 2 or recs.shape[1] != POS_BYTES:
             raise ValueError(f"a PlayoutEvaluator takes position records uint8 [B, {POS_BYTES}], got {recs.shape}")
+        if self.wants_games and games is None:
+            raise TypeError("this evaluator keeps a reply table per game: submit needs games=, the table of every row")
+        if not self.wants_games and games is not None:
+            raise TypeError("games= names reply tables: this evaluator keeps none per game (replies=True, games=G)")
         self.positions += len(recs)
         self.batches += 1
         ticket = None
@@ -942,13 +993,13 @@ class PlayoutEvaluator:
         # rave: every row with its history, both sides counted, and the prior reads side 0 of the first rows of those counts
         run = _playouts(t, self.playouts, self.seed, self.rules, self.komi, self.patterns, self.tactics,
                         counted=len(recs) if self.rave else counted, sides=2 if self.rave else 1,
-                        owned=counted if self.criticality > 0.0 else 0, replies=self.replies)
+                        owned=counted if self.criticality > 0.0 else 0, replies=self.replies, slots=games)
         if counted and self.pattern_prior > 0.0:                          # (the device's launch: nothing waits for it)
             weights = (move_weights_host if host else _move_weights_device)(t[:counted], self.prior_patterns, self.prior_tactics)
         return SimpleNamespace(ticket=ticket, run=run, n_policy=counted, weights=weights, recs=recs[:counted])
 
     def reset_replies(self):
-        """An empty reply table again (replies=True): what a new game starts with."""
+        """An empty reply table again (replies=True; every table with games=G): what a new game starts with."""
         if self.replies is None:
             raise TypeError("this evaluator keeps no reply table: replies=True")
         self.replies.clear()

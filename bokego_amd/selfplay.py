@@ -79,6 +79,7 @@ TREE_SYMBOLS = {
     "bk_pool_set_rave": (ctypes.c_int, [_VP, ctypes.c_double]),
     "bk_pool_deliver_rave": (None, [_VP, _VP, _VP, ctypes.c_int, _VP, _VP, _VP]),
     "bk_pool_node_rave": (ctypes.c_int, [_VP, ctypes.c_int, ctypes.c_int, _VP, _VP]),
+    "bk_pool_batch_games": (ctypes.c_int, [_VP, _VP, ctypes.c_int]),
     "bk_pool_phase_seconds": (None, [_VP, _VP]),
     "bk_pool_set_dedup": (None, [_VP, ctypes.c_int]),
     "bk_pool_set_lanes": (None, [_VP, ctypes.c_int]),
@@ -261,6 +262,15 @@ class GamePool:
         self._lib.bk_pool_deliver_rave(self._h, probs.ctypes.data, values.ctypes.data, int(playouts), wins.ctypes.data,
                                        played.ctypes.data, won_at.ctypes.data)
 
+    def batch_games(self):
+        """int32 [B]: the game (0..n-1) behind every row of the batch now out, in batch order (bk_pool_batch_games); between
+        a collect and its deliver, and not with de-duplication on, where a row may belong to several games (RuntimeError)."""
+        games = np.empty(self.cap, np.int32)
+        n = self._lib.bk_pool_batch_games(self._h, games.ctypes.data, self.cap)
+        if n < 0:
+            raise RuntimeError("bk_pool_batch_games: no batch is out, or it was laid out with de-duplication on")
+        return games[:n].copy()
+
     def set_rave(self, equiv):
         """RAVE on the pool's games (bk_pool_set_rave): equiv > 0 is the equivalence parameter k, 0 switches it off.
         ValueError when the pool's search mode has no RAVE (leaves > 1, simulate, no value net) or equiv is no such number."""
@@ -395,9 +405,17 @@ class RecordEvaluator(CallableEvaluator):
         return feats, n_policy
 
 
+def _refuse_native(evaluator):
+    """The C step loop's bk_evaluator carries neither the game of a row nor AMAF records (include/bokego_tree.h)."""
+    if getattr(evaluator, "wants_games", False) or getattr(evaluator, "rave", False):
+        raise TypeError("an evaluator with per-game reply tables or RAVE records needs the Python step loop (run_pools): "
+                        "bk_pools_run's bk_evaluator carries neither games nor records")
+
+
 def callback_evaluator(evaluator):
     """Any Python evaluator (submit / finish) as a bk_evaluator for the native step loop: the CPU tests run bk_pools_run on
     the oracle nets this way.  The batch is evaluated inside submit(); keep the returned struct alive while it is in use."""
+    _refuse_native(evaluator)
     state = {"ticket": 0, "error": None}
 
     def submit(_ctx, recs, B, n_policy, probs, values):
@@ -424,6 +442,7 @@ def run_pools_native(pools, evaluator, cap=None):
     """run_pools with the step loop in C (bk_pools_run): no interpreter between two steps.  evaluator: an EngineEvaluator on
     position records (the engine's own bk_evaluator is used), or any evaluator of records (through callbacks).  Returns the
     number of steps; evaluator.positions / .batches are kept up to date."""
+    _refuse_native(evaluator)
     lib = treelib()
     eng = getattr(evaluator, "engine", None)
     if eng is not None and getattr(evaluator, "wants_positions", False) and getattr(evaluator, "value", True) == eng.has_value:
@@ -449,7 +468,11 @@ def run_pools_native(pools, evaluator, cap=None):
 
 def run_pools(pools, evaluator, progress=None):
     """Drive one or two pools to completion.  With two pools the host advances one while the
-    evaluator (GPU) works on the other's batch.  (The step loop in Python; run_pools_native is the same loop in C.)"""
+    evaluator (GPU) works on the other's batch.  (The step loop in Python; run_pools_native is the same loop in C.)
+    An evaluator with wants_games (PlayoutEvaluator(replies=True, games=G): a reply table per game) is told the slot of every
+    row: pool i's games are the slots base[i] .. base[i] + pool.n - 1, base[i] the number of games in the pools before it."""
+    wants_games = getattr(evaluator, "wants_games", False)
+    base = np.concatenate([[0], np.cumsum([p.n for p in pools])]).astype(np.int64)
     inflight = [None] * len(pools)
     live = [True] * len(pools)
     steps = 0
@@ -463,7 +486,10 @@ def run_pools(pools, evaluator, progress=None):
                 if len(feats) == 0:
                     live[i] = False
                 else:
-                    inflight[i] = evaluator.submit(feats, npol)
+                    if wants_games:
+                        inflight[i] = evaluator.submit(feats, npol, games=base[i] + pool.batch_games())
+                    else:
+                        inflight[i] = evaluator.submit(feats, npol)
                     steps += 1
         if progress is not None:
             progress(steps, pools)
@@ -651,7 +677,8 @@ def shard_game_ids(n_games, rank, world):
 def self_play(evaluator, n_games=512, rollouts=400, rank=0, world=1, seed_base=20260, noise_weight=0.25,
               sample_plies=8, expand_thresh=100, max_turns=80, cap=4096, threads=None, n_pools=None,
               reduce_device=None, progress=None, prune=1, record_visits=0, native_comm=None, gids=None, eager_top=None, task_cap=None,
-              dedup=None, native_loop=None, pool_sizes=None, speculate=None, speculate_rows=8, leaves=1, leaves_visit_only=0):
+              dedup=None, native_loop=None, pool_sizes=None, speculate=None, speculate_rows=8, leaves=1, leaves_visit_only=0,
+              rave=0.0):
     """Play this rank's share of a generation; returns (local result dict, reduced stats dict).
     gids: play exactly these game ids instead of the shard `gid % world == rank` -- a game is a pure function of
     `seed_base + gid` and the networks, so the shard of a rank that died can be re-played anywhere (by a survivor, or by
@@ -665,7 +692,29 @@ def self_play(evaluator, n_games=512, rollouts=400, rank=0, world=1, seed_base=2
     speculate: evaluation ahead of expansion in the pools (bk_search_params.speculate; None: small_shard_defaults()).
     leaves: > 1 = the OPT-IN multi-leaf throughput mode (bk_search_params.leaves: up to that many rollouts of a step wait for a
     value together, under virtual loss).  Not the reference's search -- other trees, other games, no parity claim --
-    but still a pure function of the seeds: the games do not depend on sharding, pools, threads or batch grouping.  Default 1: off."""
+    but still a pure function of the seeds: the games do not depend on sharding, pools, threads or batch grouping.  Default 1: off.
+    rave: k > 0 = RAVE in every pool (GamePool.set_rave(k); it needs an evaluator whose finish returns the AMAF records,
+    PlayoutEvaluator(rave=True)).  An evaluator with wants_games (PlayoutEvaluator(replies=True, games=G)) gives every game
+    a reply table of its own, slot = the game's place among this rank's games; the tables are cleared first and G must cover
+    the rank's games.  Either one needs the Python step loop (native_loop=True is a ValueError), and per-game tables need
+    de-duplication off (dedup=True is a ValueError: equal records of different games no longer have equal values).  A game
+    stays a pure function of seed_base + gid: its table sees only its own requests, in its own row order."""
+    rave = float(rave or 0.0)
+    per_game = bool(getattr(evaluator, "wants_games", False))
+    if rave < 0.0:
+        raise ValueError("rave must be 0 (off) or the equivalence parameter k > 0")
+    if rave > 0.0 and not getattr(evaluator, "rave", False):
+        raise TypeError("rave=k needs an evaluator that returns the AMAF records: PlayoutEvaluator(rave=True)")
+    if rave > 0.0 or per_game:
+        if native_loop:
+            raise ValueError("RAVE and per-game reply tables need the Python step loop: bk_pools_run's bk_evaluator carries "
+                             "neither records nor games (native_loop=True)")
+        native_loop = False
+    if per_game:
+        if dedup:
+            raise ValueError("per-game reply tables need de-duplication off: equal records of different games no longer have "
+                             "equal values (dedup=True)")
+        dedup = False
     gids = shard_game_ids(n_games, rank, world) if gids is None else [int(g) for g in gids]
     precision = getattr(getattr(evaluator, "engine", None), "precision", "f16x2")
     leaves = max(1, int(leaves))
@@ -699,7 +748,15 @@ def self_play(evaluator, n_games=512, rollouts=400, rank=0, world=1, seed_base=2
             at += k
     else:
         parts = [gids[i::n_pools] for i in range(n_pools)]
+    if per_game:
+        if evaluator.replies.count < len(gids):
+            raise ValueError(f"the evaluator keeps {evaluator.replies.count} reply tables, this rank plays {len(gids)} games: "
+                             "PlayoutEvaluator(games=) must cover them")
+        evaluator.reset_replies()
     pools = [GamePool([seed_base + g for g in part], prm, cap=cap, threads=threads) for part in parts]
+    if rave > 0.0:
+        for pool in pools:
+            pool.set_rave(rave)
     if task_cap is None:
         # fp32 engine: a step's launch costs whole rounds of 3-board workgroups (0.75 ms per 768 tasks on 256 CUs), and a batch
         # just over a round pays for two: hold batches to the whole number of rounds nearest to what the pool's games ask for
@@ -859,8 +916,22 @@ def parse_args(argv=None):
     ap.add_argument("--replay-shard", metavar="RANK/WORLD", default=None,
                     help="re-play the games a failed rank owned (e.g. 3/8: the gids with gid %% 8 == 3) in this process")
     PlayoutOptions.add_arguments(ap, rave=False, replies=False)       # --playout-value N: not with --value or --host-encode
+    # the pools' own forms of the two options left out above: RAVE records per game, and a reply table per game
+    ap.add_argument("--game-rave", type=float, nargs="?", const=4.0, default=0.0, metavar="K",
+                    help="with --playout-value and --playout-prior: RAVE in every game's search, equivalence parameter K (4 when "
+                         "no value is given, as --playout-rave of gtp and match); the step loop runs in Python")
+    ap.add_argument("--game-replies", action="store_true",
+                    help="with --playout-value: every game's playouts learn a last-good-reply table of their own, all games of a "
+                         "batch in one launch; the step loop runs in Python, without de-duplication")
     args = ap.parse_args(argv)
     args.playout = PlayoutOptions.from_args(ap, args)
+    for flag, on in (("--game-rave", args.game_rave != 0.0), ("--game-replies", args.game_replies)):
+        if on and not args.playout_value:
+            ap.error(f"{flag} goes with the playouts of --playout-value: it needs --playout-value")
+    if not 0.0 <= args.game_rave < float("inf"):
+        ap.error("--game-rave must be a finite number, 0 or more")
+    if args.game_rave and args.value is None and not args.playout_prior > 0.0:
+        ap.error("--game-rave searches without a value net: it needs --playout-prior above 0")
     if args.playout_value:
         for flag, on in (("--value", args.value is not None), ("--host-encode", args.host_encode)):
             if on:
@@ -907,7 +978,12 @@ def main(argv=None):
         if args.playout_prior != 1.0:
             eng = LeafEngine(load(args.policy, "policy_19.bkw"), None, device_id=local_rank, max_batch=args.max_batch,
                              precision=args.precision)
-        ev = PlayoutEvaluator(eng, **args.playout.evaluator_keywords())
+        more = dict(rave=True) if args.game_rave else {}
+        if args.game_replies:
+            here = len(shard_game_ids(args.games, *(int(v) for v in args.replay_shard.split("/")))) if args.replay_shard \
+                else len(shard_game_ids(args.games, rank, world))
+            more.update(replies=True, games=max(1, here))
+        ev = PlayoutEvaluator(eng, **args.playout.evaluator_keywords(), **more)
     else:
         eng = LeafEngine(load(args.policy, "policy_19.bkw"), load(args.value, "value_synth.bkw"), device_id=local_rank,
                          max_batch=args.max_batch, precision=args.precision)
@@ -919,7 +995,7 @@ def main(argv=None):
     local, total = self_play(ev, n_games=args.games, rollouts=args.rollouts, rank=rank, world=world,
                              max_turns=args.max_turns, cap=args.max_batch, threads=args.threads, n_pools=args.pools,
                              reduce_device=on_gpu, record_visits=int(bool(args.out)), gids=gids,
-                             eager_top=args.eager_top, task_cap=args.task_cap)
+                             eager_top=args.eager_top, task_cap=args.task_cap, rave=args.game_rave)
     secs = local["seconds"]
     if world > 1:
         t = torch.tensor([secs], dtype=torch.float64, device=on_gpu or "cpu")

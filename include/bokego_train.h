@@ -370,6 +370,24 @@ size_t bkt_reply_scratch_bytes(int records);
 int bkt_reply_update(const void *pos, const int16_t *moves, int max_plies, const uint8_t *won, int records, int playouts,
                      uint8_t *replies, void *scratch, void *stream);
 
+/* Many tables at once (a table per game of a self-play batch).  The use rule and the update rule are the two
+ * above; new is only which table a row uses.  replies is uint8 [tables][2][81] on the device, and slots, int32 on the
+ * device, names a table per row: slots[i] is the table of row i of bkt_reply_playouts_tables (batch entries) and of record
+ * i of bkt_reply_update_tables (records entries).  A slot outside 0..tables-1 is compared before it indexes anything: such
+ * a row plays as if its table were all 255, and such a record updates no table.  1 <= tables <= BKT_MAX_BATCH.
+ * bkt_reply_playouts_tables: one launch; with tables = 1 and every slot 0 it is bkt_reply_playouts byte for byte.
+ * bkt_reply_update_tables: table t becomes what bkt_reply_update makes of it with the records whose slot is t, in ascending
+ * record order; a table that no record names keeps every byte, whatever it is.  Two launches: bkt_reply_update's first, and
+ * one in which every table is owned by exactly one workgroup.  Integers only, no atomics, no workgroup waits on another.
+ * scratch: bkt_reply_scratch_bytes(records), as above.
+ * replies == NULL or slots == NULL returns BKT_ERR_ARG, nothing is launched and nothing is written; the other argument checks
+ * are those of bkt_reply_playouts and bkt_reply_update. */
+int bkt_reply_playouts_tables(void *pos, int batch, uint64_t seed, const uint32_t *counters, const uint16_t *table,
+                              const uint16_t *tactics, const uint8_t *replies, int tables, const int32_t *slots,
+                              int max_plies, uint8_t *over, int32_t *plies, int16_t *moves, int32_t *status, void *stream);
+int bkt_reply_update_tables(const void *pos, const int16_t *moves, int max_plies, const uint8_t *won, int records,
+                            int playouts, uint8_t *replies, int tables, const int32_t *slots, void *scratch, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -181,6 +181,13 @@ void bk_pool_deliver_rave(bk_pool *p, const float *probs, const float *values, i
                           const int32_t *played, const int32_t *won_at);
 int bk_pool_node_rave(const bk_pool *p, int g, int id, int64_t *rn, int64_t *rw);
 
+/* Which game a batch row belongs to: between a collect (either flavour) and its deliver, games[row] = the index of the game
+ * that asked for row `row` of the batch now out, in batch order; returns the number of rows.  Returns -1 and writes nothing
+ * when no batch is out, when cap is smaller than the batch, or when the batch was laid out with in-batch de-duplication on
+ * (bk_pool_set_dedup): a row may then belong to several games.  An evaluator that keeps something per game -- a reply table
+ * of its own (bkt_reply_playouts_tables, include/bokego_train.h) -- names its rows with this. */
+int bk_pool_batch_games(const bk_pool *p, int32_t *games, int cap);
+
 /* host seconds this pool has spent so far advancing its games (select / expand / backup), writing request rows, and taking
  * deliveries: out3 = {advance, emit, deliver} (tools/selfplay_breakdown.py) */
 void bk_pool_phase_seconds(const bk_pool *p, double *out3);
