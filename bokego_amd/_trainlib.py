@@ -413,15 +413,20 @@ def pattern_codes(pos):
     return codes
 
 
+def _weight_tables(pos, table, tactics):
+    """(table, tactics) as the C calls take them, None staying NULL: each a tensor on the device of pos."""
+    for t in (table, tactics):
+        if t is not None and (not isinstance(t, torch.Tensor) or t.device != pos.device):
+            raise ValueError("the pattern table and the tactics table must be on the device of pos")
+    return (None if table is None else _dev(table, "table", (PATTERN_ENTRIES,), torch.int16),
+            None if tactics is None else _dev(tactics, "tactics", (TACTIC_ENTRIES,), torch.int16))
+
+
 def tactical_playouts(pos, seed, counters, table, tactics, max_plies, over=None, history=True):
     """pattern_playouts whose weights are multiplied by a second table (bkt_tactical_playouts): tactics int16
     [TACTIC_ENTRIES] on the device of pos, the bits of the uint16 entries (256: neutral), indexed by the tactical code;
     table: pattern_playouts' table, or None for no patterns (every pattern weight 256)."""
-    if tactics.device != pos.device or (table is not None and table.device != pos.device):
-        raise ValueError("the pattern table and the tactics table must be on the device of pos")
-    return _playouts("bkt_tactical_playouts", pos, seed, counters,
-                     (None if table is None else _dev(table, "table", (PATTERN_ENTRIES,), torch.int16),
-                      _dev(tactics, "tactics", (TACTIC_ENTRIES,), torch.int16)), max_plies, over, history)
+    return _playouts("bkt_tactical_playouts", pos, seed, counters, _weight_tables(pos, table, tactics), max_plies, over, history)
 
 
 def tactical_codes(pos):
@@ -433,12 +438,18 @@ def tactical_codes(pos):
     return codes
 
 
-def _amaf_args(moves, won, records, playouts):
-    """The checks amaf_counts and amaf_counts_sides share -> (records, playouts, max_plies)."""
+def _sample_rows(records, playouts):
+    """records and playouts as ints, in the range of the reductions over records * playouts rows."""
     records, playouts = int(records), int(playouts)
     if records < 1 or playouts < 1 or records * playouts > MAX_SAMPLE_ROWS:
         raise ValueError(f"records and playouts must be at least 1 and records * playouts at most {MAX_SAMPLE_ROWS}, "
                          f"got {records} x {playouts}")
+    return records, playouts
+
+
+def _amaf_args(moves, won, records, playouts):
+    """The checks amaf_counts, amaf_counts_sides and reply_update share -> (records, playouts, max_plies)."""
+    records, playouts = _sample_rows(records, playouts)
     if not isinstance(moves, torch.Tensor) or moves.dim() != 2 or moves.shape[0] != records * playouts:
         raise ValueError(f"moves must be [{records * playouts}, max_plies]")
     max_plies = int(moves.shape[1])
@@ -486,10 +497,7 @@ def owner_counts(pos, records, playouts, komi=5.5):
     -> (black int32 [records, 81], white int32 [records, 81], agree int32 [records, 81], hist int32 [records, 163],
     black_wins int32 [records]): the playouts in which the point ended up black's, white's and the winner's, the playouts
     by their margin B - W + 81 before komi, and those black won (bkt_area_score's score > 0)."""
-    records, playouts = int(records), int(playouts)
-    if records < 1 or playouts < 1 or records * playouts > MAX_SAMPLE_ROWS:
-        raise ValueError(f"records and playouts must be at least 1 and records * playouts at most {MAX_SAMPLE_ROWS}, "
-                         f"got {records} x {playouts}")
+    records, playouts = _sample_rows(records, playouts)
     if not isinstance(pos, torch.Tensor) or pos.dim() != 2 or tuple(pos.shape) != (records * playouts, POS_BYTES):
         raise ValueError(f"pos must be [{records * playouts}, {POS_BYTES}]")
     komi = float(komi)
@@ -511,94 +519,67 @@ def move_weights(pos, table=None, tactics=None):
     -> int32 [B,81]: the weight tactical_playouts' draw gives the point at the first ply from the record (below 2^24), 0
     where the point is not playable."""
     B = _pos_batch(pos)
-    if (table is not None and (not isinstance(table, torch.Tensor) or table.device != pos.device)) or \
-            (tactics is not None and (not isinstance(tactics, torch.Tensor) or tactics.device != pos.device)):
-        raise ValueError("the pattern table and the tactics table must be on the device of pos")
+    tables = _weight_tables(pos, table, tactics)
     weights = torch.empty((B, 81), dtype=torch.int32, device=pos.device)
-    _check(load().bkt_move_weights(_dev(pos, "pos", dtype=torch.uint8), B,
-                                   None if table is None else _dev(table, "table", (PATTERN_ENTRIES,), torch.int16),
-                                   None if tactics is None else _dev(tactics, "tactics", (TACTIC_ENTRIES,), torch.int16),
+    _check(load().bkt_move_weights(_dev(pos, "pos", dtype=torch.uint8), B, *tables,
                                    _dev(weights, "weights", dtype=torch.int32), _stream(pos)), "bkt_move_weights")
     return weights
 
 
-def reply_playouts(pos, seed, counters, table, tactics, replies, max_plies, over=None, history=True):
+def reply_playouts(pos, seed, counters, table, tactics, replies, max_plies, over=None, history=True, slots=None):
     """tactical_playouts whose draw asks a last-good-reply table first (bkt_reply_playouts; include/bokego_train.h has the
     rule): replies uint8 [2,81] on the device of pos, read only; table and tactics: tactical_playouts' tables, each of which
-    may be None here (neither: the uniform draw)."""
-    for t in (table, tactics, replies):
-        if t is not None and (not isinstance(t, torch.Tensor) or t.device != pos.device):
-            raise ValueError("the pattern table, the tactics table and the reply table must be on the device of pos")
-    return _playouts("bkt_reply_playouts", pos, seed, counters,
-                     (None if table is None else _dev(table, "table", (PATTERN_ENTRIES,), torch.int16),
-                      None if tactics is None else _dev(tactics, "tactics", (TACTIC_ENTRIES,), torch.int16),
-                      _dev(replies, "replies", (2, 81), torch.uint8)), max_plies, over, history)
+    may be None here (neither: the uniform draw).  With slots, many tables in the same launch (bkt_reply_playouts_tables):
+    replies uint8 [tables,2,81] and slots int32 [B] on the device of pos, both read only; row i asks table slots[i], and a
+    slot outside 0..tables-1 plays as an empty table."""
+    weights = _weight_tables(pos, table, tactics)
+    suffix, tables = _reply_tables(replies, slots, _pos_batch(pos), pos.device, "pos")
+    return _playouts("bkt_reply_playouts" + suffix, pos, seed, counters, (*weights, *tables), max_plies, over, history)
 
 
-def reply_update(pos, moves, won, records, playouts, replies, scratch=None):
+def reply_update(pos, moves, won, records, playouts, replies, scratch=None, slots=None):
     """Fold a batch of playouts into a last-good-reply table, in place (bkt_reply_update; include/bokego_train.h has the
     rule): pos uint8 [records,192], the starting records (read only); moves and won as amaf_counts_sides takes them; replies
-    uint8 [2,81].  scratch: None (allocated here) or a uint8 tensor of at least bkt_reply_scratch_bytes(records) bytes.  Two
-    launches on the current stream; nothing waits.  -> replies."""
+    uint8 [2,81].  scratch: None (allocated here) or a uint8 tensor of at least bkt_reply_scratch_bytes(records) bytes.
+    With slots, many tables (bkt_reply_update_tables): replies uint8 [tables,2,81]; slots int32 [records], the table of every
+    record -- table t is folded with the records whose slot is t, in ascending order; a slot outside 0..tables-1 updates
+    nothing.  Two launches on the current stream either way; nothing waits.  -> replies."""
     records, playouts, max_plies = _amaf_args(moves, won, records, playouts)
     if not isinstance(pos, torch.Tensor) or tuple(pos.shape) != (records, POS_BYTES) or pos.device != moves.device:
         raise ValueError(f"pos must be [{records}, {POS_BYTES}] on the device of moves")
-    if not isinstance(replies, torch.Tensor) or replies.device != moves.device:
-        raise ValueError("replies must be on the device of moves")
+    suffix, tables = _reply_tables(replies, slots, records, moves.device, "moves")
+    name = "bkt_reply_update" + suffix
     need = load().bkt_reply_scratch_bytes(records)
     if scratch is None:
         scratch = torch.empty((need,), dtype=torch.uint8, device=moves.device)
     elif not isinstance(scratch, torch.Tensor) or scratch.device != moves.device or scratch.dim() != 1 or scratch.numel() < need:
         raise ValueError(f"scratch must be uint8 [>= {need}] on the device of moves")
-    _check(load().bkt_reply_update(_dev(pos, "pos", dtype=torch.uint8), _dev(moves, "moves", dtype=torch.int16), max_plies,
-                                   _dev(won, "won", (records * playouts,), torch.uint8), records, playouts,
-                                   _dev(replies, "replies", (2, 81), torch.uint8), _dev(scratch, "scratch", dtype=torch.uint8),
-                                   _stream(moves)), "bkt_reply_update")
+    _check(getattr(load(), name)(_dev(pos, "pos", dtype=torch.uint8), _dev(moves, "moves", dtype=torch.int16), max_plies,
+                                 _dev(won, "won", (records * playouts,), torch.uint8), records, playouts, *tables,
+                                 _dev(scratch, "scratch", dtype=torch.uint8), _stream(moves)), name)
     return replies
 
 
 def _reply_tables(replies, slots, n, dev, what):
-    """The checks reply_playouts_tables and reply_update_tables share -> (tables, replies pointer, slots pointer)."""
-    if not isinstance(replies, torch.Tensor) or replies.device != dev or replies.dim() != 3:
-        raise ValueError(f"replies must be uint8 [tables, 2, 81] on the device of {what}")
+    """replies, and slots for n rows, as the C calls take them -> ("", (replies,)) for the single table of slots=None, else
+    ("_tables", (replies, tables, slots)): the suffix of the symbol and its table arguments."""
+    if not isinstance(replies, torch.Tensor) or replies.device != dev or (slots is not None and replies.dim() != 3):
+        raise ValueError(f"replies must be uint8 [2, 81], or with slots [tables, 2, 81], on the device of {what}")
+    if slots is None:
+        return "", (_dev(replies, "replies", (2, 81), torch.uint8),)
     tables = int(replies.shape[0])
     if not 1 <= tables <= MAX_BATCH:
         raise ValueError(f"the number of reply tables must be 1..{MAX_BATCH}, got {tables}")
     if not isinstance(slots, torch.Tensor) or slots.device != dev:
         raise ValueError(f"slots must be int32 [{n}] on the device of {what}")
-    return tables, _dev(replies, "replies", (tables, 2, 81), torch.uint8), _dev(slots, "slots", (n,), torch.int32)
+    return "_tables", (_dev(replies, "replies", (tables, 2, 81), torch.uint8), tables, _dev(slots, "slots", (n,), torch.int32))
 
 
 def reply_playouts_tables(pos, seed, counters, table, tactics, replies, slots, max_plies, over=None, history=True):
-    """reply_playouts over many tables in one launch (bkt_reply_playouts_tables): replies uint8 [tables,2,81] and slots int32
-    [B] on the device of pos, both read only; row i asks table slots[i], and a slot outside 0..tables-1 plays as an empty
-    table."""
-    for t in (table, tactics):
-        if t is not None and (not isinstance(t, torch.Tensor) or t.device != pos.device):
-            raise ValueError("the pattern table and the tactics table must be on the device of pos")
-    tables, r, sl = _reply_tables(replies, slots, _pos_batch(pos), pos.device, "pos")
-    return _playouts("bkt_reply_playouts_tables", pos, seed, counters,
-                     (None if table is None else _dev(table, "table", (PATTERN_ENTRIES,), torch.int16),
-                      None if tactics is None else _dev(tactics, "tactics", (TACTIC_ENTRIES,), torch.int16), r, tables, sl),
-                     max_plies, over, history)
+    """reply_playouts with slots, by position."""
+    return reply_playouts(pos, seed, counters, table, tactics, replies, max_plies, over, history, slots)
 
 
 def reply_update_tables(pos, moves, won, records, playouts, replies, slots, scratch=None):
-    """reply_update over many tables (bkt_reply_update_tables): replies uint8 [tables,2,81], updated in place; slots int32
-    [records], the table of every record -- table t is folded with the records whose slot is t, in ascending order; a slot
-    outside 0..tables-1 updates nothing.  scratch as reply_update.  Two launches on the current stream; nothing waits.
-    -> replies."""
-    records, playouts, max_plies = _amaf_args(moves, won, records, playouts)
-    if not isinstance(pos, torch.Tensor) or tuple(pos.shape) != (records, POS_BYTES) or pos.device != moves.device:
-        raise ValueError(f"pos must be [{records}, {POS_BYTES}] on the device of moves")
-    tables, r, sl = _reply_tables(replies, slots, records, moves.device, "moves")
-    need = load().bkt_reply_scratch_bytes(records)
-    if scratch is None:
-        scratch = torch.empty((need,), dtype=torch.uint8, device=moves.device)
-    elif not isinstance(scratch, torch.Tensor) or scratch.device != moves.device or scratch.dim() != 1 or scratch.numel() < need:
-        raise ValueError(f"scratch must be uint8 [>= {need}] on the device of moves")
-    _check(load().bkt_reply_update_tables(_dev(pos, "pos", dtype=torch.uint8), _dev(moves, "moves", dtype=torch.int16), max_plies,
-                                          _dev(won, "won", (records * playouts,), torch.uint8), records, playouts, r, tables, sl,
-                                          _dev(scratch, "scratch", dtype=torch.uint8), _stream(moves)),
-           "bkt_reply_update_tables")
-    return replies
+    """reply_update with slots, by position."""
+    return reply_update(pos, moves, won, records, playouts, replies, scratch, slots)

@@ -3,9 +3,10 @@
 // 24).  bkt_reply_playouts is bkt_tactical_playouts whose draw asks a reply table first (ReplyDraw around WeightedDraw, or
 // around the uniform draw when there is no table to weigh with); bkt_reply_update folds the histories of a batch of playouts
 // and their winners back into that table, in two launches: reply_summaries_kernel, one workgroup per record, and
-// reply_apply_kernel, one workgroup in all.  bkt_reply_playouts_tables and bkt_reply_update_tables are the same two for many
-// tables at once -- a table per game of a self-play batch, named per row by `slots`: ReplyTablesDraw stages one
-// table per seat of the workgroup, and reply_tables_apply_kernel gives every table a workgroup of its own.
+// the apply launch (reply_apply), one workgroup per table.  bkt_reply_playouts_tables and bkt_reply_update_tables are the same two for
+// many tables at once -- a table per game of a self-play batch, named per row by `slots`.  One table is the case
+// "every row uses table 0": the same draw with one staged table instead of one per seat of the workgroup, and the same apply
+// body with one workgroup and no slots to test.
 
 namespace {
 
@@ -51,36 +52,51 @@ struct TrackedUniformDraw {
     __device__ __forceinline__ bool picks(uint32_t r24, unsigned n) const { return inner.picks(r24, n); }
 };
 
-// The fourth draw: the inner draw, overruled by the reply table.  start() stages the 162 bytes in LDS, published by the ply
-// loop's first barrier.  publish() is the inner one's -- its last barrier is already behind the thread when the reply is
-// looked up, so no barrier is added: the side to move and the last move are the registers the inner draw carries, the entry
-// is one LDS byte every thread of a row reads at the same address, and whether it is playable is one byte of the set
+// The fourth draw: the inner draw, overruled by a reply table.  start() stages SEATS tables of 162 bytes in LDS, published
+// by the ply loop's first barrier.  SEATS == 1: the one table at `replies`, which every row uses; slots, tables and B are
+// not read.  SEATS == PPW: a table per seat, the one of that seat's row (replies + 162 * slot; 255 everywhere for a seat
+// without a row or a slot outside 0..tables-1 -- the slot is compared before it indexes), in two rounds of the workgroup.
+// publish() is the inner one's -- its last barrier is already behind the thread when the reply is looked up, so no barrier
+// is added: the side to move and the last move are the registers the inner draw carries, the entry is one LDS byte of the
+// seat's table that every thread of a row reads at the same address, and whether it is playable is one byte of the set
 // play_body left in L.playable, which nothing writes before the next play().  An entry is compared (<= 80) before it
 // indexes.  Every branch here is per thread and reaches no barrier.  A row that is over, or has no playable point, never
 // gets here with a reply: the loop asks picks() only when total() > 0, and a reply in P makes the total positive.
-template <class Inner>
+template <class Inner, int SEATS>
 struct ReplyDraw {
     Inner inner;
     const uint8_t* __restrict__ replies;
+    const int32_t* __restrict__ slots;
+    int tables, B;
     int q, reply;
+    static constexpr int STRIDE = REPLY_ENTRIES + 2;
     static __device__ __forceinline__ uint8_t* lds() {
-        __shared__ uint8_t table[REPLY_ENTRIES + 2];
+        __shared__ uint8_t table[SEATS * STRIDE];
         return table;
     }
     __device__ __forceinline__ void start(Seat s, int last_move, int turn) {
-        if (s.tid < REPLY_ENTRIES) lds()[s.tid] = replies[s.tid];
+        if (SEATS == 1) {
+            if (s.tid < REPLY_ENTRIES) lds()[s.tid] = replies[s.tid];
+        } else {
+            for (int i = s.tid; i < SEATS * REPLY_ENTRIES; i += 256) {    // two rounds: 486 entries
+                const int seat = i / REPLY_ENTRIES, e = i - REPLY_ENTRIES * seat;
+                const int row = (int)blockIdx.x * PPW + seat;
+                const int slot = row < B ? slots[row] : -1;
+                lds()[STRIDE * seat + e] = slot >= 0 && slot < tables ? replies[(size_t)slot * REPLY_ENTRIES + e] : (uint8_t)BKT_REPLY_NONE;
+            }
+        }
         q = s.q;
         inner.start(s, last_move, turn);
     }
-    __device__ __forceinline__ void play(unsigned char* pos, int B, unsigned char* over, PlyLds* L) const {
-        inner.play(pos, B, over, L);
+    __device__ __forceinline__ void play(unsigned char* pos, int B_, unsigned char* over, PlyLds* L) const {
+        inner.play(pos, B_, over, L);
     }
     __device__ __forceinline__ void publish(Seat s, const PlyLds& L, bool mine, int played) {
         inner.publish(s, L, mine, played);
         const int lm = inner.lm;                                     // the move before this ply: the inner draw keeps it
         reply = -1;
         if (lm >= 0 && lm < NN) {
-            const int r = lds()[(((inner.turn0 + played) & 1) ? NN : 0) + lm];
+            const int r = lds()[(SEATS == 1 ? 0 : STRIDE * s.pp) + (((inner.turn0 + played) & 1) ? NN : 0) + lm];
             if (r < NN && L.playable[NN * s.pp + r] != 0) reply = r;
         }
     }
@@ -98,7 +114,7 @@ __global__ void __launch_bounds__(256) reply_playouts_kernel(unsigned char* pos,
                                                              unsigned char* over, int32_t* __restrict__ plies,
                                                              int16_t* __restrict__ hist, int32_t* __restrict__ status) {
     playouts(pos, B, k0, k1, counters, max_plies, over, plies, hist, status,
-             ReplyDraw<WeightedDraw<OptionalTacticalWeight>>{{{table, tactics}}, replies});
+             ReplyDraw<WeightedDraw<OptionalTacticalWeight>, 1>{{{table, tactics}}, replies});
 }
 
 // With neither table the inner draw is the uniform one: bkt_random_playouts' kernel and its cost, not the tactical kernel's
@@ -110,53 +126,10 @@ __global__ void __launch_bounds__(256) reply_uniform_playouts_kernel(unsigned ch
                                                                      int16_t* __restrict__ hist, int32_t* __restrict__ status) {
     __shared__ unsigned sel[8];
     playouts(pos, B, k0, k1, counters, max_plies, over, plies, hist, status,
-             ReplyDraw<TrackedUniformDraw>{{UniformDraw{sel}, 0, 0}, replies});
+             ReplyDraw<TrackedUniformDraw, 1>{{UniformDraw{sel}, 0, 0}, replies});
 }
 
-// The reply draw over many tables: ReplyDraw with a table per seat.  start() stages PPW tables, the one of each seat's row
-// (replies + 162 * slot; 255 everywhere for a seat without a row or a slot outside 0..tables-1 -- the slot is compared
-// before it indexes), published by the ply loop's first barrier like ReplyDraw's one.  publish() looks the entry up in its own
-// seat's copy: every thread of a row still reads one address.  Nothing else differs: the lookup sits behind the inner
-// draw's last barrier, no branch here reaches a barrier, and an entry is compared (<= 80) before it indexes L.playable.
-template <class Inner>
-struct ReplyTablesDraw {
-    Inner inner;
-    const uint8_t* __restrict__ replies;
-    const int32_t* __restrict__ slots;
-    int tables, B;
-    int q, reply;
-    static constexpr int STRIDE = REPLY_ENTRIES + 2;
-    static __device__ __forceinline__ uint8_t* lds() {
-        __shared__ uint8_t table[PPW * STRIDE];
-        return table;
-    }
-    __device__ __forceinline__ void start(Seat s, int last_move, int turn) {
-        for (int i = s.tid; i < PPW * REPLY_ENTRIES; i += 256) {      // two rounds: 486 entries
-            const int seat = i / REPLY_ENTRIES, e = i - REPLY_ENTRIES * seat;
-            const int row = (int)blockIdx.x * PPW + seat;
-            const int slot = row < B ? slots[row] : -1;
-            lds()[STRIDE * seat + e] = slot >= 0 && slot < tables ? replies[(size_t)slot * REPLY_ENTRIES + e] : (uint8_t)BKT_REPLY_NONE;
-        }
-        q = s.q;
-        inner.start(s, last_move, turn);
-    }
-    __device__ __forceinline__ void play(unsigned char* pos, int B_, unsigned char* over, PlyLds* L) const {
-        inner.play(pos, B_, over, L);
-    }
-    __device__ __forceinline__ void publish(Seat s, const PlyLds& L, bool mine, int played) {
-        inner.publish(s, L, mine, played);
-        const int lm = inner.lm;
-        reply = -1;
-        if (lm >= 0 && lm < NN) {
-            const int r = lds()[STRIDE * s.pp + (((inner.turn0 + played) & 1) ? NN : 0) + lm];
-            if (r < NN && L.playable[NN * s.pp + r] != 0) reply = r;
-        }
-    }
-    __device__ __forceinline__ unsigned total(Seat s) { return inner.total(s); }
-    __device__ __forceinline__ bool picks(uint32_t r24, unsigned S) const {
-        return reply >= 0 ? q == reply : inner.picks(r24, S);
-    }
-};
+// The same two with a table per row: slots[i] names the table of row i among `tables`.
 
 __global__ void __launch_bounds__(256) reply_tables_playouts_kernel(unsigned char* pos, int B, uint32_t k0, uint32_t k1,
                                                                     const uint32_t* __restrict__ counters,
@@ -167,7 +140,7 @@ __global__ void __launch_bounds__(256) reply_tables_playouts_kernel(unsigned cha
                                                                     unsigned char* over, int32_t* __restrict__ plies,
                                                                     int16_t* __restrict__ hist, int32_t* __restrict__ status) {
     playouts(pos, B, k0, k1, counters, max_plies, over, plies, hist, status,
-             ReplyTablesDraw<WeightedDraw<OptionalTacticalWeight>>{{{table, tactics}}, replies, slots, tables, B});
+             ReplyDraw<WeightedDraw<OptionalTacticalWeight>, PPW>{{{table, tactics}}, replies, slots, tables, B});
 }
 
 __global__ void __launch_bounds__(256) reply_tables_uniform_playouts_kernel(unsigned char* pos, int B, uint32_t k0, uint32_t k1,
@@ -179,7 +152,7 @@ __global__ void __launch_bounds__(256) reply_tables_uniform_playouts_kernel(unsi
                                                                             int32_t* __restrict__ status) {
     __shared__ unsigned sel[8];
     playouts(pos, B, k0, k1, counters, max_plies, over, plies, hist, status,
-             ReplyTablesDraw<TrackedUniformDraw>{{UniformDraw{sel}, 0, 0}, replies, slots, tables, B});
+             ReplyDraw<TrackedUniformDraw, PPW>{{UniformDraw{sel}, 0, 0}, replies, slots, tables, B});
 }
 
 constexpr int REPLY_WAVES = 4;                                       // rows staged per barrier round
@@ -259,39 +232,24 @@ __global__ void __launch_bounds__(64 * REPLY_WAVES) reply_summaries_kernel(const
     }
 }
 
-// The second launch: one workgroup; thread e < 162 applies the records' summaries of entry e to replies[e] in record order.
-// The loads do not depend on the entry's value, so they run ahead of the chain of selects.  A value above 80 is in no F.
-__global__ void __launch_bounds__(256) reply_apply_kernel(const uint32_t* __restrict__ scratch, int records,
-                                                          uint8_t* __restrict__ replies) {
-    const int tid = threadIdx.x;
-    if (tid >= REPLY_ENTRIES) return;
-    unsigned x = replies[tid];
-    const uint32_t* in = scratch + tid;
-    for (int r = 0; r < records; ++r, in += REPLY_WORDS * REPLY_ENTRIES) {
-        const uint32_t f0 = in[0], f1 = in[REPLY_ENTRIES], f2 = in[2 * REPLY_ENTRIES], sv = in[3 * REPLY_ENTRIES];
-        const uint32_t word = x < 32u ? f0 : x < 64u ? f1 : f2;
-        if (x < (unsigned)NN && (word >> (x & 31u) & 1u)) x = BKT_REPLY_NONE;
-        if (sv & 256u) x = sv & 255u;
-    }
-    replies[tid] = (uint8_t)x;
-}
-
-// The second launch over many tables: workgroup t owns table t, and thread e < 162 applies to replies[t][e], in ascending
-// record order, the summaries of the records whose slot is t -- reply_apply_kernel's chain with a test in front of it.  The
-// test reads slots[r], the same word in every thread (uniform, and independent of the entry's value, so it and the loads
-// behind it run ahead of the selects).  A table no record names is read and written back unchanged; a slot outside
-// 0..tables-1 equals no workgroup's index, so such a record updates nothing.  One writer per byte, no workgroup reads what
-// another writes: the result is the sequential fold whatever the scheduling.
-__global__ void __launch_bounds__(192) reply_tables_apply_kernel(const uint32_t* __restrict__ scratch, int records,
-                                                                 const int32_t* __restrict__ slots,
-                                                                 uint8_t* __restrict__ replies) {
+// The second launch: workgroup t owns table t, and thread e < 162 applies to replies[t][e], in ascending record order, the
+// summaries of the records whose slot is t: a chain of selects with a test in front of it.  SLOTS == false: every record
+// belongs to the table, slots is not read, and the launch is one workgroup.  The test reads slots[r], the same word in every
+// thread (uniform, and independent of the entry's value, so it and the loads behind it run ahead of the selects).  A value
+// above 80 is in no F.  A table no record names is read and written back unchanged; a slot outside 0..tables-1 equals no
+// workgroup's index, so such a record updates nothing.  One writer per byte, no workgroup reads what another writes: the
+// result is the sequential fold whatever the scheduling.  (The test is a template parameter because a test of the pointer
+// at run time, in one kernel for both, measured 10 us slower over 1,536 records with many tables: DESIGN 25.)
+template <bool SLOTS>
+__device__ __forceinline__ void reply_apply(const uint32_t* __restrict__ scratch, int records,
+                                            const int32_t* __restrict__ slots, uint8_t* __restrict__ replies) {
     const int tid = threadIdx.x;
     if (tid >= REPLY_ENTRIES) return;
     const int t = (int)blockIdx.x;
     uint8_t* mine = replies + (size_t)t * REPLY_ENTRIES + tid;
     unsigned x = *mine;
     for (int r = 0; r < records; ++r) {
-        if (slots[r] != t) continue;
+        if (SLOTS && slots[r] != t) continue;
         const uint32_t* in = scratch + (size_t)r * REPLY_WORDS * REPLY_ENTRIES + tid;
         const uint32_t f0 = in[0], f1 = in[REPLY_ENTRIES], f2 = in[2 * REPLY_ENTRIES], sv = in[3 * REPLY_ENTRIES];
         const uint32_t word = x < 32u ? f0 : x < 64u ? f1 : f2;
@@ -301,17 +259,60 @@ __global__ void __launch_bounds__(192) reply_tables_apply_kernel(const uint32_t*
     *mine = (uint8_t)x;
 }
 
+__global__ void __launch_bounds__(192) reply_apply_kernel(const uint32_t* __restrict__ scratch, int records,
+                                                          uint8_t* __restrict__ replies) {
+    reply_apply<false>(scratch, records, nullptr, replies);
+}
+
+__global__ void __launch_bounds__(192) reply_slots_apply_kernel(const uint32_t* __restrict__ scratch, int records,
+                                                                const int32_t* __restrict__ slots,
+                                                                uint8_t* __restrict__ replies) {
+    reply_apply<true>(scratch, records, slots, replies);
+}
+
+// What the two playout entry points share: slots == nullptr is the single table (tables is then 1), and with neither weight
+// table the inner draw is the uniform one.
+int reply_playouts(void* pos, int batch, uint64_t seed, const uint32_t* counters, const uint16_t* table, const uint16_t* tactics,
+                   const uint8_t* replies, int tables, const int32_t* slots, int max_plies, uint8_t* over, int32_t* plies,
+                   int16_t* moves, int32_t* status, void* stream) {
+    if (!replies || tables < 1 || tables > BKT_MAX_BATCH) return BKT_ERR_ARG;
+    const auto launch = [&](auto kernel, auto... extra) {
+        return launch_playouts(kernel, pos, batch, seed, counters, max_plies, over, plies, moves, status, stream, extra...);
+    };
+    if (!table && !tactics)
+        return slots ? launch(reply_tables_uniform_playouts_kernel, replies, tables, slots)
+                     : launch(reply_uniform_playouts_kernel, replies);
+    return slots ? launch(reply_tables_playouts_kernel, table, tactics, replies, tables, slots)
+                 : launch(reply_playouts_kernel, table, tactics, replies);
+}
+
+// What the two update entry points share: the summaries of the records, then a workgroup per table (slots == nullptr: one,
+// tables is then 1).
+int reply_update(const void* pos, const int16_t* moves, int max_plies, const uint8_t* won, int records, int playouts,
+                 uint8_t* replies, int tables, const int32_t* slots, void* scratch, void* stream) {
+    if (!pos || !moves || !won || !replies || !scratch || records < 1 || playouts < 1 || tables < 1 ||
+        tables > BKT_MAX_BATCH || (int64_t)records * playouts > BKT_MAX_SAMPLE_ROWS || max_plies < 1 ||
+        max_plies > BKT_MAX_PLAYOUT_PLIES)
+        return BKT_ERR_ARG;
+    hipLaunchKernelGGL(reply_summaries_kernel, dim3(records), dim3(64 * REPLY_WAVES), 0, (hipStream_t)stream,
+                       static_cast<const unsigned char*>(pos), moves, max_plies, won, playouts, static_cast<uint32_t*>(scratch));
+    if (hipGetLastError() != hipSuccess) return BKT_ERR_HIP;
+    if (slots)
+        hipLaunchKernelGGL(reply_slots_apply_kernel, dim3(tables), dim3(192), 0, (hipStream_t)stream,
+                           static_cast<const uint32_t*>(scratch), records, slots, replies);
+    else
+        hipLaunchKernelGGL(reply_apply_kernel, dim3(1), dim3(192), 0, (hipStream_t)stream,
+                           static_cast<const uint32_t*>(scratch), records, replies);
+    return hipGetLastError() == hipSuccess ? BKT_OK : BKT_ERR_HIP;
+}
+
 }  // namespace
 
 extern "C" int bkt_reply_playouts(void* pos, int batch, uint64_t seed, const uint32_t* counters, const uint16_t* table,
                                   const uint16_t* tactics, const uint8_t* replies, int max_plies, uint8_t* over,
                                   int32_t* plies, int16_t* moves, int32_t* status, void* stream) {
-    if (!replies) return BKT_ERR_ARG;
-    if (!table && !tactics)
-        return launch_playouts(reply_uniform_playouts_kernel, pos, batch, seed, counters, max_plies, over, plies, moves, status,
-                               stream, replies);
-    return launch_playouts(reply_playouts_kernel, pos, batch, seed, counters, max_plies, over, plies, moves, status, stream,
-                           table, tactics, replies);
+    return reply_playouts(pos, batch, seed, counters, table, tactics, replies, 1, nullptr, max_plies, over, plies, moves, status,
+                          stream);
 }
 
 extern "C" size_t bkt_reply_scratch_bytes(int records) {
@@ -320,40 +321,21 @@ extern "C" size_t bkt_reply_scratch_bytes(int records) {
 
 extern "C" int bkt_reply_update(const void* pos, const int16_t* moves, int max_plies, const uint8_t* won, int records,
                                 int playouts, uint8_t* replies, void* scratch, void* stream) {
-    if (!pos || !moves || !won || !replies || !scratch || records < 1 || playouts < 1 ||
-        (int64_t)records * playouts > BKT_MAX_SAMPLE_ROWS || max_plies < 1 || max_plies > BKT_MAX_PLAYOUT_PLIES)
-        return BKT_ERR_ARG;
-    hipLaunchKernelGGL(reply_summaries_kernel, dim3(records), dim3(64 * REPLY_WAVES), 0, (hipStream_t)stream,
-                       static_cast<const unsigned char*>(pos), moves, max_plies, won, playouts, static_cast<uint32_t*>(scratch));
-    if (hipGetLastError() != hipSuccess) return BKT_ERR_HIP;
-    hipLaunchKernelGGL(reply_apply_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream,
-                       static_cast<const uint32_t*>(scratch), records, replies);
-    return hipGetLastError() == hipSuccess ? BKT_OK : BKT_ERR_HIP;
+    return reply_update(pos, moves, max_plies, won, records, playouts, replies, 1, nullptr, scratch, stream);
 }
 
 extern "C" int bkt_reply_playouts_tables(void* pos, int batch, uint64_t seed, const uint32_t* counters, const uint16_t* table,
                                          const uint16_t* tactics, const uint8_t* replies, int tables, const int32_t* slots,
                                          int max_plies, uint8_t* over, int32_t* plies, int16_t* moves, int32_t* status,
                                          void* stream) {
-    if (!replies || !slots || tables < 1 || tables > BKT_MAX_BATCH) return BKT_ERR_ARG;
-    if (!table && !tactics)
-        return launch_playouts(reply_tables_uniform_playouts_kernel, pos, batch, seed, counters, max_plies, over, plies, moves,
-                               status, stream, replies, tables, slots);
-    return launch_playouts(reply_tables_playouts_kernel, pos, batch, seed, counters, max_plies, over, plies, moves, status,
-                           stream, table, tactics, replies, tables, slots);
+    if (!slots) return BKT_ERR_ARG;
+    return reply_playouts(pos, batch, seed, counters, table, tactics, replies, tables, slots, max_plies, over, plies, moves,
+                          status, stream);
 }
 
 extern "C" int bkt_reply_update_tables(const void* pos, const int16_t* moves, int max_plies, const uint8_t* won, int records,
                                        int playouts, uint8_t* replies, int tables, const int32_t* slots, void* scratch,
                                        void* stream) {
-    if (!pos || !moves || !won || !replies || !slots || !scratch || records < 1 || playouts < 1 || tables < 1 ||
-        tables > BKT_MAX_BATCH || (int64_t)records * playouts > BKT_MAX_SAMPLE_ROWS || max_plies < 1 ||
-        max_plies > BKT_MAX_PLAYOUT_PLIES)
-        return BKT_ERR_ARG;
-    hipLaunchKernelGGL(reply_summaries_kernel, dim3(records), dim3(64 * REPLY_WAVES), 0, (hipStream_t)stream,
-                       static_cast<const unsigned char*>(pos), moves, max_plies, won, playouts, static_cast<uint32_t*>(scratch));
-    if (hipGetLastError() != hipSuccess) return BKT_ERR_HIP;
-    hipLaunchKernelGGL(reply_tables_apply_kernel, dim3(tables), dim3(192), 0, (hipStream_t)stream,
-                       static_cast<const uint32_t*>(scratch), records, slots, replies);
-    return hipGetLastError() == hipSuccess ? BKT_OK : BKT_ERR_HIP;
+    if (!slots) return BKT_ERR_ARG;
+    return reply_update(pos, moves, max_plies, won, records, playouts, replies, tables, slots, scratch, stream);
 }

@@ -30,10 +30,10 @@ class ReplyTable:
     that the device playouts read and update in place -- whichever was written last is the table, and the other is brought
     up to date when it is asked for (`.array` after a device update waits for that device)."""
 
-    def __init__(self, array):
+    def __init__(self, array, shape=(2, 81)):
         array = np.asarray(array)
-        if array.shape != (2, 81) or array.dtype != np.uint8:
-            raise ValueError(f"a reply table is uint8 [2, 81], got {array.dtype} {array.shape}")
+        if array.shape != shape or array.dtype != np.uint8:
+            raise ValueError(f"a reply table is uint8 [2, 81]: expected uint8 {list(shape)}, got {array.dtype} {array.shape}")
         self._array = np.array(array, np.uint8, order="C")
         self._device = {}
         self._live = None                                             # the device whose tensor is newer than _array
@@ -93,13 +93,8 @@ class ReplyTables(ReplyTable):
         count = int(count)
         if not 1 <= count <= 65536:
             raise ValueError("the number of reply tables must be 1..65536 (BKT_MAX_BATCH)")
-        array = np.full((count, 2, 81), NONE, np.uint8) if array is None else np.asarray(array)
-        if array.shape != (count, 2, 81) or array.dtype != np.uint8:
-            raise ValueError(f"{count} reply tables are uint8 [{count}, 2, 81], got {array.dtype} {array.shape}")
+        super().__init__(np.full((count, 2, 81), NONE, np.uint8) if array is None else array, (count, 2, 81))
         self.count = count
-        self._array = np.array(array, np.uint8, order="C")
-        self._device = {}
-        self._live = None
 
     @classmethod
     def empty(cls, count=1):
@@ -126,11 +121,14 @@ def _host_array(table):
     return table.array if isinstance(table, ReplyTable) else np.asarray(table)
 
 
-def _slots_of(t, slots, n, what):
-    """slots for n rows (records) of tables t [count,2,81] -> int64 [n]; None with a single table [2,81]."""
-    if t.ndim == 2:
+def slots_of(table, slots, n, what="record"):
+    """The one check of slots: for n rows (records) of many tables -- a ReplyTables or an array [count,2,81] -- an int array
+    [n] -> int64 [n]; with a single table (a ReplyTable or an array [2,81]) or none at all, slots must be None -> None.  It
+    looks at the kind of `table` only, never at its entries: a table that lives on a device stays there."""
+    many = isinstance(table, ReplyTables) or (table is not None and not isinstance(table, ReplyTable) and np.ndim(table) == 3)
+    if not many:
         if slots is not None:
-            raise TypeError("slots name one of many tables: a single reply table takes none")
+            raise TypeError("slots name the table of every record among many reply tables: not with a single table or without one")
         return None
     if slots is None:
         raise TypeError(f"reply tables need slots: the table of every {what}")
@@ -140,23 +138,23 @@ def _slots_of(t, slots, n, what):
     return slots.astype(np.int64)
 
 
+def _tables_and_slots(t, slots, n, what):
+    """The array t and its checked slots, a single table read as [1,2,81] (a view) with every slot 0
+    -> (tables [count,2,81], slots int64 [n])."""
+    slots = slots_of(t, slots, n, what)
+    return (t[None], np.zeros(n, np.int64)) if slots is None else (t, slots)
+
+
 def reply_moves(table, recs, playable, slots=None):
     """The use rule for rows: recs uint8 [R,192], playable bool [R,81] -> int64 [R]: the reply the table makes the side to
     move play, or -1 where it decides nothing (the last move is no board point, the entry is no point, or the point is
     not playable).  An entry is compared before it indexes.  With tables [count,2,81], slots [R] names each row's table;
     a slot outside 0..count-1 is compared before it indexes, and such a row has no reply."""
-    t = _host_array(table)
+    t, slots = _tables_and_slots(_host_array(table), slots, len(recs), "row")
     lm = L.record_last_move(recs).astype(np.int64)
     c = (L.record_turns(recs) & 1).astype(np.int64)
-    on_board = (lm >= 0) & (lm <= 80)
-    slots = _slots_of(t, slots, len(recs), "row")
-    if slots is not None:
-        on_board = on_board & (slots >= 0) & (slots < len(t))
-        t = t[np.where(on_board, slots, 0)]                           # [R,2,81]: each row's table
-        r = np.where(on_board, t[np.arange(len(recs)), c, np.where(on_board, lm, 0)], NONE).astype(np.int64)
-        ok = (r <= 80) & np.asarray(playable)[np.arange(len(recs)), np.minimum(r, 80)]
-        return np.where(ok, r, -1)
-    r = np.where(on_board, t[c, np.where(on_board, lm, 0)], NONE).astype(np.int64)
+    asks = (lm >= 0) & (lm <= 80) & (slots >= 0) & (slots < len(t))   # the row has a table and a move to reply to
+    r = np.where(asks, t[np.where(asks, slots, 0), c, np.where(asks, lm, 0)], NONE).astype(np.int64)
     ok = (r <= 80) & np.asarray(playable)[np.arange(len(recs)), np.minimum(r, 80)]
     return np.where(ok, r, -1)
 
@@ -195,18 +193,15 @@ def reply_update_host(table, recs, moves, won, records, playouts, slots=None):
                          f"[{records} * {playouts}]")
     if tables.shape[-2:] != (2, 81) or tables.ndim not in (2, 3) or tables.dtype != np.uint8:
         raise ValueError("a reply table is uint8 [2, 81], reply tables uint8 [count, 2, 81]")
-    slots = _slots_of(tables, slots, records, "record")
-    t = tables
+    tables, slots = _tables_and_slots(tables, slots, records, "record")
     lm0 = L.record_last_move(recs).astype(np.int64)
     c0 = (L.record_turns(recs) & 1).astype(np.int64)
     n_set = n_cleared = n_nothing = 0
     for row in range(len(moves)):
         r = row // playouts
-        if slots is not None:
-            if not 0 <= slots[r] < len(tables):
-                continue
-            t = tables[slots[r]]
-        prev, win = int(lm0[r]), bool(won[row])
+        if not 0 <= slots[r] < len(tables):
+            continue
+        t, prev, win = tables[slots[r]], int(lm0[r]), bool(won[row])
         for k, m in enumerate(moves[row].tolist()):
             if m <= MOVE_NONE:
                 break

@@ -86,7 +86,7 @@ from . import _trainlib as T
 from . import go
 from . import lockstep as L
 from .lockstep import record_turns  # noqa: F401  (public here: see __all__)
-from .replies import ReplyTable, ReplyTables, reply_moves, reply_plies_of, reply_update_host
+from .replies import ReplyTable, ReplyTables, reply_moves, reply_plies_of, reply_update_host, slots_of
 
 MAX_PLIES = 400            # default cap of finish_games: 2.8x the longest playout measured (142 plies)
 CHECK_EVERY = 16           # plies between two looks at `over`
@@ -446,13 +446,12 @@ def random_playouts(pos, seed, counters=None, max_plies=MAX_PLIES, rules="device
     start = L.records_to_device(pos, dev, clone=False)
     pos = start.clone()
     ctr = L.counters_to_device(counters, G, dev, clone=False)
-    if slots is not None:
-        slots = torch.from_numpy(slots.astype(np.int32)).to(dev)
+    slots = _slots_device(slots, dev)
     over, plies, moves, status = _play_random_device(pos, key, ctr, max_plies, history or replies is not None, table, tactics,
                                                      replies, slots)
     score, owner = _area_score_device(pos, komi, True)
     if replies is not None:
-        _reply_update_device(start, moves, ((score > 0) == L.black_to_move(start)).to(torch.uint8), G, 1, replies, slots)
+        T.reply_update(start, moves, ((score > 0) == L.black_to_move(start)).to(torch.uint8), G, 1, replies.device(dev), slots=slots)
     _check_status(status, "selected")
     fin = _finished(pos, moves if history else None, plies.cpu().numpy().astype(np.int64), over.cpu().numpy() != 0,
                     score.cpu().numpy(), owner.cpu().numpy())
@@ -461,62 +460,48 @@ def random_playouts(pos, seed, counters=None, max_plies=MAX_PLIES, rules="device
 
 
 def _check_replies(replies, slots=None, records=None):
-    """-> slots as an int64 array [records], or None without tables."""
+    """replies= and slots= of the callers here -> slots as an int64 array [records], or None without tables (slots_of)."""
     if replies is not None and not isinstance(replies, ReplyTable):
         raise TypeError("replies must be a ReplyTable or a ReplyTables (it is updated in place) or None")
-    if not isinstance(replies, ReplyTables):
-        if slots is not None:
-            raise TypeError("slots name the table of every record among a ReplyTables: not with a ReplyTable or without one")
-        return None
-    if slots is None:
-        raise TypeError("a ReplyTables needs slots: the table of every record")
-    slots = np.asarray(_numpy(slots))
-    if slots.shape != (records,) or slots.dtype.kind not in "iu":
-        raise ValueError(f"slots must be an int array of one entry per record, [{records}]")
-    return slots.astype(np.int64)
+    return slots_of(replies, None if slots is None else _numpy(slots), records)
 
 
-def _reply_update_device(recs, moves, won, records, playouts, replies, slots):
-    """bkt_reply_update, or bkt_reply_update_tables with slots (int32 [records] on the device)."""
-    if slots is None:
-        T.reply_update(recs, moves, won, records, playouts, replies.device(recs.device))
-    else:
-        T.reply_update_tables(recs, moves, won, records, playouts, replies.device(recs.device), slots)
+def _slots_device(slots, dev):
+    """Checked slots as the launches take them: int32 on dev; None stays None."""
+    return None if slots is None else torch.from_numpy(slots.astype(np.int32)).to(dev)
+
+
+def _per_batch(call, *rows):
+    """call(*chunks) for every T.MAX_BATCH rows of the tensors `rows` (a None among them is handed on as None), its results
+    concatenated: a tensor, or a tuple of columns in which a None column stays None."""
+    parts = [call(*(x if x is None else x[s:s + T.MAX_BATCH] for x in rows)) for s in range(0, len(rows[0]), T.MAX_BATCH)]
+    if len(parts) == 1:
+        return parts[0]
+    if not isinstance(parts[0], tuple):
+        return torch.cat(parts)
+    return tuple(None if col[0] is None else torch.cat(col) for col in zip(*parts))
 
 
 def _play_random_device(pos, key, ctr, max_plies, history, table=None, tactics=None, replies=None, slots=None):
     """pos uint8 [G,192] and ctr int32 [G,4] on the device; pos is played on in place; table: None or a PatternTable;
     tactics: None or a TacticTable; replies: None or a ReplyTable, which every launch reads as it stands, or a ReplyTables with
-    slots int32 [G] on the device, the table of every row (bkt_reply_playouts_tables).
+    slots int32 [G] on the device, the table of every row.
     -> (over uint8 [G], plies int32 [G], moves int16 [G,max_plies] or None, status int32 [G]), T.MAX_BATCH rows per launch."""
-    w = None if table is None else table.device(pos.device)
-    if slots is not None:
-        tac, rep = None if tactics is None else tactics.device(pos.device), replies.device(pos.device)
-        parts = [T.reply_playouts_tables(pos[s:s + T.MAX_BATCH], key, ctr[s:s + T.MAX_BATCH], w, tac, rep,
-                                         slots[s:s + T.MAX_BATCH], max_plies, history=history)
-                 for s in range(0, len(pos), T.MAX_BATCH)]
-        return parts[0] if len(parts) == 1 else tuple(None if col[0] is None else torch.cat(col) for col in zip(*parts))
+    w, tac = (None if t is None else t.device(pos.device) for t in (table, tactics))
     if replies is not None:
-        play = T.reply_playouts
-        tables = (w, None if tactics is None else tactics.device(pos.device), replies.device(pos.device))
+        play, tables = T.reply_playouts, (w, tac, replies.device(pos.device))
     elif tactics is not None:
-        play, tables = T.tactical_playouts, (w, tactics.device(pos.device))
+        play, tables = T.tactical_playouts, (w, tac)
     elif table is None:
         play, tables = T.random_playouts, ()
     else:
         play, tables = T.pattern_playouts, (w,)
-    parts = [play(pos[s:s + T.MAX_BATCH], key, ctr[s:s + T.MAX_BATCH], *tables, max_plies, history=history)
-             for s in range(0, len(pos), T.MAX_BATCH)]
-    if len(parts) == 1:
-        return parts[0]
-    return tuple(None if col[0] is None else torch.cat(col) for col in zip(*parts))
+    return _per_batch(lambda p, c, s: play(p, key, c, *tables, max_plies, history=history, **({} if s is None else {"slots": s})),
+                      pos, ctr, slots)
 
 
 def _area_score_device(pos, komi, owner):
-    parts = [T.area_score(pos[s:s + T.MAX_BATCH], komi, owner=owner) for s in range(0, len(pos), T.MAX_BATCH)]
-    if len(parts) == 1:
-        return parts[0]
-    return tuple(torch.cat(col) for col in zip(*parts)) if owner else torch.cat(parts)
+    return _per_batch(lambda p: T.area_score(p, komi, owner=owner), pos)
 
 
 def value_counters(recs, n):
@@ -573,8 +558,7 @@ def _playouts(recs, n, key, rules, komi=L.KOMI, table=None, tactics=None, max_pl
         pos, moves, black_wins = fin.records, fin.moves, fin.score.reshape(R, n) > 0
     else:
         pos = recs.repeat_interleave(n, 0)                                 # a copy: the caller's records stay
-        if slots is not None:
-            slots = torch.from_numpy(slots.astype(np.int32)).to(recs.device)
+        slots = _slots_device(slots, recs.device)
         moves = _play_random_device(pos, key, L.value_counters_device(recs, n), max_plies, history, table, tactics, replies,
                                     None if slots is None else slots.repeat_interleave(n))[2]
         black_wins = _area_score_device(pos, komi, False).view(R, n) > 0 if score else None
@@ -588,7 +572,7 @@ def _playouts(recs, n, key, rules, komi=L.KOMI, table=None, tactics=None, max_pl
             run.reply_plies = fin.reply_plies
             reply_update_host(replies, recs, moves, run.won.reshape(-1), R, n, slots)
         else:
-            _reply_update_device(recs, moves, run.won.reshape(-1).to(torch.uint8), R, n, replies, slots)
+            T.reply_update(recs, moves, run.won.reshape(-1).to(torch.uint8), R, n, replies.device(recs.device), slots=slots)
     if counted:
         reduce = ((T.amaf_counts, T.amaf_counts_sides), (amaf_counts_host, amaf_counts_sides_host))[host][sides - 1]
         won = run.won[:counted].reshape(-1)
@@ -815,8 +799,7 @@ def move_weights(recs, patterns=None, tactics=None, rules="device", device=None)
 def _move_weights_device(recs, table, tactics):
     """recs: a uint8 [R,192] tensor on the device -> int32 [R,81] on the device; nothing here waits for it."""
     tables = (None if table is None else table.device(recs.device), None if tactics is None else tactics.device(recs.device))
-    parts = [T.move_weights(recs[s:s + T.MAX_BATCH], *tables) for s in range(0, len(recs), T.MAX_BATCH)]
-    return parts[0] if len(parts) == 1 else torch.cat(parts)
+    return _per_batch(lambda r: T.move_weights(r, *tables), recs)
 
 
 def _not_negative(x, name):

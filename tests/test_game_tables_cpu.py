@@ -400,7 +400,9 @@ def test_headers_and_bindings_name_the_new_symbols():
     assert selfplay.TREE_SYMBOLS["bk_pool_batch_games"] == (I, [P, P, I]) and selfplay.treelib().bk_pool_batch_games
     own = open(os.path.join(CSRC, "bk_playout_reply.hip")).read()
     assert "atomic" not in own.replace("no atomics", "") and "float" not in own
-    assert "struct ReplyTablesDraw" in own and "reply_tables_apply_kernel" in own
+    # one draw and one apply body serve one table and many
+    assert own.count("struct ReplyDraw") == 1 and "ReplyTablesDraw" not in own and "reply_tables_apply_kernel" not in own
+    assert own.count("void reply_apply(") == 1
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")
@@ -418,10 +420,12 @@ def test_the_new_kernels_build_without_spills_or_scratch_at_their_siblings_occup
                  ("sspill", r"SGPRs Spill"), ("vspill", r"VGPRs Spill"), ("lds", r"LDS Size \[bytes/block\]"))}
 
     for new, old in (("reply_tables_playouts_kernel", "reply_playouts_kernel"),
-                     ("reply_tables_uniform_playouts_kernel", "reply_uniform_playouts_kernel"),
-                     ("reply_tables_apply_kernel", "reply_apply_kernel")):
+                     ("reply_tables_uniform_playouts_kernel", "reply_uniform_playouts_kernel")):
         f, g = fields(new), fields(old)
         assert f["scratch"] == 0 and f["sspill"] == 0 and f["vspill"] == 0, (new, f)
         assert f["occupancy"] >= g["occupancy"] >= 4, (new, f, g)
         # two more tables of 162 bytes (+ 2 of padding each), rounded up
         assert f["lds"] <= g["lds"] + 2 * 164 + 8, (new, f, g)
+    for name in ("reply_apply_kernel", "reply_slots_apply_kernel"):   # the two instantiations of the one apply body
+        f = fields(name)
+        assert f["scratch"] == 0 and f["sspill"] == 0 and f["vspill"] == 0 and f["occupancy"] >= 8 and f["lds"] == 0, (name, f)
