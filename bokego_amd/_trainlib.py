@@ -58,6 +58,9 @@ SYMBOLS = {
     "bkt_reply_update": (_I, [_P, _P, _I, _P, _I, _I, _P, _P, _P]),
     "bkt_reply_playouts_tables": (_I, [_P, _I, _U64, _P, _P, _P, _P, _I, _P, _I, _P, _P, _P, _P, _P]),
     "bkt_reply_update_tables": (_I, [_P, _P, _I, _P, _I, _I, _P, _I, _P, _P, _P]),
+    "bkt_reply2_playouts": (_I, [_P, _I, _U64, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P]),
+    "bkt_reply2_scratch_bytes": (_Z, []),
+    "bkt_reply2_update": (_I, [_P, _P, _I, _P, _I, _I, _P, _P, _P]),
 }
 MAX_BATCH = 65536          # BKT_MAX_BATCH
 PRECISIONS = ("fp32", "bf16")
@@ -583,3 +586,36 @@ def reply_playouts_tables(pos, seed, counters, table, tactics, replies, slots, m
 def reply_update_tables(pos, moves, won, records, playouts, replies, slots, scratch=None):
     """reply_update with slots, by position."""
     return reply_update(pos, moves, won, records, playouts, replies, scratch, slots)
+
+
+def _reply2_table(replies2, dev, what):
+    if not isinstance(replies2, torch.Tensor) or replies2.device != dev:
+        raise ValueError(f"replies2 must be uint8 [2, 82, 81] on the device of {what}")
+    return _dev(replies2, "replies2", (2, 82, 81), torch.uint8)
+
+
+def reply2_playouts(pos, seed, counters, table, tactics, replies2, max_plies, over=None, history=True):
+    """reply_playouts whose table is keyed by the last two moves (bkt_reply2_playouts; include/bokego_train.h has the rule):
+    replies2 uint8 [2,82,81] on the device of pos, read only, plane 81 being reply_playouts' table; one table for all rows."""
+    weights = _weight_tables(pos, table, tactics)
+    return _playouts("bkt_reply2_playouts", pos, seed, counters, (*weights, _reply2_table(replies2, pos.device, "pos")), max_plies,
+                     over, history)
+
+
+def reply2_update(pos, moves, won, records, playouts, replies2, scratch=None):
+    """Fold a batch of playouts into a pair reply table, in place (bkt_reply2_update; include/bokego_train.h has the rule):
+    reply_update's arguments with replies2 uint8 [2,82,81].  scratch: None (allocated here) or a uint8 tensor of at least
+    bkt_reply2_scratch_bytes() bytes, 8-byte aligned.  Four launches on the current stream; nothing waits.  -> replies2."""
+    records, playouts, max_plies = _amaf_args(moves, won, records, playouts)
+    if not isinstance(pos, torch.Tensor) or tuple(pos.shape) != (records, POS_BYTES) or pos.device != moves.device:
+        raise ValueError(f"pos must be [{records}, {POS_BYTES}] on the device of moves")
+    table = _reply2_table(replies2, moves.device, "moves")
+    need = load().bkt_reply2_scratch_bytes()
+    if scratch is None:
+        scratch = torch.empty((need,), dtype=torch.uint8, device=moves.device)
+    elif not isinstance(scratch, torch.Tensor) or scratch.device != moves.device or scratch.dim() != 1 or scratch.numel() < need:
+        raise ValueError(f"scratch must be uint8 [>= {need}] on the device of moves")
+    _check(load().bkt_reply2_update(_dev(pos, "pos", dtype=torch.uint8), _dev(moves, "moves", dtype=torch.int16), max_plies,
+                                    _dev(won, "won", (records * playouts,), torch.uint8), records, playouts, table,
+                                    _dev(scratch, "scratch", dtype=torch.uint8), _stream(moves)), "bkt_reply2_update")
+    return replies2

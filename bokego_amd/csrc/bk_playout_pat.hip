@@ -172,3 +172,4 @@ extern "C" int bkt_pattern_playouts(void* pos, int batch, uint64_t seed, const u
 
 #include "bk_playout_tac.hip"   // the tactical playouts: text, part of this translation unit
 #include "bk_playout_reply.hip" // the last-good-reply playouts and their table's update: text likewise
+#include "bk_playout_reply2.hip" // replies keyed by the last two moves and their event-parallel update: likewise

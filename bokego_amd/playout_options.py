@@ -6,7 +6,7 @@ and NativeMCTS as keywords, declared once, checked once, and turned into the key
     PlayoutOptions.from_keywords(kwargs)        the record of NativeMCTS's keywords; TypeError / ValueError
     .search_keywords()                          the keywords of NativeMCTS / NativeGTP: only the options that are set
     .evaluator_keywords()                       the keywords of rollout.PlayoutEvaluator
-    .name_suffix()                              what match calls such an engine: -mc64-pat-amaf1-rave4-lgr
+    .name_suffix()                              what match calls such an engine: -mc64-pat-amaf1-rave4-lgr (-lgr2 with pairs)
 
 Nothing here imports torch or rollout: a front end parses its command line before it loads either.
 """
@@ -43,6 +43,9 @@ FLAGS = {  # field -> (flag, what argparse needs, help)
     "playout_replies": ("--playout-replies", dict(action="store_true"),
                         "with --playout-value: the playouts of a search learn a last-good-reply table from each other and play "
                         "its replies where they are playable (untuned; default off, DESIGN 24)"),
+    "playout_reply_pairs": ("--playout-reply-pairs", dict(action="store_true"),
+                            "with --playout-value: as --playout-replies with replies keyed by the last two moves as well, the "
+                            "single-move table being the fallback (LGRF-2; untuned; default off, DESIGN 26)"),
 }
 
 
@@ -59,6 +62,9 @@ class PlayoutOptions:
     playout_pattern_prior: float = 0.0  # 0: no pattern term in the prior
     prior_patterns: object = None       # the tables of that term; None: the playouts' own
     prior_tactics: object = None
+    # False: no replies keyed by the last two moves; in playout_replies' form, and in front of it so that the
+    # order of the fields before and the last field are what they were.
+    playout_reply_pairs: bool = dataclasses.field(default=False, init=False)
     # False: no reply table.  The last field, and none of the constructor's: its default lives on the class, so a
     # record built without it has the instance attributes (vars()) it had before the option existed, which NativeMCTS copies
     # onto itself; from_args and from_keywords set it, and so may a caller (opts.playout_replies = True).
@@ -77,7 +83,7 @@ class PlayoutOptions:
         there are no per-game RAVE records there, and the games would mix their reply tables.  selfplay has two flags of
         its own instead, --game-rave and --game-replies (RAVE records and a reply table per game)."""
         for field, (flag, kw, text) in FLAGS.items():
-            if (rave or field != "playout_rave") and (replies or field != "playout_replies"):
+            if (rave or field != "playout_rave") and (replies or field not in ("playout_replies", "playout_reply_pairs")):
                 if field == "playout_value" and not (rave and replies):
                     text += "; RAVE and last-good-reply tables are per game here: --game-rave, --game-replies"
                 parser.add_argument(flag, help=text, **kw)
@@ -85,9 +91,11 @@ class PlayoutOptions:
     @classmethod
     def from_args(cls, parser, args):
         """The record of a parsed command line; a refused combination ends in parser.error, which names the flag."""
-        self = cls(**{f: getattr(args, f) for f in FLAGS if hasattr(args, f) and f != "playout_replies"})
-        if hasattr(args, "playout_replies"):
-            self.playout_replies = bool(args.playout_replies)
+        late = ("playout_replies", "playout_reply_pairs")
+        self = cls(**{f: getattr(args, f) for f in FLAGS if hasattr(args, f) and f not in late})
+        for f in late:
+            if hasattr(args, f):
+                setattr(self, f, bool(getattr(args, f)))
         self.check(lambda field: FLAGS[field][0], lambda kind, text: parser.error(text), command_line=True)
         return self
 
@@ -104,6 +112,7 @@ class PlayoutOptions:
                                                             "playout_pattern_prior")),
                    kwargs.get("prior_patterns"), kwargs.get("prior_tactics"))
         self.playout_replies = bool(kwargs.get("playout_replies"))
+        self.playout_reply_pairs = bool(kwargs.get("playout_reply_pairs"))
         self.check(str, fail)
         return self
 
@@ -113,7 +122,8 @@ class PlayoutOptions:
         value, prior = name("playout_value"), name("playout_prior")
         if self.playout_value < 0:
             fail(ValueError, f"{value} must not be negative")
-        for field in ("playout_patterns", "playout_tactics", "playout_prior", "playout_rave", "playout_replies"):
+        for field in ("playout_patterns", "playout_tactics", "playout_prior", "playout_rave", "playout_replies",
+                      "playout_reply_pairs"):
             if self.given(field) and not self.playout_value:
                 fail(TypeError, f"{name(field)} goes with the playouts of {value}: it needs {value}")
         if not 0.0 <= self.playout_prior <= 1.0:
@@ -137,7 +147,8 @@ class PlayoutOptions:
     def search_keywords(self):
         """The keywords of NativeMCTS / NativeGTP: the options that are set, and no others."""
         more = {f: getattr(self, f) for f in ("playout_value", "playout_patterns", "playout_tactics", "playout_prior",
-                                              "playout_rave", "playout_criticality", "playout_replies") if self.given(f)}
+                                              "playout_rave", "playout_criticality", "playout_replies",
+                                              "playout_reply_pairs") if self.given(f)}
         if self.playout_pattern_prior:
             more.update(playout_pattern_prior=self.playout_pattern_prior, prior_patterns=self.prior_patterns,
                         prior_tactics=self.prior_tactics)
@@ -150,8 +161,8 @@ class PlayoutOptions:
                 if self.given(f)}
         if self.playout_rave:
             more["rave"] = True
-        if self.playout_replies:
-            more["replies"] = True
+        if self.playout_replies or self.playout_reply_pairs:
+            more["replies"] = 2 if self.playout_reply_pairs else True        # pairs contain singles
         if self.playout_pattern_prior:
             more.update(pattern_prior=self.playout_pattern_prior, prior_patterns=self.prior_patterns,
                         prior_tactics=self.prior_tactics)
@@ -159,9 +170,9 @@ class PlayoutOptions:
 
     def name_suffix(self):
         """-mc64, then -pat with a playout table, -amaf, -rave, -crit, -pp with their parameters for the terms that are on, and
-        -lgr with the reply table."""
+        -lgr with the reply table, -lgr2 when it is keyed by the last two moves."""
         name = f"-mc{self.playout_value}" + ("-pat" if self.given("playout_patterns") or self.given("playout_tactics") else "")
         for tag, x in (("amaf", self.playout_prior), ("rave", self.playout_rave), ("crit", self.playout_criticality),
                        ("pp", self.playout_pattern_prior)):
             name += f"-{tag}{x:g}" if x else ""
-        return name + ("-lgr" if self.playout_replies else "")
+        return name + ("-lgr2" if self.playout_reply_pairs else "-lgr" if self.playout_replies else "")

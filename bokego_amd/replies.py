@@ -14,6 +14,15 @@ on the device (bkt_reply_playouts reads it, bkt_reply_update writes it) and `.ar
 ReplyTables(count) is `count` such tables in one array, a table per game of a self-play batch: the playouts and
 the update then take `slots`, the table of every row (of every record): the single-table rules applied, per slot, to that
 slot's rows in order.  A slot outside 0..count-1 plays as an empty table and updates nothing.
+
+ReplyTable2 is the table keyed by the last two moves (LGRF-2; the header has its definition too):
+
+    replies2 uint8 [2,82,81]  replies2[c, p2, p1], p2 < 81: the reply of colour c to the opponent's move on p1 that followed
+                              c's own move on p2; plane p2 == 81 is the table above, replies2[c, 81, p1] = replies[c, p1]
+    use       (reply2_moves)        the pair entry when p1 and p2 are board points and its point is playable; else the single
+                                    entry (plane 81) likewise; else the playout's own draw
+    update    (reply2_update_host)  the fold above, applied at every event to [c, 81, p1] and, when p2 is a board point, to
+                                    [c, p2, p1]
 """
 import numpy as np
 
@@ -22,7 +31,8 @@ from . import lockstep as L
 NONE = 255                 # BKT_REPLY_NONE
 MOVE_NONE = -2             # BKT_MOVE_NONE
 
-__all__ = ["NONE", "ReplyTable", "ReplyTables", "reply_moves", "reply_update_host"]
+__all__ = ["NONE", "ReplyTable", "ReplyTable2", "ReplyTables", "reply_moves", "reply_update_host", "reply2_moves",
+           "reply2_plies_of", "reply2_update_host"]
 
 
 class ReplyTable:
@@ -115,6 +125,33 @@ class ReplyTables(ReplyTable):
 
     def __setstate__(self, state):
         self.__init__(state["count"], state["array"])
+
+
+class ReplyTable2(ReplyTable):
+    """uint8 [2,82,81]: the replies keyed by the last two moves, plane 81 the single-move table (module docstring).
+    `.array`, device(dev), clear(), occupancy() (over all planes) and the caching contract are ReplyTable's; singles() is a
+    ReplyTable copy of plane 81 and pairs_occupancy() the entries of planes 0..80 that hold a point."""
+
+    SHAPE = (2, 82, 81)
+
+    def __init__(self, array):
+        array = np.asarray(array)
+        if array.shape != self.SHAPE or array.dtype != np.uint8:
+            raise ValueError(f"a pair reply table is uint8 [2, 82, 81], got {array.dtype} {array.shape}")
+        super().__init__(array, self.SHAPE)
+
+    @classmethod
+    def empty(cls):
+        return cls(np.full(cls.SHAPE, NONE, np.uint8))
+
+    def copy(self):
+        return ReplyTable2(self.array)
+
+    def singles(self):
+        return ReplyTable(self.array[:, 81])
+
+    def pairs_occupancy(self):
+        return int((self.array[:, :81] <= 80).sum())
 
 
 def _host_array(table):
@@ -217,3 +254,86 @@ def reply_update_host(table, recs, moves, won, records, playouts, slots=None):
                     n_nothing += 1
             prev = m
     return n_set, n_cleared, n_nothing
+
+
+def reply2_moves(table, recs, prev2, playable):
+    """The use rule of a pair table for rows: table a ReplyTable2 (or uint8 [2,82,81]), recs uint8 [R,192], prev2 int [R]
+    the move played two plies ago in each row's playout (anything outside 0..80 where there is none or it was a pass),
+    playable bool [R,81] -> (move int64 [R], which int64 [R]): the reply the table makes the side to move play, or -1 where
+    it decides nothing, and which lookup decided -- 2 the pair entry, 1 the single entry (plane 81), 0 neither.  Entries and
+    moves are compared before they index."""
+    t = _host_array(table)
+    playable = np.asarray(playable)
+    rows = np.arange(len(recs))
+    p1 = L.record_last_move(recs).astype(np.int64)
+    p2 = np.asarray(prev2).astype(np.int64)
+    c = (L.record_turns(recs) & 1).astype(np.int64)
+    asks = (p1 >= 0) & (p1 <= 80)
+    pair = asks & (p2 >= 0) & (p2 <= 80)
+    at = np.where(asks, p1, 0)
+    r2 = np.where(pair, t[c, np.where(pair, p2, 81), at], NONE).astype(np.int64)
+    r1 = np.where(asks, t[c, 81, at], NONE).astype(np.int64)
+    ok2 = (r2 <= 80) & playable[rows, np.minimum(r2, 80)]
+    ok1 = (r1 <= 80) & playable[rows, np.minimum(r1, 80)]
+    return np.where(ok2, r2, np.where(ok1, r1, -1)), np.where(ok2, 2, np.where(ok1, 1, 0))
+
+
+def reply2_plies_of(table, recs, moves, playouts):
+    """reply_plies_of for a pair table -> (pair plies, single plies): the plies of finished playouts that the pair entries
+    of `table` (as it stood while they ran) decided, and those its plane 81 decided.  A playable reply is always played and
+    a played move was playable, so the pair entry decided ply t exactly when moves[row, t] equals it, and plane 81 did
+    when the pair entry did not and moves[row, t] equals the single entry."""
+    t = _host_array(table)
+    moves = np.asarray(moves).astype(np.int64)
+    lm0 = np.repeat(L.record_last_move(recs).astype(np.int64), playouts)
+    c0 = np.repeat((L.record_turns(recs) & 1).astype(np.int64), playouts)
+    p1 = np.concatenate([lm0[:, None], moves[:, :-1]], 1)
+    p2 = np.concatenate([np.full((len(moves), 1), MOVE_NONE, np.int64), p1[:, :-1]], 1)
+    live = np.cumsum(moves <= MOVE_NONE, 1) == 0
+    c = c0[:, None] ^ (np.arange(moves.shape[1]) & 1)[None, :]
+    ok = live & (moves >= 0) & (moves <= 80) & (p1 >= 0) & (p1 <= 80)
+    has2 = ok & (p2 >= 0) & (p2 <= 80)
+    at = np.clip(p1, 0, 80)
+    by_pair = has2 & (t[c, np.clip(p2, 0, 80), at] == moves)
+    by_single = ok & ~by_pair & (t[c, 81, at] == moves)
+    return int(by_pair.sum()), int(by_single.sum())
+
+
+def reply2_update_host(table, recs, moves, won, records, playouts):
+    """bkt_reply2_update on the host, the sequential fold itself: table a ReplyTable2 (or a uint8 [2,82,81] array), updated
+    in place; the other arguments as reply_update_host takes them.  Rows ascending, plies ascending up to the first entry
+    <= MOVE_NONE: with c the mover's colour, p1 the move before (the record's last move at t = 0), p2 the move before that
+    (the record's last move at t = 1, none at t = 0) and m = moves[row, t] -- when m and p1 are board points, the fold of
+    reply_update_host is applied to table[c, 81, p1] and, when p2 is a board point, to table[c, p2, p1].
+    -> (set, cleared, nothing): the entries touched that were stored, that were cleared, and that stayed."""
+    t = _host_array(table)
+    records, playouts = int(records), int(playouts)
+    recs, moves, won = np.asarray(recs), np.asarray(moves), np.asarray(won).reshape(-1) != 0
+    if records < 1 or playouts < 1 or moves.ndim != 2 or len(moves) != records * playouts or len(won) != len(moves) \
+            or recs.shape != (records, L.POS_BYTES):
+        raise ValueError(f"recs must be [{records}, {L.POS_BYTES}], moves [{records} * {playouts}, max_plies] and won "
+                         f"[{records} * {playouts}]")
+    if t.shape != (2, 82, 81) or t.dtype != np.uint8:
+        raise ValueError("a pair reply table is uint8 [2, 82, 81]")
+    lm0 = L.record_last_move(recs).astype(np.int64)
+    c0 = (L.record_turns(recs) & 1).astype(np.int64)
+    counts = [0, 0, 0]
+    for row in range(len(moves)):
+        r = row // playouts
+        p1, p2, win = int(lm0[r]), None, bool(won[row])
+        for k, m in enumerate(moves[row].tolist()):
+            if m <= MOVE_NONE:
+                break
+            if 0 <= m <= 80 and 0 <= p1 <= 80:
+                c = int(c0[r]) ^ (k & 1)
+                for plane in (81,) + ((p2,) if p2 is not None and 0 <= p2 <= 80 else ()):
+                    if win == (k % 2 == 0):
+                        t[c, plane, p1] = m
+                        counts[0] += 1
+                    elif t[c, plane, p1] == m:
+                        t[c, plane, p1] = NONE
+                        counts[1] += 1
+                    else:
+                        counts[2] += 1
+            p1, p2 = m, p1
+    return tuple(counts)

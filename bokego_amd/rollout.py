@@ -66,9 +66,13 @@ replies= (a ReplyTable, bokego_amd/replies.py) lets those playouts learn from ea
 forgetting.  The table holds, per colour and previous move, the reply that last won a playout; a playout plays
 it where it is playable (bkt_reply_playouts), and after the score one bkt_reply_update stores the winners' replies of the
 batch and takes the losers' out.  playout_value, playout_amaf and random_playouts update the table they are given in place;
-PlayoutEvaluator(replies=True) keeps one across the requests of a search (opt-in, untuned).
+PlayoutEvaluator(replies=True) keeps one across the requests of a search (opt-in, untuned).  A ReplyTable2 in its place keys
+the replies by the last two moves, with that table as its plane 81 and fallback (bkt_reply2_playouts, bkt_reply2_update;
+DESIGN 26); PlayoutEvaluator(replies=2) keeps one.
 
     python -m bokego_amd.rollout --sgf FILE [--move K] --random --replies [-n 256] [--chunk 16]   # the share of plies the table decided
+    python -m bokego_amd.rollout --sgf FILE [--move K] --random --reply-pairs [-n 256] [--chunk 16]   # the same with a ReplyTable2:
+                                                                          # replies keyed by the last two moves
 
 rules="host" is one loop (_playout_host) on the host rules with the same draws (lockstep's play_host, features_batch
 and area_score_host, bk_pos_is_legal, bk_pos_possible_eye, lockstep.sample_host in float64): the reference the tests
@@ -86,7 +90,8 @@ from . import _trainlib as T
 from . import go
 from . import lockstep as L
 from .lockstep import record_turns  # noqa: F401  (public here: see __all__)
-from .replies import ReplyTable, ReplyTables, reply_moves, reply_plies_of, reply_update_host, slots_of
+from .replies import (ReplyTable, ReplyTable2, ReplyTables, reply2_moves, reply2_plies_of, reply2_update_host, reply_moves, reply_plies_of,
+                      reply_update_host, slots_of)
 
 MAX_PLIES = 400            # default cap of finish_games: 2.8x the longest playout measured (142 plies)
 CHECK_EVERY = 16           # plies between two looks at `over`
@@ -94,8 +99,8 @@ MOVE_NONE = -2             # BKT_MOVE_NONE; in the history: the game was over be
 SEKI_THRESHOLD = 0.5       # |mean ownership| of a stone's point below this: the stone is in seki (rollout_score)
 POS_BYTES = L.POS_BYTES
 
-__all__ = ["MAX_PLIES", "MOVE_NONE", "Amaf", "Finished", "Ownership", "PlayoutEvaluator", "ReplyTable", "ReplyTables", "RolloutScore",
-           "amaf_counts_host", "reply_update_host",
+__all__ = ["MAX_PLIES", "MOVE_NONE", "Amaf", "Finished", "Ownership", "PlayoutEvaluator", "ReplyTable", "ReplyTable2", "ReplyTables", "RolloutScore",
+           "amaf_counts_host", "reply_update_host", "reply2_update_host", "reply_pairs_report",
            "amaf_counts_sides_host", "amaf_prior",
            "default_counters", "finish_games", "format_score", "move_weights", "move_weights_host", "owner_board",
            "ownership_score", "reply_report", "owner_counts_host", "owner_host", "pattern_prior",
@@ -116,6 +121,7 @@ class Finished:
     unfinished  int             rows not over at the cap
     min_margin  float64 [G]     rules="host" only: the smallest lockstep.cdf_margin among the game's draws
     reply_plies int or None     random_playouts(replies=): the plies the reply table decided (rules="host"; None on the device)
+    reply_pair_plies            with a ReplyTable2: those of them its pair entries decided (likewise); None with any other table
     """
 
 
@@ -353,7 +359,9 @@ def _random_host(pos, key, ctr, max_plies, komi, history, table=None, tactics=No
     (a tactics.TacticTable), tactics.select_tactical on those entries (or none) and the entries of the tactical codes.
     replies (a ReplyTable or uint8 [2,81], read only here): the use rule of replies.py goes first -- where the table's reply
     to a row's last move is playable it is the move, whatever the draw above says; the Finished then carries reply_plies,
-    the number of plies the table decided.  slots: with tables [count,2,81] (a ReplyTables), the table of every row."""
+    the number of plies the table decided.  slots: with tables [count,2,81] (a ReplyTables), the table of every row.
+    With a ReplyTable2 the use rule is reply2_moves': the move two plies back is kept per row across the plies here (none at
+    ply 0, the record's last move at ply 1), and reply_pair_plies is the pair entries' share of reply_plies."""
     def choose(k, recs, live, ok, x0):
         n = ok.sum(1)
         pick = np.argmax(np.cumsum(ok, 1) > select_index(x0, n).astype(np.int64)[:, None], 1)
@@ -376,15 +384,23 @@ def _random_host(pos, key, ctr, max_plies, komi, history, table=None, tactics=No
         choose = choose_weighted
     if replies is None:
         return _playout_host(pos, key, ctr, max_plies, komi, choose, "selected", history)
-    decided, draw = [0], choose
+    decided, draw = [0, 0], choose
+    pairs = isinstance(replies, ReplyTable2)
+    prev2 = np.full(len(pos), MOVE_NONE, np.int64)                        # per row: the move two plies back, none yet
 
     def choose(k, recs, live, ok, x0):                                    # noqa: F811  (the draw, overruled by the table)
-        r = reply_moves(replies, recs[live], ok, None if slots is None else np.asarray(slots)[live])
+        if pairs:
+            r, which = reply2_moves(replies, recs[live], prev2[live], ok)
+            prev2[live] = L.record_last_move(recs[live])                  # every live row plays a move or passes now
+            decided[1] += int((which == 2).sum())
+        else:
+            r = reply_moves(replies, recs[live], ok, None if slots is None else np.asarray(slots)[live])
         decided[0] += int((r >= 0).sum())
         return np.where(r >= 0, r, draw(k, recs, live, ok, x0))
 
     fin = _playout_host(pos, key, ctr, max_plies, komi, choose, "selected", history)
     fin.reply_plies = decided[0]
+    fin.reply_pair_plies = decided[1] if pairs else None
     return fin
 
 
@@ -439,7 +455,7 @@ def random_playouts(pos, seed, counters=None, max_plies=MAX_PLIES, rules="device
                            tactics, replies, slots)
         if replies is not None:
             start = np.asarray(_numpy(pos))                               # (moves is cut to the longest game: the same fold)
-            reply_update_host(replies, start, fin.moves, (fin.score > 0) == L.black_to_move(start), G, 1, slots)
+            _update_host(replies, start, fin.moves, (fin.score > 0) == L.black_to_move(start), G, 1, slots)
             fin.moves = fin.moves if history else None
         return fin
     dev = _device(device, None, pos)
@@ -451,12 +467,26 @@ def random_playouts(pos, seed, counters=None, max_plies=MAX_PLIES, rules="device
                                                      replies, slots)
     score, owner = _area_score_device(pos, komi, True)
     if replies is not None:
-        T.reply_update(start, moves, ((score > 0) == L.black_to_move(start)).to(torch.uint8), G, 1, replies.device(dev), slots=slots)
+        _update_device(start, moves, ((score > 0) == L.black_to_move(start)).to(torch.uint8), G, 1, replies, slots)
     _check_status(status, "selected")
     fin = _finished(pos, moves if history else None, plies.cpu().numpy().astype(np.int64), over.cpu().numpy() != 0,
                     score.cpu().numpy(), owner.cpu().numpy())
-    fin.reply_plies = None
+    fin.reply_plies = fin.reply_pair_plies = None
     return fin
+
+
+def _update_host(replies, recs, moves, won, records, playouts, slots):
+    """The fold of the table's kind on the host: reply2_update_host for a ReplyTable2 (slots is then None)."""
+    if isinstance(replies, ReplyTable2):
+        return reply2_update_host(replies, recs, moves, won, records, playouts)
+    return reply_update_host(replies, recs, moves, won, records, playouts, slots)
+
+
+def _update_device(recs, moves, won, records, playouts, replies, slots):
+    """The same on the device, on the current stream: bkt_reply2_update for a ReplyTable2, else bkt_reply_update(_tables)."""
+    if isinstance(replies, ReplyTable2):
+        return T.reply2_update(recs, moves, won, records, playouts, replies.device(recs.device))
+    return T.reply_update(recs, moves, won, records, playouts, replies.device(recs.device), slots=slots)
 
 
 def _check_replies(replies, slots=None, records=None):
@@ -489,7 +519,8 @@ def _play_random_device(pos, key, ctr, max_plies, history, table=None, tactics=N
     -> (over uint8 [G], plies int32 [G], moves int16 [G,max_plies] or None, status int32 [G]), T.MAX_BATCH rows per launch."""
     w, tac = (None if t is None else t.device(pos.device) for t in (table, tactics))
     if replies is not None:
-        play, tables = T.reply_playouts, (w, tac, replies.device(pos.device))
+        play = T.reply2_playouts if isinstance(replies, ReplyTable2) else T.reply_playouts
+        tables = (w, tac, replies.device(pos.device))
     elif tactics is not None:
         play, tables = T.tactical_playouts, (w, tac)
     elif table is None:
@@ -544,7 +575,9 @@ def _playouts(recs, n, key, rules, komi=L.KOMI, table=None, tactics=None, max_pl
                                     the host, None on the device, where nothing counts them.  It needs score=True: the
                                     update reads `won`.  With a ReplyTables, slots (an int array [R], required) is the
                                     table of every record, repeated per playout for the launch
-                                    (bkt_reply_playouts_tables, bkt_reply_update_tables)."""
+                                    (bkt_reply_playouts_tables, bkt_reply_update_tables).  With a ReplyTable2
+                                     the launches are bkt_reply2_playouts and bkt_reply2_update, slots is
+                                    refused, and reply_pair_plies is the pair entries' share of reply_plies (host rules)."""
     R, host = len(recs), rules == "host"
     counted, owned = (R if x is True else int(x) for x in (counted, owned))
     slots = _check_replies(replies, slots, R)
@@ -563,16 +596,16 @@ def _playouts(recs, n, key, rules, komi=L.KOMI, table=None, tactics=None, max_pl
                                     None if slots is None else slots.repeat_interleave(n))[2]
         black_wins = _area_score_device(pos, komi, False).view(R, n) > 0 if score else None
     run = SimpleNamespace(value=None, wins=None, won=None, moves=moves, final=pos if final else None, played=None, won_at=None,
-                          owner=None, reply_plies=None)
+                          owner=None, reply_plies=None, reply_pair_plies=None)
     if score:
         run.won = black_wins == L.black_to_move(recs)[:, None]
         run.wins = run.won.sum(1)
     if replies is not None:                                                # playouts, then score, then update: submit order
         if host:
-            run.reply_plies = fin.reply_plies
-            reply_update_host(replies, recs, moves, run.won.reshape(-1), R, n, slots)
+            run.reply_plies, run.reply_pair_plies = fin.reply_plies, fin.reply_pair_plies
+            _update_host(replies, recs, moves, run.won.reshape(-1), R, n, slots)
         else:
-            T.reply_update(recs, moves, run.won.reshape(-1).to(torch.uint8), R, n, replies.device(recs.device), slots=slots)
+            _update_device(recs, moves, run.won.reshape(-1).to(torch.uint8), R, n, replies, slots)
     if counted:
         reduce = ((T.amaf_counts, T.amaf_counts_sides), (amaf_counts_host, amaf_counts_sides_host))[host][sides - 1]
         won = run.won[:counted].reshape(-1)
@@ -915,6 +948,9 @@ class PlayoutEvaluator:
     per game of a self-play batch, and submit takes games=, the table of every row (selfplay.run_pools passes them); one
     bkt_reply_playouts_tables and one bkt_reply_update_tables serve all games of a request.  `wants_games` says
     which of the two an instance is.
+    replies=2: `.replies` is a ReplyTable2, replies keyed by the last two moves with the single-move table as its
+    plane 81 (bkt_reply2_playouts, bkt_reply2_update; the same stream order, the same determinism).  Pair tables per game do
+    not exist: replies=2 with games= is a TypeError.
     The engine is kept as `policy_engine`, not `engine`: selfplay.run_pools_native hands an evaluator's `engine` to the C
     step loop as its own bk_evaluator, which would compute no playouts -- this class goes through callback_evaluator."""
     wants_positions = True
@@ -926,7 +962,12 @@ class PlayoutEvaluator:
         L.check_rules(rules)
         if games is not None and not replies:
             raise TypeError("games= is the number of reply tables: it needs replies=True")
-        self.replies = (ReplyTable.empty() if games is None else ReplyTables(games)) if replies else None
+        if replies == 2 and not isinstance(replies, bool):
+            if games is not None:
+                raise TypeError("pair reply tables per game do not exist: replies=2 goes without games= (replies=True takes it)")
+            self.replies = ReplyTable2.empty()
+        else:
+            self.replies = (ReplyTable.empty() if games is None else ReplyTables(games)) if replies else None
         if games is not None:
             self.wants_games = True
         self.rave = bool(rave)
@@ -1139,7 +1180,10 @@ def _parse(argv):
     ap.add_argument("--replies", action="store_true",
                     help="with --random: play the playouts in chunks that learn a last-good-reply table from each other, and "
                          "print the share of plies the table decided and its occupancy instead of the score")
-    ap.add_argument("--chunk", type=int, default=16, metavar="C", help="with --replies: playouts per chunk")
+    ap.add_argument("--reply-pairs", action="store_true",
+                    help="with --random: as --replies with a table keyed by the last two moves (LGRF-2): print the shares of "
+                         "plies its pair entries and its single entries decided, and the occupancy of both parts")
+    ap.add_argument("--chunk", type=int, default=16, metavar="C", help="with --replies or --reply-pairs: playouts per chunk")
     ap.add_argument("--sides", type=int, default=1, choices=(1, 2),
                     help="with --amaf: 2 also prints the opponent's heaviest points (the two-sided counts RAVE is fed with)")
     ap.add_argument("-n", dest="n", type=int, default=256, help="playouts")
@@ -1155,6 +1199,9 @@ def _parse(argv):
         ap.error("--weights reads the one-launch playouts' draw: it needs --random, and not --amaf or --ownership")
     if args.replies and (not args.random or args.amaf or args.ownership or args.weights):
         ap.error("--replies reads the one-launch playouts: it needs --random, and not --amaf, --ownership or --weights")
+    if args.reply_pairs and (not args.random or args.amaf or args.ownership or args.weights or args.replies):
+        ap.error("--reply-pairs reads the one-launch playouts: it needs --random, and not --amaf, --ownership, --weights or "
+                 "--replies (pairs contain singles)")
     if args.chunk < 1:
         ap.error("--chunk must be at least 1")
     if args.sides != 1 and not args.amaf:
@@ -1204,6 +1251,24 @@ def reply_report(recs, n, seed, chunk, rules="device", komi=L.KOMI, **kw):
             "occupancy": table.occupancy(), "black_win": black / n}
 
 
+def reply_pairs_report(recs, n, seed, chunk, rules="device", komi=L.KOMI, **kw):
+    """reply_report with a ReplyTable2 -> a dict: the plies played, those the pair entries and the single
+    entries decided and their shares, the occupancy of both parts of the table at the end and black's share of the wins."""
+    table, plies, pair, single, black = ReplyTable2.empty(), 0, 0, 0, 0
+    ctr = default_counters(n, np.repeat(record_turns(recs), n))
+    for s in range(0, n, chunk):
+        c = min(chunk, n - s)
+        before = table.copy()
+        fin = random_playouts(np.repeat(recs, c, 0), seed, counters=ctr[s:s + c], rules=rules, komi=komi, replies=table, **kw)
+        plies += int(fin.plies.sum())
+        by_pair, by_single = reply2_plies_of(before, np.repeat(recs, c, 0), fin.moves, 1)
+        pair, single = pair + by_pair, single + by_single
+        black += int((fin.score > 0).sum())
+    return {"playouts": n, "chunk": chunk, "plies": plies, "pair_plies": pair, "single_plies": single,
+            "pair_share": pair / max(plies, 1), "single_share": single / max(plies, 1),
+            "pair_occupancy": table.pairs_occupancy(), "single_occupancy": table.singles().occupancy(), "black_win": black / n}
+
+
 def main(argv=None):
     args = _parse(argv)
     game = sgf_position(args.sgf, args.move)
@@ -1233,6 +1298,11 @@ def main(argv=None):
     if args.replies:
         print(json.dumps(reply_report(_as_records(game), args.n, args.seed, args.chunk, komi=args.komi, patterns=args.patterns,
                                       tactics=args.tactics, device=torch.device("cuda", args.device))))
+        return
+    if args.reply_pairs:
+        print(json.dumps(reply_pairs_report(_as_records(game), args.n, args.seed, args.chunk, komi=args.komi,
+                                            patterns=args.patterns, tactics=args.tactics,
+                                            device=torch.device("cuda", args.device))))
         return
     if args.ownership:
         o = playout_ownership(_as_records(game), args.n, args.seed, komi=args.komi, device=torch.device("cuda", args.device),

@@ -388,6 +388,43 @@ int bkt_reply_playouts_tables(void *pos, int batch, uint64_t seed, const uint32_
 int bkt_reply_update_tables(const void *pos, const int16_t *moves, int max_plies, const uint8_t *won, int records,
                             int playouts, uint8_t *replies, int tables, const int32_t *slots, void *scratch, void *stream);
 
+/* Replies keyed by the last two moves (LGRF-2, Baier & Drake 2010; bokego_amd/replies.py ReplyTable2).
+ * replies2 is uint8 [2][82][81], 13284 bytes, 4-byte aligned (a misaligned pointer is BKT_ERR_ARG).
+ * replies2[c][p2][p1] with p2 < 81 is the reply of colour c to the opponent's move on p1 that followed c's own move on p2.
+ * Plane p2 == 81 is the LGRF-1 table: replies2[c][81][p1] is replies[c][p1] above.  Values are as there: 0..80 a point,
+ * BKT_REPLY_NONE none, any other value above 80 treated as none and compared before it indexes anything.
+ *
+ * Use (in a playout).  c is the side to move, p1 the last move, p2 the move played two plies ago in this playout, P the
+ * playable set.  At ply 1, p2 is the record's last move; at ply 0 there is no p2, because a record holds one move.
+ *   if p1 and p2 are board points and replies2[c][p2][p1] is a point of P, that is the move;
+ *   else, if p1 is a board point and replies2[c][81][p1] is a point of P, that is the move;
+ *   else the inner draw decides (uniform, pattern or tactical, as in bkt_reply_playouts).
+ * A pass or "no move" as p1 asks nothing; as p2 it skips the pair lookup only.  The Philox word stays indexed by the ply.
+ *
+ * bkt_reply2_playouts is bkt_reply_playouts' contract with replies2 in place of replies: one launch, one table for all
+ * rows.  replies2 == NULL or misaligned returns BKT_ERR_ARG and nothing is launched.  With planes 0..80 all 255 it plays
+ * bkt_reply_playouts' games with plane 81 as the table, byte for byte.
+ *
+ * Update.  The sequential fold of bkt_reply_update: rows ascending, plies ascending up to the first entry <= BKT_MOVE_NONE
+ * or max_plies.  An event is a ply t whose move m and whose p1 are board points (p1: the record's last move at t = 0, else
+ * moves[row, t - 1]); it is applied to entry [c][81][p1], and when p2 is a board point (the record's last move at t = 1,
+ * moves[row, t - 2] from t = 2 on) also to entry [c][p2][p1]: a mover who won the row stores m; a mover who lost clears the
+ * entry if it holds m.  Entries without an event keep their value, whatever it is.  Plane 81 therefore ends as
+ * bkt_reply_update leaves replies from the same start.
+ * bkt_reply2_update computes that fold event-parallel, in four launches on `stream`: the scratch is initialised; every
+ * winner's event takes a 64-bit atomic max of (row * max_plies + t + 1) << 8 | m on its entries' keys; every loser's event
+ * reads the key and the table and flags the entry when its m would clear it (a later clear of the last store's value, or
+ * with no store a clear of the value on entry); one thread per entry writes the table.  Integers only; integer max is
+ * order-independent and a flag is only ever written with one value, so the result is the fold's whatever the scheduling.
+ * scratch: bkt_reply2_scratch_bytes() = 119556 bytes on the device, 8-byte aligned, whatever `records`; its contents on
+ * entry do not matter.  The argument checks are bkt_reply_update's; else BKT_ERR_ARG, nothing launched, nothing written. */
+int bkt_reply2_playouts(void *pos, int batch, uint64_t seed, const uint32_t *counters, const uint16_t *table,
+                        const uint16_t *tactics, const uint8_t *replies2, int max_plies, uint8_t *over, int32_t *plies,
+                        int16_t *moves, int32_t *status, void *stream);
+size_t bkt_reply2_scratch_bytes(void);
+int bkt_reply2_update(const void *pos, const int16_t *moves, int max_plies, const uint8_t *won, int records, int playouts,
+                      uint8_t *replies2, void *scratch, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
