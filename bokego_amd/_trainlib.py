@@ -61,6 +61,9 @@ SYMBOLS = {
     "bkt_reply2_playouts": (_I, [_P, _I, _U64, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P]),
     "bkt_reply2_scratch_bytes": (_Z, []),
     "bkt_reply2_update": (_I, [_P, _P, _I, _P, _I, _I, _P, _P, _P]),
+    "bkt_reply2_playouts_tables": (_I, [_P, _I, _U64, _P, _P, _P, _P, _I, _P, _I, _P, _P, _P, _P, _P]),
+    "bkt_reply2_tables_scratch_bytes": (_Z, [_I]),
+    "bkt_reply2_update_tables": (_I, [_P, _P, _I, _P, _I, _I, _P, _I, _P, _P, _P]),
 }
 MAX_BATCH = 65536          # BKT_MAX_BATCH
 PRECISIONS = ("fp32", "bf16")
@@ -588,34 +591,67 @@ def reply_update_tables(pos, moves, won, records, playouts, replies, slots, scra
     return reply_update(pos, moves, won, records, playouts, replies, scratch, slots)
 
 
+MAX_REPLY2_TABLES = 4096   # BKT_MAX_REPLY2_TABLES
+_reply2_scratch = {}       # (device, stream, bytes) -> the scratch of reply2_update with slots
+
+
 def _reply2_table(replies2, dev, what):
     if not isinstance(replies2, torch.Tensor) or replies2.device != dev:
         raise ValueError(f"replies2 must be uint8 [2, 82, 81] on the device of {what}")
     return _dev(replies2, "replies2", (2, 82, 81), torch.uint8)
 
 
-def reply2_playouts(pos, seed, counters, table, tactics, replies2, max_plies, over=None, history=True):
+def _reply2_tables(replies2, slots, n, dev, what):
+    """_reply_tables for pair tables -> ("", (replies2,)) for the single table of slots=None, else ("_tables", (replies2,
+    tables, slots))."""
+    if slots is None:
+        return "", (_reply2_table(replies2, dev, what),)
+    if not isinstance(replies2, torch.Tensor) or replies2.device != dev or replies2.dim() != 4:
+        raise ValueError(f"replies2 must with slots be uint8 [tables, 2, 82, 81] on the device of {what}")
+    tables = int(replies2.shape[0])
+    if not 1 <= tables <= MAX_REPLY2_TABLES:
+        raise ValueError(f"the number of pair reply tables must be 1..{MAX_REPLY2_TABLES}, got {tables}")
+    if not isinstance(slots, torch.Tensor) or slots.device != dev:
+        raise ValueError(f"slots must be int32 [{n}] on the device of {what}")
+    return "_tables", (_dev(replies2, "replies2", (tables, 2, 82, 81), torch.uint8), tables,
+                       _dev(slots, "slots", (n,), torch.int32))
+
+
+def reply2_playouts(pos, seed, counters, table, tactics, replies2, max_plies, over=None, history=True, slots=None):
     """reply_playouts whose table is keyed by the last two moves (bkt_reply2_playouts; include/bokego_train.h has the rule):
-    replies2 uint8 [2,82,81] on the device of pos, read only, plane 81 being reply_playouts' table; one table for all rows."""
+    replies2 uint8 [2,82,81] on the device of pos, read only, plane 81 being reply_playouts' table; one table for all rows.
+    With slots, many tables in the same launch (bkt_reply2_playouts_tables): replies2 uint8 [tables,2,82,81] and slots int32
+    [B] on the device of pos, both read only; row i asks table slots[i], and a slot outside 0..tables-1 plays as an empty
+    table."""
     weights = _weight_tables(pos, table, tactics)
-    return _playouts("bkt_reply2_playouts", pos, seed, counters, (*weights, _reply2_table(replies2, pos.device, "pos")), max_plies,
-                     over, history)
+    suffix, tables = _reply2_tables(replies2, slots, _pos_batch(pos), pos.device, "pos")
+    return _playouts("bkt_reply2_playouts" + suffix, pos, seed, counters, (*weights, *tables), max_plies, over, history)
 
 
-def reply2_update(pos, moves, won, records, playouts, replies2, scratch=None):
+def reply2_update(pos, moves, won, records, playouts, replies2, scratch=None, slots=None):
     """Fold a batch of playouts into a pair reply table, in place (bkt_reply2_update; include/bokego_train.h has the rule):
     reply_update's arguments with replies2 uint8 [2,82,81].  scratch: None (allocated here) or a uint8 tensor of at least
-    bkt_reply2_scratch_bytes() bytes, 8-byte aligned.  Four launches on the current stream; nothing waits.  -> replies2."""
+    bkt_reply2_scratch_bytes() bytes, 8-byte aligned.  Four launches on the current stream; nothing waits.
+    With slots, many tables (bkt_reply2_update_tables): replies2 uint8 [tables,2,82,81]; slots int32 [records], the table of
+    every record -- table t is folded with the records whose slot is t, in ascending order; a slot outside 0..tables-1
+    updates nothing.  The scratch is then bkt_reply2_tables_scratch_bytes(tables) bytes, and the one allocated here is
+    kept per device, stream and size: the launches that use it are ordered by the stream.  -> replies2."""
     records, playouts, max_plies = _amaf_args(moves, won, records, playouts)
     if not isinstance(pos, torch.Tensor) or tuple(pos.shape) != (records, POS_BYTES) or pos.device != moves.device:
         raise ValueError(f"pos must be [{records}, {POS_BYTES}] on the device of moves")
-    table = _reply2_table(replies2, moves.device, "moves")
-    need = load().bkt_reply2_scratch_bytes()
-    if scratch is None:
+    suffix, tables = _reply2_tables(replies2, slots, records, moves.device, "moves")
+    name = "bkt_reply2_update" + suffix
+    need = load().bkt_reply2_scratch_bytes() if slots is None else load().bkt_reply2_tables_scratch_bytes(tables[1])
+    if scratch is None and slots is not None:
+        key = (moves.device, torch.cuda.current_stream(moves.device).cuda_stream, need)
+        if key not in _reply2_scratch:
+            _reply2_scratch[key] = torch.empty((need,), dtype=torch.uint8, device=moves.device)
+        scratch = _reply2_scratch[key]
+    elif scratch is None:
         scratch = torch.empty((need,), dtype=torch.uint8, device=moves.device)
     elif not isinstance(scratch, torch.Tensor) or scratch.device != moves.device or scratch.dim() != 1 or scratch.numel() < need:
         raise ValueError(f"scratch must be uint8 [>= {need}] on the device of moves")
-    _check(load().bkt_reply2_update(_dev(pos, "pos", dtype=torch.uint8), _dev(moves, "moves", dtype=torch.int16), max_plies,
-                                    _dev(won, "won", (records * playouts,), torch.uint8), records, playouts, table,
-                                    _dev(scratch, "scratch", dtype=torch.uint8), _stream(moves)), "bkt_reply2_update")
+    _check(getattr(load(), name)(_dev(pos, "pos", dtype=torch.uint8), _dev(moves, "moves", dtype=torch.int16), max_plies,
+                                 _dev(won, "won", (records * playouts,), torch.uint8), records, playouts, *tables,
+                                 _dev(scratch, "scratch", dtype=torch.uint8), _stream(moves)), name)
     return replies2

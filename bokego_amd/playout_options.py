@@ -81,11 +81,12 @@ class PlayoutOptions:
     def add_arguments(parser, rave=True, replies=True):
         """rave=False, replies=False: a front end whose one evaluator serves many games at once (selfplay) takes neither --
         there are no per-game RAVE records there, and the games would mix their reply tables.  selfplay has two flags of
-        its own instead, --game-rave and --game-replies (RAVE records and a reply table per game)."""
+        its own instead, --game-rave and --game-replies (RAVE records and a reply table per game), and
+        --game-reply-pairs (a pair reply table per game)."""
         for field, (flag, kw, text) in FLAGS.items():
             if (rave or field != "playout_rave") and (replies or field not in ("playout_replies", "playout_reply_pairs")):
                 if field == "playout_value" and not (rave and replies):
-                    text += "; RAVE and last-good-reply tables are per game here: --game-rave, --game-replies"
+                    text += "; RAVE and last-good-reply tables are per game here: --game-rave, --game-replies, --game-reply-pairs"
                 parser.add_argument(flag, help=text, **kw)
 
     @classmethod

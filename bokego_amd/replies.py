@@ -23,6 +23,10 @@ ReplyTable2 is the table keyed by the last two moves (LGRF-2; the hea
                                     entry (plane 81) likewise; else the playout's own draw
     update    (reply2_update_host)  the fold above, applied at every event to [c, 81, p1] and, when p2 is a board point, to
                                     [c, p2, p1]
+
+ReplyTables2(count) is `count` pair tables in one array, a pair table per game of a self-play batch, with `slots`
+exactly as a ReplyTables takes them: reply2_moves and reply2_update_host are then the single-table rules applied, per slot,
+to that slot's rows in order.
 """
 import numpy as np
 
@@ -31,7 +35,7 @@ from . import lockstep as L
 NONE = 255                 # BKT_REPLY_NONE
 MOVE_NONE = -2             # BKT_MOVE_NONE
 
-__all__ = ["NONE", "ReplyTable", "ReplyTable2", "ReplyTables", "reply_moves", "reply_update_host", "reply2_moves",
+__all__ = ["NONE", "ReplyTable", "ReplyTable2", "ReplyTables", "ReplyTables2", "reply_moves", "reply_update_host", "reply2_moves",
            "reply2_plies_of", "reply2_update_host"]
 
 
@@ -154,15 +158,63 @@ class ReplyTable2(ReplyTable):
         return int((self.array[:, :81] <= 80).sum())
 
 
+class ReplyTables2(ReplyTable):
+    """uint8 [count,2,82,81]: `count` pair reply tables, table i for the rows whose slot is i.  `.array`, device(dev),
+    clear() and the caching contract are ReplyTable's; occupancy() and pairs_occupancy() are per table, table(i) is a
+    ReplyTable2 copy of table i and singles() a ReplyTables copy of the plane-81s."""
+
+    MAX = 4096                                                        # BKT_MAX_REPLY2_TABLES
+
+    def __init__(self, count, array=None):
+        count = int(count)
+        if not 1 <= count <= self.MAX:
+            raise ValueError(f"the number of pair reply tables must be 1..{self.MAX} (BKT_MAX_REPLY2_TABLES)")
+        shape = (count,) + ReplyTable2.SHAPE
+        array = np.full(shape, NONE, np.uint8) if array is None else np.asarray(array)
+        if array.shape != shape or array.dtype != np.uint8:
+            raise ValueError(f"pair reply tables are uint8 [count, 2, 82, 81]: expected {list(shape)}, got {array.dtype} {array.shape}")
+        super().__init__(array, shape)
+        self.count = count
+
+    @classmethod
+    def empty(cls, count=1):
+        return cls(count)
+
+    def copy(self):
+        return ReplyTables2(self.count, self.array)
+
+    def occupancy(self):
+        """int64 [count]: the number of entries of each table, over all planes, that hold a point."""
+        return (self.array <= 80).sum((1, 2, 3)).astype(np.int64)
+
+    def pairs_occupancy(self):
+        """int64 [count]: the entries of planes 0..80 of each table that hold a point."""
+        return (self.array[:, :, :81] <= 80).sum((1, 2, 3)).astype(np.int64)
+
+    def table(self, i):
+        return ReplyTable2(self.array[int(i)])
+
+    def singles(self):
+        return ReplyTables(self.count, self.array[:, :, 81])
+
+    def __getstate__(self):
+        return {"count": self.count, "array": self.array.copy()}
+
+    def __setstate__(self, state):
+        self.__init__(state["count"], state["array"])
+
+
 def _host_array(table):
     return table.array if isinstance(table, ReplyTable) else np.asarray(table)
 
 
 def slots_of(table, slots, n, what="record"):
-    """The one check of slots: for n rows (records) of many tables -- a ReplyTables or an array [count,2,81] -- an int array
-    [n] -> int64 [n]; with a single table (a ReplyTable or an array [2,81]) or none at all, slots must be None -> None.  It
-    looks at the kind of `table` only, never at its entries: a table that lives on a device stays there."""
-    many = isinstance(table, ReplyTables) or (table is not None and not isinstance(table, ReplyTable) and np.ndim(table) == 3)
+    """The one check of slots: for n rows (records) of many tables -- a ReplyTables or an array [count,2,81], a ReplyTables2
+    or an array [count,2,82,81] -- an int array [n] -> int64 [n]; with a single table (a ReplyTable, a ReplyTable2 or an
+    array [2,81]) or none at all, slots must be None -> None.  It looks at the kind of `table` only, never at its entries:
+    a table that lives on a device stays there."""
+    many = isinstance(table, (ReplyTables, ReplyTables2)) or (
+        table is not None and not isinstance(table, ReplyTable) and np.ndim(table) in (3, 4))
     if not many:
         if slots is not None:
             raise TypeError("slots name the table of every record among many reply tables: not with a single table or without one")
@@ -256,23 +308,36 @@ def reply_update_host(table, recs, moves, won, records, playouts, slots=None):
     return n_set, n_cleared, n_nothing
 
 
-def reply2_moves(table, recs, prev2, playable):
+def _tables2_and_slots(t, slots, n, what):
+    """_tables_and_slots for pair tables: a single table [2,82,81] read as [1,2,82,81] (a view) with every slot 0
+    -> (tables [count,2,82,81], slots int64 [n])."""
+    if t.ndim == 3:
+        if slots is not None:
+            raise TypeError("slots name the table of every record among many reply tables: not with a single table or without one")
+        return t[None], np.zeros(n, np.int64)
+    return t, slots_of(t, slots, n, what)
+
+
+def reply2_moves(table, recs, prev2, playable, slots=None):
     """The use rule of a pair table for rows: table a ReplyTable2 (or uint8 [2,82,81]), recs uint8 [R,192], prev2 int [R]
     the move played two plies ago in each row's playout (anything outside 0..80 where there is none or it was a pass),
     playable bool [R,81] -> (move int64 [R], which int64 [R]): the reply the table makes the side to move play, or -1 where
     it decides nothing, and which lookup decided -- 2 the pair entry, 1 the single entry (plane 81), 0 neither.  Entries and
-    moves are compared before they index."""
-    t = _host_array(table)
+    moves are compared before they index.  With tables [count,2,82,81] (a ReplyTables2), slots [R] names each row's table;
+    a slot outside 0..count-1 is compared before it indexes, and such a row has no reply."""
+    t, slots = _tables2_and_slots(_host_array(table), slots, len(recs), "row")
     playable = np.asarray(playable)
     rows = np.arange(len(recs))
     p1 = L.record_last_move(recs).astype(np.int64)
     p2 = np.asarray(prev2).astype(np.int64)
     c = (L.record_turns(recs) & 1).astype(np.int64)
-    asks = (p1 >= 0) & (p1 <= 80)
+    has = (slots >= 0) & (slots < len(t))
+    of = np.where(has, slots, 0)
+    asks = has & (p1 >= 0) & (p1 <= 80)
     pair = asks & (p2 >= 0) & (p2 <= 80)
     at = np.where(asks, p1, 0)
-    r2 = np.where(pair, t[c, np.where(pair, p2, 81), at], NONE).astype(np.int64)
-    r1 = np.where(asks, t[c, 81, at], NONE).astype(np.int64)
+    r2 = np.where(pair, t[of, c, np.where(pair, p2, 81), at], NONE).astype(np.int64)
+    r1 = np.where(asks, t[of, c, 81, at], NONE).astype(np.int64)
     ok2 = (r2 <= 80) & playable[rows, np.minimum(r2, 80)]
     ok1 = (r1 <= 80) & playable[rows, np.minimum(r1, 80)]
     return np.where(ok2, r2, np.where(ok1, r1, -1)), np.where(ok2, 2, np.where(ok1, 1, 0))
@@ -299,28 +364,33 @@ def reply2_plies_of(table, recs, moves, playouts):
     return int(by_pair.sum()), int(by_single.sum())
 
 
-def reply2_update_host(table, recs, moves, won, records, playouts):
+def reply2_update_host(table, recs, moves, won, records, playouts, slots=None):
     """bkt_reply2_update on the host, the sequential fold itself: table a ReplyTable2 (or a uint8 [2,82,81] array), updated
     in place; the other arguments as reply_update_host takes them.  Rows ascending, plies ascending up to the first entry
     <= MOVE_NONE: with c the mover's colour, p1 the move before (the record's last move at t = 0), p2 the move before that
     (the record's last move at t = 1, none at t = 0) and m = moves[row, t] -- when m and p1 are board points, the fold of
     reply_update_host is applied to table[c, 81, p1] and, when p2 is a board point, to table[c, p2, p1].
+    With tables [count,2,82,81] (a ReplyTables2), slots [records] names each record's table: table i is folded with the
+    records whose slot is i, in ascending order; a record whose slot is outside 0..count-1 updates nothing.
     -> (set, cleared, nothing): the entries touched that were stored, that were cleared, and that stayed."""
-    t = _host_array(table)
+    tables = _host_array(table)
     records, playouts = int(records), int(playouts)
     recs, moves, won = np.asarray(recs), np.asarray(moves), np.asarray(won).reshape(-1) != 0
     if records < 1 or playouts < 1 or moves.ndim != 2 or len(moves) != records * playouts or len(won) != len(moves) \
             or recs.shape != (records, L.POS_BYTES):
         raise ValueError(f"recs must be [{records}, {L.POS_BYTES}], moves [{records} * {playouts}, max_plies] and won "
                          f"[{records} * {playouts}]")
-    if t.shape != (2, 82, 81) or t.dtype != np.uint8:
-        raise ValueError("a pair reply table is uint8 [2, 82, 81]")
+    if tables.shape[-3:] != (2, 82, 81) or tables.ndim not in (3, 4) or tables.dtype != np.uint8:
+        raise ValueError("a pair reply table is uint8 [2, 82, 81], pair reply tables uint8 [count, 2, 82, 81]")
+    tables, slots = _tables2_and_slots(tables, slots, records, "record")
     lm0 = L.record_last_move(recs).astype(np.int64)
     c0 = (L.record_turns(recs) & 1).astype(np.int64)
     counts = [0, 0, 0]
     for row in range(len(moves)):
         r = row // playouts
-        p1, p2, win = int(lm0[r]), None, bool(won[row])
+        if not 0 <= slots[r] < len(tables):
+            continue
+        t, p1, p2, win = tables[slots[r]], int(lm0[r]), None, bool(won[row])
         for k, m in enumerate(moves[row].tolist()):
             if m <= MOVE_NONE:
                 break

@@ -68,7 +68,8 @@ it where it is playable (bkt_reply_playouts), and after the score one bkt_reply_
 batch and takes the losers' out.  playout_value, playout_amaf and random_playouts update the table they are given in place;
 PlayoutEvaluator(replies=True) keeps one across the requests of a search (opt-in, untuned).  A ReplyTable2 in its place keys
 the replies by the last two moves, with that table as its plane 81 and fallback (bkt_reply2_playouts, bkt_reply2_update;
-DESIGN 26); PlayoutEvaluator(replies=2) keeps one.
+DESIGN 26); PlayoutEvaluator(replies=2) keeps one.  A ReplyTables2 with slots= is a pair table per game of a batch
+(bkt_reply2_playouts_tables, bkt_reply2_update_tables); PlayoutEvaluator(pair_games=G) keeps G of them.
 
     python -m bokego_amd.rollout --sgf FILE [--move K] --random --replies [-n 256] [--chunk 16]   # the share of plies the table decided
     python -m bokego_amd.rollout --sgf FILE [--move K] --random --reply-pairs [-n 256] [--chunk 16]   # the same with a ReplyTable2:
@@ -90,7 +91,7 @@ from . import _trainlib as T
 from . import go
 from . import lockstep as L
 from .lockstep import record_turns  # noqa: F401  (public here: see __all__)
-from .replies import (ReplyTable, ReplyTable2, ReplyTables, reply2_moves, reply2_plies_of, reply2_update_host, reply_moves, reply_plies_of,
+from .replies import (ReplyTable, ReplyTable2, ReplyTables, ReplyTables2, reply2_moves, reply2_plies_of, reply2_update_host, reply_moves, reply_plies_of,
                       reply_update_host, slots_of)
 
 MAX_PLIES = 400            # default cap of finish_games: 2.8x the longest playout measured (142 plies)
@@ -99,7 +100,7 @@ MOVE_NONE = -2             # BKT_MOVE_NONE; in the history: the game was over be
 SEKI_THRESHOLD = 0.5       # |mean ownership| of a stone's point below this: the stone is in seki (rollout_score)
 POS_BYTES = L.POS_BYTES
 
-__all__ = ["MAX_PLIES", "MOVE_NONE", "Amaf", "Finished", "Ownership", "PlayoutEvaluator", "ReplyTable", "ReplyTable2", "ReplyTables", "RolloutScore",
+__all__ = ["MAX_PLIES", "MOVE_NONE", "Amaf", "Finished", "Ownership", "PlayoutEvaluator", "ReplyTable", "ReplyTable2", "ReplyTables", "ReplyTables2", "RolloutScore",
            "amaf_counts_host", "reply_update_host", "reply2_update_host", "reply_pairs_report",
            "amaf_counts_sides_host", "amaf_prior",
            "default_counters", "finish_games", "format_score", "move_weights", "move_weights_host", "owner_board",
@@ -361,7 +362,8 @@ def _random_host(pos, key, ctr, max_plies, komi, history, table=None, tactics=No
     to a row's last move is playable it is the move, whatever the draw above says; the Finished then carries reply_plies,
     the number of plies the table decided.  slots: with tables [count,2,81] (a ReplyTables), the table of every row.
     With a ReplyTable2 the use rule is reply2_moves': the move two plies back is kept per row across the plies here (none at
-    ply 0, the record's last move at ply 1), and reply_pair_plies is the pair entries' share of reply_plies."""
+    ply 0, the record's last move at ply 1), and reply_pair_plies is the pair entries' share of reply_plies; with a
+    ReplyTables2 likewise, slots naming the pair table of every row."""
     def choose(k, recs, live, ok, x0):
         n = ok.sum(1)
         pick = np.argmax(np.cumsum(ok, 1) > select_index(x0, n).astype(np.int64)[:, None], 1)
@@ -385,12 +387,12 @@ def _random_host(pos, key, ctr, max_plies, komi, history, table=None, tactics=No
     if replies is None:
         return _playout_host(pos, key, ctr, max_plies, komi, choose, "selected", history)
     decided, draw = [0, 0], choose
-    pairs = isinstance(replies, ReplyTable2)
+    pairs = isinstance(replies, _PAIRS)
     prev2 = np.full(len(pos), MOVE_NONE, np.int64)                        # per row: the move two plies back, none yet
 
     def choose(k, recs, live, ok, x0):                                    # noqa: F811  (the draw, overruled by the table)
         if pairs:
-            r, which = reply2_moves(replies, recs[live], prev2[live], ok)
+            r, which = reply2_moves(replies, recs[live], prev2[live], ok, None if slots is None else np.asarray(slots)[live])
             prev2[live] = L.record_last_move(recs[live])                  # every live row plays a move or passes now
             decided[1] += int((which == 2).sum())
         else:
@@ -438,7 +440,8 @@ def random_playouts(pos, seed, counters=None, max_plies=MAX_PLIES, rules="device
     game a record of its own (bkt_reply_update).  The history is written whatever `history` says; black wins a
     game whose score is > 0.  The games then depend on the table too.
     slots: with a ReplyTables (a table per game of a batch), an int array [G], the table of every game: required
-    with a ReplyTables and refused with a ReplyTable."""
+    with a ReplyTables and refused with a ReplyTable.  A ReplyTables2 takes them likewise (a pair table per game),
+    and a ReplyTable2 refuses them."""
     L.check_rules(rules)
     table, tactics = _table(patterns), _tactics(tactics)
     slots = _check_replies(replies, slots, len(pos))
@@ -476,17 +479,21 @@ def random_playouts(pos, seed, counters=None, max_plies=MAX_PLIES, rules="device
 
 
 def _update_host(replies, recs, moves, won, records, playouts, slots):
-    """The fold of the table's kind on the host: reply2_update_host for a ReplyTable2 (slots is then None)."""
-    if isinstance(replies, ReplyTable2):
-        return reply2_update_host(replies, recs, moves, won, records, playouts)
+    """The fold of the table's kind on the host: reply2_update_host for a ReplyTable2 (slots is then None) or a ReplyTables2."""
+    if isinstance(replies, _PAIRS):
+        return reply2_update_host(replies, recs, moves, won, records, playouts, slots)
     return reply_update_host(replies, recs, moves, won, records, playouts, slots)
 
 
 def _update_device(recs, moves, won, records, playouts, replies, slots):
-    """The same on the device, on the current stream: bkt_reply2_update for a ReplyTable2, else bkt_reply_update(_tables)."""
-    if isinstance(replies, ReplyTable2):
-        return T.reply2_update(recs, moves, won, records, playouts, replies.device(recs.device))
+    """The same on the device, on the current stream: bkt_reply2_update(_tables) for a ReplyTable2 or a ReplyTables2, else
+    bkt_reply_update(_tables)."""
+    if isinstance(replies, _PAIRS):
+        return T.reply2_update(recs, moves, won, records, playouts, replies.device(recs.device), slots=slots)
     return T.reply_update(recs, moves, won, records, playouts, replies.device(recs.device), slots=slots)
+
+
+_PAIRS = (ReplyTable2, ReplyTables2)                                      # the tables keyed by the last two moves
 
 
 def _check_replies(replies, slots=None, records=None):
@@ -514,12 +521,12 @@ def _per_batch(call, *rows):
 
 def _play_random_device(pos, key, ctr, max_plies, history, table=None, tactics=None, replies=None, slots=None):
     """pos uint8 [G,192] and ctr int32 [G,4] on the device; pos is played on in place; table: None or a PatternTable;
-    tactics: None or a TacticTable; replies: None or a ReplyTable, which every launch reads as it stands, or a ReplyTables with
-    slots int32 [G] on the device, the table of every row.
+    tactics: None or a TacticTable; replies: None or a ReplyTable, which every launch reads as it stands, or a ReplyTables or
+    a ReplyTables2 with slots int32 [G] on the device, the table of every row.
     -> (over uint8 [G], plies int32 [G], moves int16 [G,max_plies] or None, status int32 [G]), T.MAX_BATCH rows per launch."""
     w, tac = (None if t is None else t.device(pos.device) for t in (table, tactics))
     if replies is not None:
-        play = T.reply2_playouts if isinstance(replies, ReplyTable2) else T.reply_playouts
+        play = T.reply2_playouts if isinstance(replies, _PAIRS) else T.reply_playouts
         tables = (w, tac, replies.device(pos.device))
     elif tactics is not None:
         play, tables = T.tactical_playouts, (w, tac)
@@ -577,7 +584,9 @@ def _playouts(recs, n, key, rules, komi=L.KOMI, table=None, tactics=None, max_pl
                                     table of every record, repeated per playout for the launch
                                     (bkt_reply_playouts_tables, bkt_reply_update_tables).  With a ReplyTable2
                                      the launches are bkt_reply2_playouts and bkt_reply2_update, slots is
-                                    refused, and reply_pair_plies is the pair entries' share of reply_plies (host rules)."""
+                                    refused, and reply_pair_plies is the pair entries' share of reply_plies (host rules).
+                                    With a ReplyTables2 slots is required again, and the launches are
+                                    bkt_reply2_playouts_tables and bkt_reply2_update_tables."""
     R, host = len(recs), rules == "host"
     counted, owned = (R if x is True else int(x) for x in (counted, owned))
     slots = _check_replies(replies, slots, R)
@@ -949,8 +958,11 @@ class PlayoutEvaluator:
     bkt_reply_playouts_tables and one bkt_reply_update_tables serve all games of a request.  `wants_games` says
     which of the two an instance is.
     replies=2: `.replies` is a ReplyTable2, replies keyed by the last two moves with the single-move table as its
-    plane 81 (bkt_reply2_playouts, bkt_reply2_update; the same stream order, the same determinism).  Pair tables per game do
-    not exist: replies=2 with games= is a TypeError.
+    plane 81 (bkt_reply2_playouts, bkt_reply2_update; the same stream order, the same determinism).  replies=2 with games= is
+    a TypeError: pair tables per game are the next keyword.
+    pair_games=G (default None: exactly the above; without replies= and games=, TypeError with either): `.replies` is a
+    ReplyTables2(G), a pair table per game, and submit takes games= as with games=G; one bkt_reply2_playouts_tables and one
+    bkt_reply2_update_tables serve all games of a request.  A one-game pool is then replies=2 bit for bit.
     The engine is kept as `policy_engine`, not `engine`: selfplay.run_pools_native hands an evaluator's `engine` to the C
     step loop as its own bk_evaluator, which would compute no playouts -- this class goes through callback_evaluator."""
     wants_positions = True
@@ -958,17 +970,21 @@ class PlayoutEvaluator:
 
     def __init__(self, engine, playouts=64, seed=0, rules="device", komi=L.KOMI, patterns=None, tactics=None, prior=0.0,
                  prior_k=PRIOR_K, prior_temperature=PRIOR_TEMPERATURE, rave=False, criticality=0.0, pattern_prior=0.0,
-                 prior_patterns=None, prior_tactics=None, replies=False, games=None):
+                 prior_patterns=None, prior_tactics=None, replies=False, games=None, pair_games=None):
         L.check_rules(rules)
+        if pair_games is not None and (replies or games is not None):
+            raise TypeError("pair_games= is the number of pair reply tables, a ReplyTables2: it goes without replies= and games=")
         if games is not None and not replies:
             raise TypeError("games= is the number of reply tables: it needs replies=True")
         if replies == 2 and not isinstance(replies, bool):
             if games is not None:
-                raise TypeError("pair reply tables per game do not exist: replies=2 goes without games= (replies=True takes it)")
+                raise TypeError("replies=2 goes without games= (replies=True takes it): pair reply tables per game are pair_games=G")
             self.replies = ReplyTable2.empty()
+        elif pair_games is not None:
+            self.replies = ReplyTables2(pair_games)
         else:
             self.replies = (ReplyTable.empty() if games is None else ReplyTables(games)) if replies else None
-        if games is not None:
+        if games is not None or pair_games is not None:
             self.wants_games = True
         self.rave = bool(rave)
         self.criticality = _not_negative(criticality, "criticality")
@@ -1004,7 +1020,7 @@ class PlayoutEvaluator:
         if self.wants_games and games is None:
             raise TypeError("this evaluator keeps a reply table per game: submit needs games=, the table of every row")
         if not self.wants_games and games is not None:
-            raise TypeError("games= names reply tables: this evaluator keeps none per game (replies=True, games=G)")
+            raise TypeError("games= names reply tables: this evaluator keeps none per game (replies=True, games=G, or pair_games=G)")
         self.positions += len(recs)
         self.batches += 1
         ticket = None
@@ -1023,7 +1039,7 @@ class PlayoutEvaluator:
         return SimpleNamespace(ticket=ticket, run=run, n_policy=counted, weights=weights, recs=recs[:counted])
 
     def reset_replies(self):
-        """An empty reply table again (replies=True; every table with games=G): what a new game starts with."""
+        """An empty reply table again (replies=True; every table with games=G or pair_games=G): what a new game starts with."""
         if self.replies is None:
             raise TypeError("this evaluator keeps no reply table: replies=True")
         self.replies.clear()

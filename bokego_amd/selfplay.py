@@ -694,8 +694,8 @@ def self_play(evaluator, n_games=512, rollouts=400, rank=0, world=1, seed_base=2
     value together, under virtual loss).  Not the reference's search -- other trees, other games, no parity claim --
     but still a pure function of the seeds: the games do not depend on sharding, pools, threads or batch grouping.  Default 1: off.
     rave: k > 0 = RAVE in every pool (GamePool.set_rave(k); it needs an evaluator whose finish returns the AMAF records,
-    PlayoutEvaluator(rave=True)).  An evaluator with wants_games (PlayoutEvaluator(replies=True, games=G)) gives every game
-    a reply table of its own, slot = the game's place among this rank's games; the tables are cleared first and G must cover
+    PlayoutEvaluator(rave=True)).  An evaluator with wants_games (PlayoutEvaluator(replies=True, games=G), or
+    PlayoutEvaluator(pair_games=G) for tables keyed by the last two moves) gives every game a reply table of its own, slot = the game's place among this rank's games; the tables are cleared first and G must cover
     the rank's games.  Either one needs the Python step loop (native_loop=True is a ValueError), and per-game tables need
     de-duplication off (dedup=True is a ValueError: equal records of different games no longer have equal values).  A game
     stays a pure function of seed_base + gid: its table sees only its own requests, in its own row order."""
@@ -751,7 +751,7 @@ def self_play(evaluator, n_games=512, rollouts=400, rank=0, world=1, seed_base=2
     if per_game:
         if evaluator.replies.count < len(gids):
             raise ValueError(f"the evaluator keeps {evaluator.replies.count} reply tables, this rank plays {len(gids)} games: "
-                             "PlayoutEvaluator(games=) must cover them")
+                             "PlayoutEvaluator(games=) or (pair_games=) must cover them")
         evaluator.reset_replies()
     pools = [GamePool([seed_base + g for g in part], prm, cap=cap, threads=threads) for part in parts]
     if rave > 0.0:
@@ -916,16 +916,22 @@ def parse_args(argv=None):
     ap.add_argument("--replay-shard", metavar="RANK/WORLD", default=None,
                     help="re-play the games a failed rank owned (e.g. 3/8: the gids with gid %% 8 == 3) in this process")
     PlayoutOptions.add_arguments(ap, rave=False, replies=False)       # --playout-value N: not with --value or --host-encode
-    # the pools' own forms of the two options left out above: RAVE records per game, and a reply table per game
+    # the pools' own forms of the options left out above: RAVE records per game, and a reply table per game, or
+    # a pair reply table per game
     ap.add_argument("--game-rave", type=float, nargs="?", const=4.0, default=0.0, metavar="K",
                     help="with --playout-value and --playout-prior: RAVE in every game's search, equivalence parameter K (4 when "
                          "no value is given, as --playout-rave of gtp and match); the step loop runs in Python")
     ap.add_argument("--game-replies", action="store_true",
                     help="with --playout-value: every game's playouts learn a last-good-reply table of their own, all games of a "
                          "batch in one launch; the step loop runs in Python, without de-duplication")
+    ap.add_argument("--game-reply-pairs", action="store_true",
+                    help="with --playout-value: as --game-replies with every game's replies keyed by the last two moves as well, "
+                         "the single-move table being the fallback (LGRF-2 per game); with or without --game-replies, since "
+                         "pairs contain singles")
     args = ap.parse_args(argv)
     args.playout = PlayoutOptions.from_args(ap, args)
-    for flag, on in (("--game-rave", args.game_rave != 0.0), ("--game-replies", args.game_replies)):
+    for flag, on in (("--game-rave", args.game_rave != 0.0), ("--game-replies", args.game_replies),
+                     ("--game-reply-pairs", args.game_reply_pairs)):
         if on and not args.playout_value:
             ap.error(f"{flag} goes with the playouts of --playout-value: it needs --playout-value")
     if not 0.0 <= args.game_rave < float("inf"):
@@ -939,6 +945,14 @@ def parse_args(argv=None):
     if args.playout_prior == 1.0 and args.policy is not None:
         ap.error("--playout-prior 1 searches without a policy net: not allowed with --policy")
     return args
+
+
+def game_table_keywords(args, games):
+    """The PlayoutEvaluator keywords of --game-replies and --game-reply-pairs for `games` games of this rank: pairs contain
+    singles, so with both flags the tables are the pair tables."""
+    if args.game_reply_pairs:
+        return dict(pair_games=games)
+    return dict(replies=True, games=games) if args.game_replies else {}
 
 
 def main(argv=None):
@@ -979,10 +993,10 @@ def main(argv=None):
             eng = LeafEngine(load(args.policy, "policy_19.bkw"), None, device_id=local_rank, max_batch=args.max_batch,
                              precision=args.precision)
         more = dict(rave=True) if args.game_rave else {}
-        if args.game_replies:
+        if args.game_replies or args.game_reply_pairs:
             here = len(shard_game_ids(args.games, *(int(v) for v in args.replay_shard.split("/")))) if args.replay_shard \
                 else len(shard_game_ids(args.games, rank, world))
-            more.update(replies=True, games=max(1, here))
+            more.update(game_table_keywords(args, max(1, here)))
         ev = PlayoutEvaluator(eng, **args.playout.evaluator_keywords(), **more)
     else:
         eng = LeafEngine(load(args.policy, "policy_19.bkw"), load(args.value, "value_synth.bkw"), device_id=local_rank,

@@ -425,6 +425,34 @@ size_t bkt_reply2_scratch_bytes(void);
 int bkt_reply2_update(const void *pos, const int16_t *moves, int max_plies, const uint8_t *won, int records, int playouts,
                       uint8_t *replies2, void *scratch, void *stream);
 
+/* Many pair tables at once (a pair table per game of a self-play batch).  The use rule and the update rule are
+ * the two above; new is only which table a row uses.  replies2 is uint8 [tables][2][82][81] on the device, 4-byte aligned
+ * (13284 is a multiple of 4, so every table is; a misaligned pointer is BKT_ERR_ARG), and slots, int32 on the device, has
+ * the meaning it has for bkt_reply_playouts_tables: slots[i] is the table of row i of bkt_reply2_playouts_tables (batch
+ * entries) and of record i of bkt_reply2_update_tables (records entries).  A slot outside 0..tables-1 is compared before
+ * it indexes anything: such a row plays as if its table were all 255, and such a record updates no table.
+ * 1 <= tables <= BKT_MAX_REPLY2_TABLES.
+ * bkt_reply2_playouts_tables: one launch.  Plane 81 of a row's table is staged in LDS as bkt_reply_playouts_tables stages a
+ * single table; the pair planes stay in global memory, and a thread reads its row's one pair byte per ply.  With tables = 1
+ * and every slot 0 it is bkt_reply2_playouts byte for byte; with planes 0..80 of every table all 255 it is
+ * bkt_reply_playouts_tables on the plane-81s byte for byte.
+ * bkt_reply2_update_tables: table t becomes what bkt_reply2_update makes of it with the records whose slot is t, in
+ * ascending record order; a table that no record names keeps every byte, whatever it is; plane 81 of every table ends as
+ * bkt_reply_update_tables leaves it from the same start.  bkt_reply2_update's four launches with the entry index offset by
+ * slot * 13284: integers only, and the result does not depend on the scheduling.
+ * scratch: bkt_reply2_tables_scratch_bytes(tables) = tables * 119556 bytes on the device, 8-byte aligned (0 when tables is
+ * outside 1..BKT_MAX_REPLY2_TABLES); its contents on entry do not matter.
+ * replies2 == NULL or misaligned, slots == NULL, a misaligned scratch or tables out of range returns BKT_ERR_ARG; the other
+ * argument checks are those of bkt_reply2_playouts and bkt_reply2_update.  A refused call launches nothing and writes
+ * nothing. */
+#define BKT_MAX_REPLY2_TABLES 4096
+int bkt_reply2_playouts_tables(void *pos, int batch, uint64_t seed, const uint32_t *counters, const uint16_t *table,
+                               const uint16_t *tactics, const uint8_t *replies2, int tables, const int32_t *slots,
+                               int max_plies, uint8_t *over, int32_t *plies, int16_t *moves, int32_t *status, void *stream);
+size_t bkt_reply2_tables_scratch_bytes(int tables);
+int bkt_reply2_update_tables(const void *pos, const int16_t *moves, int max_plies, const uint8_t *won, int records,
+                             int playouts, uint8_t *replies2, int tables, const int32_t *slots, void *scratch, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
