@@ -737,8 +737,22 @@ struct Game {
         if (!prm.leaves_visit_only) n.V += (double)sign;     // (visit only: the waiting rollout counts as a visit, not as a loss)
         n.avg = n.N > 0 ? n.V / (double)n.N : 0.0;
     }
+    // The most rows one more rollout of a step can add to the request: what its expansion asks for -- the node's policy row and
+    // every child (eager), or the policy row alone / the eager_top best children (priors unknown / known) -- and what its leaf asks
+    // for (request_leaf: its value and its eager_top - 1 next-best siblings).
+    int rollout_rows() const {
+        const int expansion = prm.eager_top > 0 ? prm.eager_top : prm.eager ? 1 + 81 : 1;
+        return expansion + (prm.use_value ? std::max(1, prm.eager_top) : 0);
+    }
     bool search_leaves() {  // true: a request goes out (n_pend rollouts wait for it); false: this move's rollouts are done
+        const int worst = rollout_rows();
         while (remaining > n_pend) {
+            // The step stops gathering while its request still fits a collect: `leaves` rollouts may bring leaves x 82 rows, and a
+            // request beyond row_cap would be skipped by every collect (the game stalled and the drivers took the empty
+            // batch for the end of the generation).  A step's first rollout always goes: alone it asks for at most 82 rows (no
+            // virtual loss is out, so a node that is expanded has been backed up and has its value) <= cap.  The rule reads the
+            // game's own request and row_cap, nothing of the batch: games stay a pure function of seed, nets, parameters and cap.
+            if ((n_pend > 0 || has_request()) && !room_for_rows(worst)) break;
             path.clear();
             int id = root;
             path.push_back(id);
@@ -1027,16 +1041,50 @@ void bk_search_params_default(bk_search_params* p) {
     p->leaves_visit_only = 0;
 }
 
-bk_pool* bk_pool_create(int n_games, const bk_search_params* prm, const uint64_t* seeds, int threads) {
-    if (n_games <= 0 || !prm || !seeds) return nullptr;
-    bk_pool* p = new bk_pool();
-    p->games.reserve(n_games);
-    bk_search_params q = *prm;
+}  // extern "C"
+
+namespace {
+// The one validator of a game's search parameters: bk_pool_create plays with what it leaves, bk_pool_set_speculation changes
+// parameters through it, and restore_game takes a snapshot only if its parameters are what it leaves -- so a pool never plays
+// with parameters whose snapshots would be refused (leaves = 100, eager = 2, no value net without playouts -- every
+// backup is then 0, a search by priors and visit counts, which both sides now take).
+// Switches are brought to 0 / 1, combinations the search does not cover fall back (bk_search_params says which), `leaves` is
+// clamped to kMaxLeaves and eager_top to 81; anything else out of range is refused.  -1: refused; 0: in range and unchanged; 1: in range, changed.
+constexpr int kMaxLeaves = 64;
+int settle_params(bk_search_params& q) {
+    auto in = [](long v, long lo, long hi) { return v >= lo && v <= hi; };
+    auto fin = [](double v, double lo, double hi) { return v >= lo && v <= hi; };          // (false for a NaN)
+    // what the step loop divides by, indexes with or sizes requests from must be in range
+    if (!in(q.rollouts, 0, 1 << 24) || !in(q.expand_thresh, 0, 1 << 30) || !fin(q.c_puct, 0.0, 1e6) || !fin(q.noise_weight, 0.0, 1.0) ||
+        !in(q.sample_plies, 0, 1 << 20) || !in(q.max_turns, 0, 100000) || !fin(q.komi, -1000.0, 1000.0) || !in(q.speculate, 0, 1 << 30) ||
+        !in(q.speculate_rows, 0, 1 << 30) || !in(q.request_tasks, 0, 1 << 30) || !in(q.eager_top, 0, 1 << 30) || !in(q.branch_num, 0, 81) ||
+        !fin(q.value_weight, 0.0, 1.0))
+        return -1;
+    for (int v : q.request_steps)
+        if (!in(v, 0, 1 << 30)) return -1;
+    const bk_search_params was = q;
+    for (int32_t* sw : {&q.eager, &q.record_visits, &q.prune, &q.simulate, &q.use_value, &q.leaves_visit_only}) *sw = *sw != 0;
+    if (q.eager_top > 81) q.eager_top = 81;                      // (a node has at most 81 children: "all of them, best first")
     if (!q.use_value) q.eager = q.eager_top = 0;                 // no value net (mcts.py:68-69): nothing asks for a value
     if (!q.use_value || q.simulate) q.speculate = 0;             // (a playout's nodes must stay the newest ones of the tree)
-    if (q.leaves < 1 || !q.use_value || q.simulate || (q.branch_num > 0 && q.branch_num < 81)) q.leaves = 1;   // (bk_search_params.leaves)
+    // (bk_search_params.leaves; value_weight: virtual_loss() keeps avg = V / N, the backup's scale with weight 1 only)
+    if (q.leaves < 1 || !q.use_value || q.simulate || (q.branch_num > 0 && q.branch_num < 81) || q.value_weight != 1.0) q.leaves = 1;
+    if (q.leaves > kMaxLeaves) q.leaves = kMaxLeaves;
     if (q.leaves > 1) q.speculate = 0;
-    q.leaves_visit_only = q.leaves_visit_only != 0;
+    return q.eager != was.eager || q.record_visits != was.record_visits || q.prune != was.prune || q.simulate != was.simulate ||
+           q.use_value != was.use_value || q.leaves_visit_only != was.leaves_visit_only || q.eager_top != was.eager_top ||
+           q.speculate != was.speculate || q.leaves != was.leaves;
+}
+}  // namespace
+
+extern "C" {
+
+bk_pool* bk_pool_create(int n_games, const bk_search_params* prm, const uint64_t* seeds, int threads) {
+    if (n_games <= 0 || !prm || !seeds) return nullptr;
+    bk_search_params q = *prm;
+    if (settle_params(q) < 0) return nullptr;
+    bk_pool* p = new bk_pool();
+    p->games.reserve(n_games);
     for (int i = 0; i < n_games; ++i) p->games.emplace_back(q, seeds[i]);
     p->threads = threads > 0 ? threads : 1;
     return p;
@@ -1289,7 +1337,19 @@ void run_lanes(bk_pool* p, int n, GameOf game_of, Fn fn) {
 
 // advance every game to its next evaluation request and lay the batch out:
 // [policy nodes of every game ...][value nodes of every game ...]; games whose request does not fit under
-// `cap` keep it for the next collect.  emit(node position, row) writes one row of the batch.
+// `cap` keep it for the next collect (every request fits an empty batch: collect_refusal, search_leaves).  emit(node position,
+// row) writes one row of the batch.
+// What both collects look at before they touch anything: the arguments, and that every request now waiting can travel under this
+// `cap`.  A request is made to fit row_cap, the smallest cap so far; one made under a larger cap and left waiting (the batch's task
+// limit) may exceed a smaller one -- skipping it for ever would leave its game unfinished behind a batch of 0 rows, which every
+// driver reads as the end.  The pool is left as it was: a collect with a cap that is large enough carries on.
+int collect_refusal(const bk_pool* p, const void* out, int cap, const int* n_policy) {
+    if (!p || !out || !n_policy || cap < 82) return BK_POOL_ERR_ARG;
+    for (const auto& gm : p->games)
+        if (gm.req_policy.size() + gm.req_value.size() > (size_t)cap) return BK_POOL_ERR_OVERSIZE;
+    return 0;
+}
+
 template <typename Emit>
 int collect_impl(bk_pool* p, int cap, int* n_policy, Emit emit) {
     const int G = (int)p->games.size();
@@ -1339,6 +1399,7 @@ int collect_impl(bk_pool* p, int cap, int* n_policy, Emit emit) {
     }
     if (first_left >= 0) p->first = first_left;
     const int A = (int)p->active.size();
+    if (A == 0 && first_left >= 0) return BK_POOL_ERR_OVERSIZE;   // (games are waiting and none fits: never an empty batch)
     auto emit_game = [&](int a) {
         Game& gm = p->games[p->active[a]];
         for (size_t i = 0; i < gm.req_policy.size(); ++i) emit(&gm.poses[gm.req_policy[i]], (size_t)(p->pol_off[a] + i));
@@ -1357,6 +1418,7 @@ int collect_impl(bk_pool* p, int cap, int* n_policy, Emit emit) {
 extern "C" {
 
 int bk_pool_collect(bk_pool* p, uint8_t* feats, int cap, int* n_policy) {
+    if (const int rc = collect_refusal(p, feats, cap, n_policy)) return rc;
     return collect_impl(p, cap, n_policy, [feats](bk_pos* pos, size_t row) { bk_pos_features_u8(pos, feats + row * 2187, 0); });
 }
 
@@ -1467,6 +1529,7 @@ int collect_dedup(bk_pool* p, bk_pos* out, int cap, int* n_policy) {
         gm.n_requests += 1;
     }
     if (first_left >= 0) p->first = first_left;
+    if (p->active.empty() && first_left >= 0) return BK_POOL_ERR_OVERSIZE;   // (as in collect_impl)
     const int npol = (int)p->uniq_pol.size(), nval = (int)p->uniq_val.size();
     if (npol) std::memcpy(out, p->uniq_pol.data(), (size_t)npol * sizeof(bk_pos));
     if (nval) std::memcpy(out + npol, p->uniq_val.data(), (size_t)nval * sizeof(bk_pos));
@@ -1489,6 +1552,7 @@ void bk_pool_dedup_rows(const bk_pool* p, uint64_t* requested, uint64_t* sent) {
 }
 
 int bk_pool_collect_pos(bk_pool* p, bk_pos* out, int cap, int* n_policy) {
+    if (const int rc = collect_refusal(p, out, cap, n_policy)) return rc;
     if (p->dedup) return collect_dedup(p, out, cap, n_policy);
     // the history-dependent half of nnet.features() -- the lazy liberty-cache refresh, go.py:220-243 -- runs
     // here, on the node itself (its children inherit the refreshed cache, as with bk_pool_collect); the
@@ -1720,10 +1784,12 @@ void bk_pool_set_task_cap(bk_pool* p, int tasks) { p->task_cap = tasks > 0 ? tas
 
 void bk_pool_set_speculation(bk_pool* p, int speculate, int rows, int request_tasks) {   // see bk_search_params
     for (auto& g : p->games) {
-        g.prm.speculate = speculate;
-        g.prm.speculate_rows = p->row_cap > 0 ? std::min(rows, p->row_cap) : rows;
-        g.prm.request_tasks = request_tasks;
-        g.prm.request_steps[0] = request_tasks;   // the later steps stay as created
+        bk_search_params q = g.prm;
+        q.speculate = speculate;
+        q.speculate_rows = p->row_cap > 0 ? std::min(rows, p->row_cap) : rows;
+        q.request_tasks = request_tasks;
+        q.request_steps[0] = request_tasks;   // the later steps stay as created
+        if (settle_params(q) >= 0) g.prm = q;     // (the modes without evaluation ahead -- playouts, several leaves -- stay without; a value out of range changes nothing)
     }
 }
 
@@ -2058,20 +2124,11 @@ bool restore_game(Game& dst, const uint8_t* buf, size_t len) {
     if (gm.state < S_INIT || gm.state > S_IDLE || gm.remaining < 0) return false;
     // the search parameters and the request limit travel with the game: what the step loop divides by, indexes with or sizes
     // requests from must be in range (a patched row_cap of -5 or a wild branch_num was taken as it came)
+    // A game was made with settled parameters (bk_pool_create) and keeps them: what settle_params would refuse or still change
+    // -- a switch that is not 0 / 1, leaves beyond its bound or in a mode without it -- is not a snapshot of a game.
     {
-        const bk_search_params& q = gm.prm;
-        auto in = [](long v, long lo, long hi) { return v >= lo && v <= hi; };
-        auto fin = [](double v, double lo, double hi) { return v >= lo && v <= hi; };          // (false for a NaN)
-        if (!in(q.rollouts, 0, 1 << 24) || !in(q.expand_thresh, 0, 1 << 30) || !fin(q.c_puct, 0.0, 1e6) || !fin(q.noise_weight, 0.0, 1.0) ||
-            !in(q.sample_plies, 0, 1 << 20) || !in(q.max_turns, 0, 100000) || !in(q.eager, 0, 1) || !fin(q.komi, -1000.0, 1000.0) ||
-            !in(q.record_visits, 0, 1) || !in(q.prune, 0, 1) || !in(q.speculate, 0, 1 << 30) || !in(q.speculate_rows, 0, 1 << 30) ||
-            !in(q.request_tasks, 0, 1 << 30) || !in(q.eager_top, 0, 81) || !in(q.branch_num, 0, 81) || !in(q.simulate, 0, 1) ||
-            !in(q.use_value, 0, 1) || !fin(q.value_weight, 0.0, 1.0) || !in(q.leaves, 1, 64) || !in(q.leaves_visit_only, 0, 1))
-            return false;
-        if (q.leaves > 1 && (q.simulate || !q.use_value || (q.branch_num > 0 && q.branch_num < 81) || q.speculate)) return false;   // (bk_pool_create's rule)
-        for (int v : q.request_steps)
-            if (!in(v, 0, 1 << 30)) return false;
-        if (!q.use_value && !q.simulate) return false;                       // (bk_search_params: no value net needs simulate)
+        bk_search_params q = gm.prm;
+        if (settle_params(q) != 0) return false;
         if (gm.row_cap < 1) return false;
     }
     if (n == 0 ? gm.root != -1 : !node_ok(gm.root)) return false;
@@ -2242,6 +2299,7 @@ int bk_pools_run(bk_pool* const* pools, int n_pools, const bk_evaluator* ev, int
             if (l.ticket && (rc = finish(i))) break;
             if (l.live) {
                 l.n = bk_pool_collect_pos(pools[i], l.recs.data(), cap, &l.npol);
+                if (l.n < 0) { rc = l.n; l.n = 0; break; }         // (BK_POOL_ERR_OVERSIZE: a request no collect of this cap can take)
                 if (l.n == 0) { l.live = false; continue; }
                 // never more than BK_POOLS_MAX_INFLIGHT requests out (the engine's evaluator has BK_MAX_INFLIGHT = 4 tickets): with
                 // more pools than that the oldest request -- the next lane in turn that has one -- is taken in first

@@ -68,6 +68,17 @@ class RunInfo(ctypes.Structure):
                 ("seconds", ctypes.c_double), ("wait_seconds", ctypes.c_double)]
 
 
+POOL_ERR_ARG, POOL_ERR_OVERSIZE = -1, -82      # BK_POOL_ERR_ARG, BK_POOL_ERR_OVERSIZE (include/bokego_tree.h)
+
+
+def _collect_error(rc, cap, what="collect"):
+    """A collect's (or the C step loop's) negative return as an exception: 0 rows mean "every game is over" and nothing else."""
+    if rc == POOL_ERR_OVERSIZE:
+        return RuntimeError(f"{what}: a game's waiting request exceeds cap={cap} (BK_POOL_ERR_OVERSIZE): it was made under a "
+                            "larger cap; the pool is unchanged and unfinished")
+    return RuntimeError(f"{what} failed ({rc}): bad arguments (cap={cap}; a cap is at least 82)")
+
+
 _VP = ctypes.c_void_p
 TREE_SYMBOLS = {
     "bk_search_params_default": (None, [ctypes.POINTER(SearchParams)]),
@@ -230,11 +241,14 @@ class GamePool:
         return a.value, b.value
 
     def collect(self):
-        """-> (uint8 feats [B,27,9,9] view, n_policy); B == 0 when every game is finished."""
+        """-> (uint8 feats [B,27,9,9] view, n_policy); B == 0 when every game is finished, and only then: RuntimeError when a
+        waiting request exceeds the pool's cap (BK_POOL_ERR_OVERSIZE)."""
         if self._feats is None:
             self._feats = np.empty((self.cap, 27, 9, 9), np.uint8)
         npol = ctypes.c_int(0)
         B = self._lib.bk_pool_collect(self._h, self._feats.ctypes.data, self.cap, ctypes.byref(npol))
+        if B < 0:
+            raise _collect_error(B, self.cap, "bk_pool_collect")
         return self._feats[:B], npol.value
 
     def collect_positions(self):
@@ -244,6 +258,8 @@ class GamePool:
             self._recs = np.empty((self.cap, 192), np.uint8)
         npol = ctypes.c_int(0)
         B = self._lib.bk_pool_collect_pos(self._h, self._recs.ctypes.data, self.cap, ctypes.byref(npol))
+        if B < 0:
+            raise _collect_error(B, self.cap, "bk_pool_collect_pos")
         return self._recs[:B], npol.value
 
     def deliver(self, probs, values, records=None):
@@ -456,6 +472,8 @@ def run_pools_native(pools, evaluator, cap=None):
     err = getattr(ev, "_state", {}).get("error")
     if err is not None:
         raise err
+    if rc == POOL_ERR_OVERSIZE:
+        raise _collect_error(rc, cap, "bk_pools_run")
     if rc:
         msg = eng._lib.bk_last_error(eng._h).decode() if eng is not None else ""
         raise RuntimeError(f"bk_pools_run failed ({rc}) {msg}")
@@ -795,6 +813,11 @@ def self_play(evaluator, n_games=512, rollouts=400, rank=0, world=1, seed_base=2
     else:
         steps = run_pools(pools, evaluator, progress)
     dt = time.perf_counter() - t0
+    # a step loop that came back has played every game to its end, or the statistics below would count games that never were
+    # (four games of 0 moves used to reduce to "games: 4, white_wins: 4, plies: 0")
+    unfinished = [g for part, pool in zip(parts, pools) for i, g in enumerate(part) if not pool.info(i)["done"]]
+    if unfinished:
+        raise RuntimeError(f"self_play: the step loop returned with unfinished games {unfinished}")
     games, visits = {}, {}
     for part, pool in zip(parts, pools):
         for i, g in enumerate(part):

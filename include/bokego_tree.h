@@ -8,6 +8,7 @@
  *
  *   for (;;) {
  *       B = bk_pool_collect_pos(pool, recs, cap, &n_policy); // every game runs until it needs a network
+ *       if (B < 0) fail(B);                                  // BK_POOL_ERR_*: not an end
  *       if (B == 0) break;                                   // all games finished
  *       t = bk_submit_positions(engine, recs, B, n_policy, PROBS|VALUE, NULL, probs, values);   // planes made on the GPU
  *       bk_wait(engine, t);
@@ -83,7 +84,8 @@ typedef struct bk_search_params {
                               raises there; see tests/golden/simulate_playouts.json).  Playout positions outside the tree are
                               evaluated (policy) and forgotten.  Turns evaluation ahead (speculate) off.  0: off            */
     int32_t use_value;     /* 0: there is no value net (MCTS(value_net=None), mcts.py:68-69): no value is ever asked for, V stays
-                              0; rows that carry one anyway are ignored.  Needs simulate.  1: default                       */
+                              0; rows that carry one anyway are ignored.  Meant for simulate (without it every backup is 0: a
+                              search by priors and visit counts alone).  1: default                                          */
     double value_weight;   /* MCTS kwarg value_net_weight (mcts.py:65-72): a child's average reward in the selection is
                               ((1 - w) Q + w V) / N.  1.0 without simulation (the reference forces it), else default 0.5, 0
                               without a value net                                                                            */
@@ -95,11 +97,20 @@ typedef struct bk_search_params {
                               are back the losses are taken off and the rollouts are backed up in the order they were made.
                               Rollouts whose leaf value is already known are backed up at once, as ever.  A request then carries
                               ~`leaves` times the rows -- a 64-game pool asks for a full round of workgroups instead of a
-                              third of one -- and a move needs ~1 / leaves of the round trips.  Deterministic per game (the
-                              games still do not depend on sharding, threads or batch grouping), every rollout is backed up
-                              exactly once (the visit totals of a search are those of `leaves` = 1), but the tree it builds is
-                              another one: rollouts descend on statistics that are up to leaves - 1 backups behind.
-                              Ignored (= 1) with simulate, branch_num or without a value net; turns speculate off.
+                              third of one -- and a move needs ~1 / leaves of the round trips.  At most 64: a larger value is
+                              taken as 64.  A step stops gathering while its request still fits one collect: before another
+                              rollout it asks whether the most rows that rollout can add (an expansion's policy row and
+                              children, the leaf's value and siblings) still fit the smallest `cap` the pool has collected
+                              with, and sends what it has if not; a step's first rollout always goes (<= 82 rows <= cap).
+                              Deterministic per game: with leaves > 1 a game is a pure function of its seed, the networks, the
+                              parameters AND THE SMALLEST `cap` ITS POOL HAS COLLECTED WITH -- not of sharding, pools, threads
+                              or what else travels in a batch; a cap no request reaches (leaves x the rows of a rollout)
+                              changes nothing.  Every rollout is backed up exactly once (the visit totals of a search are
+                              those of `leaves` = 1), but the tree it builds is another one: rollouts descend on statistics
+                              that are up to leaves - 1 backups behind.
+                              Ignored (= 1) with simulate, branch_num, without a value net, or with value_weight != 1 (the
+                              virtual loss is on the scale of V / N, which is the backup's scale with weight 1 only); turns
+                              speculate off.
                               Measured against the one-leaf search (100 games, profiles/r06_leaves_probe.txt): 8 leaves lose
                               34 : 66 at 400 rollouts per move and win 61 : 39 at 1600; see leaves_visit_only.                  */
     int32_t leaves_visit_only; /* multi-leaf mode: 1 = a waiting rollout leaves a virtual VISIT on its path (N + 1) instead of a virtual loss
@@ -122,13 +133,30 @@ typedef struct bk_game_info {
 typedef struct bk_pool bk_pool;
 
 void bk_search_params_default(bk_search_params *p);
-/* seeds[i] drives game i's noise / move sampling: results do not depend on how games are grouped */
+/* seeds[i] drives game i's noise / move sampling: results do not depend on how games are grouped.
+ * The parameters go through the validator that bk_pool_restore applies to a snapshot's, so a pool never plays with parameters
+ * its own snapshots would be refused for: the switches (eager, record_visits, prune, simulate, use_value, leaves_visit_only)
+ * are taken as 0 / != 0, modes fall back as bk_search_params says (no value net: no eager values; playouts or no value net: no
+ * speculate; leaves), leaves > 64 is 64 and eager_top > 81 is 81; NULL is returned for anything else out of range -- rollouts
+ * 0..2^24, expand_thresh, speculate, speculate_rows, request_tasks, request_steps 0..2^30, c_puct 0..1e6, noise_weight and
+ * value_weight 0..1, sample_plies 0..2^20, max_turns 0..100000, |komi| <= 1000, eager_top >= 0, branch_num 0..81, not a NaN. */
 bk_pool *bk_pool_create(int n_games, const bk_search_params *prm, const uint64_t *seeds, int threads);
 void bk_pool_destroy(bk_pool *p);
 
 /* Advance every unfinished game until it needs network outputs; write the requested positions'
  * feature planes (uint8 [B][27][9][9]) to feats: first the n_policy positions that need policy
- * (+value), then the value-only ones.  Returns B (0 when every game is over).  cap >= 82. */
+ * (+value), then the value-only ones.  A game whose request does not fit behind the others' keeps it for the next collect.
+ * Returns (both flavours):
+ *   B > 0                  rows written, B <= cap
+ *   0                      every game is over (bk_pool_n_done == bk_pool_n_games) -- and nothing else: a game that waits is never
+ *                          left out of an empty batch
+ *   BK_POOL_ERR_ARG        a NULL argument, or cap < 82 (one game's plain request: a policy row and 81 children)
+ *   BK_POOL_ERR_OVERSIZE   a waiting request alone has more rows than cap.  Requests are made to fit the smallest cap the pool has
+ *                          collected with, so this takes a request made under a larger cap and left waiting (bk_pool_set_task_cap)
+ *                          when a smaller cap comes.
+ * On an error nothing has been advanced or written and the pool is as it was: a collect with a large enough cap carries on. */
+#define BK_POOL_ERR_ARG (-1)
+#define BK_POOL_ERR_OVERSIZE (-82)
 int bk_pool_collect(bk_pool *p, uint8_t *feats, int cap, int *n_policy);
 /* Same batch, as 192-byte position records instead of planes: each requested node's liberty cache is
  * refreshed in place (the history-dependent half of nnet.features(), go.py:220-243) and the record copied
@@ -306,8 +334,9 @@ int bk_pool_restore(bk_pool *p, int g, const void *buf, long len);
  * the value only) and returns a ticket > 0 (or a negative error); probs[n_policy][81] (softmax outputs, not yet re-normalised)
  * and values[B] must be filled in when wait(ticket) returns 0.  bk_engine_evaluator() (include/bokego_amd.h) fills one in for
  * a HIP engine: bk_submit_positions / bk_wait.
- * Returns 0, -1 for bad arguments, or the evaluator's error code (outstanding tickets are waited for first; the pools are
- * then in the middle of a step and cannot be driven on).
+ * Returns 0, -1 for bad arguments (cap < 82 among them), a collect's error (BK_POOL_ERR_OVERSIZE: some games are then unfinished),
+ * or the evaluator's error code; outstanding tickets are waited for first.  After an evaluator's error the pools are in the
+ * middle of a step and cannot be driven on.
  */
 #define BK_POOLS_MAX_INFLIGHT 4 /* bk_pools_run keeps at most this many requests out at once (= the engine's BK_MAX_INFLIGHT) */
 typedef struct bk_evaluator {

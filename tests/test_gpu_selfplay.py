@@ -344,3 +344,31 @@ def test_the_opt_in_multi_leaf_mode_on_the_engine(engine, generation):
         halves.update(loc["games"])
     assert halves == base["games"]
     assert all(sum(ply.values()) >= 399 for plies in base["visits"].values() for ply in plies)
+
+
+@pytest.mark.parametrize("expand_thresh", [100, 4])
+@pytest.mark.parametrize("precision", ["f32", "f16x2"])
+def test_multi_leaf_at_a_binding_cap_on_the_engine(engine, precision, expand_thresh):
+    """tests/test_request_cap_cpu.py's contract on the real evaluator's path (position records, in-batch de-duplication, the engine's
+    tickets): 16 leaves, every child evaluated, cap=128 -- the configuration in which one game's request used to outgrow every collect,
+    the step loops took the empty batch for the end and four games of 0 moves were reduced as four white wins.  Six games with the step
+    loop in C and in Python: the same games and visit records, every game played to the end (max_turns = 12: 13 moves, or two passes),
+    and totals that say six games and the sum of their plies.  expand_thresh 100 is self_play's default (64 rollouts per move hardly
+    expand below the root); 4 makes every step gather expansions until the cap stops it.  No new kernel runs."""
+    kw = dict(n_games=6, rollouts=64, max_turns=12, leaves=16, eager_top=0, cap=128, n_pools=2, record_visits=1, expand_thresh=expand_thresh)
+    engine.set_precision(precision)
+    try:
+        (nat, t_nat), (py, t_py) = (selfplay.self_play(selfplay.EngineEvaluator(engine), native_loop=nl, **kw) for nl in (True, False))
+    finally:
+        engine.set_precision("f32")
+    assert nat["native_loop"] and not py["native_loop"] and nat["leaves"] == 16
+    assert nat["games"] == py["games"] and nat["visits"] == py["visits"]
+    assert sorted(nat["games"]) == list(range(6))
+    for g, rec in nat["games"].items():
+        mv = rec["moves"]
+        assert len(mv) == 13 or (len(mv) >= 2 and mv[-1] == go.PASS and mv[-2] == go.PASS), (g, mv)
+        assert len(nat["visits"][g]) == len(mv) and all(sum(ply.values()) >= 64 - 1 for ply in nat["visits"][g]), g
+    plies = sum(len(rec["moves"]) for rec in nat["games"].values())
+    for tot in (t_nat, t_py):
+        assert tot["games"] == 6 and tot["plies"] == plies and tot["black_wins"] + tot["white_wins"] == 6 and tot["n_root_values"] == plies
+    assert t_nat == t_py

@@ -19,7 +19,7 @@ static bool step(bk_pool* pool, long& steps, long& rows) {
     thread_local std::vector<float> probs((size_t)CAP * 81), values(CAP);
     int npol = 0;
     const int n = bk_pool_collect_pos(pool, recs.data(), CAP, &npol);
-    if (n == 0) return false;
+    if (n <= 0) return false;                       // (0: every game is over; < 0: BK_POOL_ERR_*)
     for (int r = 0; r < npol; ++r) {
         const unsigned char* b = reinterpret_cast<const unsigned char*>(&recs[r]);
         float sum = 0;

@@ -25,7 +25,7 @@ static double generation(int G, int threads, int seed0) {
     for (;;) {
         int npol = 0;
         const int n = bk_pool_collect_pos(p, recs.data(), CAP, &npol);
-        if (!n) break;
+        if (n <= 0) break;                          // (0: every game is over; < 0: BK_POOL_ERR_*)
         for (int r = 0; r < npol; ++r) {
             const unsigned char* b = (const unsigned char*)&recs[r];
             float sum = 0;
