@@ -64,6 +64,7 @@ SYMBOLS = {
     "bkt_reply2_playouts_tables": (_I, [_P, _I, _U64, _P, _P, _P, _P, _I, _P, _I, _P, _P, _P, _P, _P]),
     "bkt_reply2_tables_scratch_bytes": (_Z, [_I]),
     "bkt_reply2_update_tables": (_I, [_P, _P, _I, _P, _I, _I, _P, _I, _P, _P, _P]),
+    "bkt_mm_sums": (_I, [_P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
 }
 MAX_BATCH = 65536          # BKT_MAX_BATCH
 PRECISIONS = ("fp32", "bf16")
@@ -74,6 +75,8 @@ PATTERN_ENTRIES = 131072   # BKT_PATTERN_ENTRIES
 TACTIC_ENTRIES = 64        # BKT_TACTIC_ENTRIES
 MAX_SAMPLE_ROWS = 1 << 24  # BKT_MAX_SAMPLE_ROWS
 REPLY_NONE = 255           # BKT_REPLY_NONE: a reply table's entry for "no reply"
+MM_MAX_ROWS = 16384        # BKT_MM_MAX_ROWS
+MM_G_MIN, MM_G_MAX = 1 << 8, 1 << 24   # BKT_MM_G_MIN, BKT_MM_G_MAX: the domain of a fixed-point strength, gamma = g / 65536
 
 _lib = None
 
@@ -655,3 +658,50 @@ def reply2_update(pos, moves, won, records, playouts, replies2, scratch=None, sl
                                  _dev(won, "won", (records * playouts,), torch.uint8), records, playouts, *tables,
                                  _dev(scratch, "scratch", dtype=torch.uint8), _stream(moves)), name)
     return replies2
+
+
+def mm_strengths(g, entries, name, device=None):
+    """A strength table as bkt_mm_sums takes it: g, integers [entries] (numpy or a tensor), each MM_G_MIN..MM_G_MAX -- else
+    ValueError, before any launch -> int32 [entries] (the bits of the uint32 words), on `device` when one is given."""
+    if hasattr(g, "astype") and g.dtype.kind in "iu":
+        g = g.astype("int64")                                           # numpy's unsigned types: torch has no arithmetic on them
+    t = g if isinstance(g, torch.Tensor) else torch.as_tensor(g)
+    if t.dim() != 1 or t.shape[0] != entries or t.dtype.is_floating_point or t.dtype == torch.bool:
+        raise ValueError(f"{name} must be integers [{entries}], got {t.dtype} {tuple(t.shape)}")
+    t = t.to(torch.int64)
+    if int(t.min()) < MM_G_MIN or int(t.max()) > MM_G_MAX:
+        raise ValueError(f"{name}: a strength is {MM_G_MIN}..{MM_G_MAX} (gamma = g / 65536 in [2^-8, 2^8]), got "
+                         f"{int(t.min())}..{int(t.max())}")
+    t = t.to(torch.int32)
+    return t if device is None else t.to(device)
+
+
+def mm_sums(codes, moves, gp, gt, den_p=None, den_t=None):
+    """One MM pass over packed positions (bkt_mm_sums; include/bokego_train.h has the definition): codes int32 [R,81] (the
+    bits of the uint32 words) and moves int32 [R] on the device, any R >= 1: one launch per MM_MAX_ROWS rows.  gp, gt: the
+    strengths, integers [PATTERN_ENTRIES] and [TACTIC_ENTRIES] on any device; a strength outside MM_G_MIN..MM_G_MAX is a
+    ValueError before any launch.  den_p, den_t: None (zeroed here) or int64 [PATTERN_ENTRIES] / [TACTIC_ENTRIES] on the
+    device of codes (the bits of the uint64 sums), added to.
+    -> (den_p, den_t, total int64 [R], chosen int64 [R], rank int32 [R])."""
+    if not isinstance(codes, torch.Tensor) or codes.dim() != 2 or codes.shape[1] != 81 or codes.shape[0] < 1:
+        raise ValueError("codes must be int32 [R, 81] with R >= 1")
+    R, dev = int(codes.shape[0]), codes.device
+    cp, mp = _dev(codes, "codes", dtype=torch.int32), _dev(moves, "moves", (R,), torch.int32)
+    if moves.device != dev:
+        raise ValueError("moves must be on the device of codes")
+    gp, gt = mm_strengths(gp, PATTERN_ENTRIES, "gp", dev), mm_strengths(gt, TACTIC_ENTRIES, "gt", dev)
+    den_p = torch.zeros((PATTERN_ENTRIES,), dtype=torch.int64, device=dev) if den_p is None else den_p
+    den_t = torch.zeros((TACTIC_ENTRIES,), dtype=torch.int64, device=dev) if den_t is None else den_t
+    if den_p.device != dev or den_t.device != dev:
+        raise ValueError("den_p and den_t must be on the device of codes")
+    dp, dt = _dev(den_p, "den_p", (PATTERN_ENTRIES,), torch.int64), _dev(den_t, "den_t", (TACTIC_ENTRIES,), torch.int64)
+    total = torch.empty((R,), dtype=torch.int64, device=dev)
+    chosen = torch.empty((R,), dtype=torch.int64, device=dev)
+    rank = torch.empty((R,), dtype=torch.int32, device=dev)
+    lib, stream = load(), _stream(codes)
+    for s in range(0, R, MM_MAX_ROWS):
+        n = min(MM_MAX_ROWS, R - s)
+        _check(lib.bkt_mm_sums(cp + s * 81 * 4, mp + s * 4, n, _dev(gp, "gp", dtype=torch.int32), _dev(gt, "gt", dtype=torch.int32),
+                               dp, dt, total.data_ptr() + s * 8, chosen.data_ptr() + s * 8, rank.data_ptr() + s * 4, stream),
+               "bkt_mm_sums")
+    return den_p, den_t, total, chosen, rank

@@ -21,7 +21,9 @@ whose inclusive prefix sum of weights exceeds t; a pass when P is empty.  No flo
 constant c selects rank floor(floor(u c n / 2^24) / c) = floor(u n / 2^24): random_playouts' own game.
 
 rollout.random_playouts, playout_value and PlayoutEvaluator take a table as patterns=; this module holds what they need
-and the fit.  No fitted table ships: `fit` makes one in about a second.
+and the fit.  No fitted table ships: `fit` makes one in about a second.  `fit` counts frequencies, played / seen, and
+knows nothing of the tactics table that multiplies its weights; mmfit.py fits both tables together as one
+model and writes this module's table format.
 """
 import argparse
 

@@ -26,7 +26,9 @@ A neutral table plays the pattern games, and without a pattern table the uniform
 The fit is one multiplicative-update step on top of the pattern table: weights = 256 * played / mass, where played[code]
 counts the moves played and mass[code] is the number of plays the pattern-only draw expects of that code on the same
 plies (each playable point adds P / the sum of P over the playable points).  Counting plain frequencies instead would count
-the shape information twice.  No fitted table ships.
+the shape information twice.  That step is the first of a minorization-maximization iteration and stops there, with the
+pattern table fixed; mmfit.py carries the iteration on over both tables and writes this module's table
+format.  No fitted table ships.
 """
 import argparse
 

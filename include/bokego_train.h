@@ -453,6 +453,40 @@ size_t bkt_reply2_tables_scratch_bytes(int tables);
 int bkt_reply2_update_tables(const void *pos, const int16_t *moves, int max_plies, const uint8_t *won, int records,
                              int playouts, uint8_t *replies2, int tables, const int32_t *slots, void *scratch, void *stream);
 
+/* One minorization-maximization (MM) pass over packed positions, in ONE launch: the sums a joint fit of the pattern and the
+ * tactics table needs (bokego_amd/mmfit.py, whose sums_host is the definition in numpy).  The move model is the
+ * playouts': a playable point j of a row has a pattern index i_j and a tactical code c_j and the strength gamma_p[i_j] *
+ * gamma_t[c_j]; the move is drawn in proportion to it.
+ *   codes  uint32 [rows, 81], one word per point: bits 0..16 bkt_pattern_codes' index, bits 17..22 bkt_tactical_codes'
+ *          code, bit 31 set when the point is in the playable set, every other bit zero (bits 23..30 are ignored);
+ *   moves  int32 [rows]: the move played from the row's position; below 0 (a pass, BKT_MOVE_NONE) or above 80: no point;
+ *   gp     uint32 [BKT_PATTERN_ENTRIES], gt uint32 [BKT_TACTIC_ENTRIES]: the strengths in fixed point, gamma = g / 65536.
+ *          Domain: 2^8 <= g <= 2^24 (gamma in [2^-8, 2^8]).  The caller guarantees it (the Python binding checks it); the
+ *          kernel assumes it.  Outside it no access goes out of bounds, but the sums below may wrap.
+ * Per row r, in unsigned 64-bit integers, over the playable points j of the row:
+ *   s_j = max(1, (gp[i_j] * gt[c_j]) >> 16);   total[r] = E_r = the sum of s_j (0 for a row with no playable point).
+ *   If moves[r] is a playable point m of the row: chosen[r] = s_m; rank[r] = the number of playable j with s_j > s_m, or
+ *   with s_j == s_m and j < m; and for EVERY playable j
+ *       den_p[i_j] += (gt[c_j] << 32) / E_r        den_t[c_j] += (gp[i_j] << 32) / E_r
+ *   (floor division, each candidate on its own).  Otherwise -- a pass, no move, a move on a point that is not playable,
+ *   such as an eye fill, a row with no playable point -- chosen[r] = 0, rank[r] = -1 and the row adds nothing; E_r = 0
+ *   never reaches a division.
+ * den_p uint64 [BKT_PATTERN_ENTRIES] and den_t uint64 [BKT_TACTIC_ENTRIES] are accumulated with +=: the caller zeroes them,
+ * and several calls add up.  total, chosen (uint64 [rows]) and rank (int32 [rows]) are written for every row.  Integer
+ * sums: the result does not depend on the scheduling, and the host mirror gives the same integers.
+ * No wrap.  In the domain gp * gt >= 2^16, so s_j is the floor of x = gp * gt / 2^16 >= 1 and x < 2 s_j.  One row adds to
+ * ALL of den_p, weighted by gp:  sum_j gp[i_j] * floor(gt[c_j] 2^32 / E_r) <= 2^48 * sum_j x_j / E_r < 2^49, so one row
+ * adds less than 2^49 / gp[i] <= 2^41 to any one den_p[i], and likewise to any den_t[c].  A call of BKT_MM_MAX_ROWS = 2^14
+ * rows stays below 2^55, and sums accumulated over fewer than 2^22 rows below 2^63.  Inside a row: s_j <= 2^32,
+ * E_r <= 81 * 2^32 < 2^39, and a dividend is at most 2^24 << 32 = 2^56.
+ * 1 <= rows <= BKT_MM_MAX_ROWS and no pointer but stream may be NULL; else BKT_ERR_ARG, nothing is launched and nothing
+ * written. */
+#define BKT_MM_MAX_ROWS 16384
+#define BKT_MM_G_MIN (1u << 8)
+#define BKT_MM_G_MAX (1u << 24)
+int bkt_mm_sums(const uint32_t *codes, const int32_t *moves, int rows, const uint32_t *gp, const uint32_t *gt,
+                uint64_t *den_p, uint64_t *den_t, uint64_t *total, uint64_t *chosen, int32_t *rank, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
