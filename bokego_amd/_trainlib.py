@@ -65,6 +65,7 @@ SYMBOLS = {
     "bkt_reply2_tables_scratch_bytes": (_Z, [_I]),
     "bkt_reply2_update_tables": (_I, [_P, _P, _I, _P, _I, _I, _P, _I, _P, _P, _P]),
     "bkt_mm_sums": (_I, [_P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "bkt_balance_sums": (_I, [_P, _I, _U64, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P]),
 }
 MAX_BATCH = 65536          # BKT_MAX_BATCH
 PRECISIONS = ("fp32", "bf16")
@@ -77,6 +78,9 @@ MAX_SAMPLE_ROWS = 1 << 24  # BKT_MAX_SAMPLE_ROWS
 REPLY_NONE = 255           # BKT_REPLY_NONE: a reply table's entry for "no reply"
 MM_MAX_ROWS = 16384        # BKT_MM_MAX_ROWS
 MM_G_MIN, MM_G_MAX = 1 << 8, 1 << 24   # BKT_MM_G_MIN, BKT_MM_G_MAX: the domain of a fixed-point strength, gamma = g / 65536
+BALANCE_Q = 24             # BKT_BALANCE_Q: a share of the draw is booked in units of 2^-24
+BALANCE_MAX_ROWS = 16384   # BKT_BALANCE_MAX_ROWS
+BALANCE_MAX_COEF = 4096    # BKT_BALANCE_MAX_COEF
 
 _lib = None
 
@@ -705,3 +709,67 @@ def mm_sums(codes, moves, gp, gt, den_p=None, den_t=None):
                                dp, dt, total.data_ptr() + s * 8, chosen.data_ptr() + s * 8, rank.data_ptr() + s * 4, stream),
                "bkt_mm_sums")
     return den_p, den_t, total, chosen, rank
+
+
+def balance_coef(coef, rows, device=None):
+    """A coefficient per row as bkt_balance_sums takes them: coef, integers [rows] (numpy or a tensor), each at most
+    BALANCE_MAX_COEF in magnitude -- else ValueError, before any launch -> int32 [rows], on `device` when one is given."""
+    t = coef if isinstance(coef, torch.Tensor) else torch.as_tensor(coef)
+    if t.dim() != 1 or t.shape[0] != rows or t.dtype.is_floating_point or t.dtype == torch.bool:
+        raise ValueError(f"coef must be integers [{rows}], got {t.dtype} {tuple(t.shape)}")
+    t = t.to(torch.int64)
+    if rows and (int(t.min()) < -BALANCE_MAX_COEF or int(t.max()) > BALANCE_MAX_COEF):
+        raise ValueError(f"coef: a coefficient is -{BALANCE_MAX_COEF}..{BALANCE_MAX_COEF} (the sums of a call then stay below "
+                         f"2^61), got {int(t.min())}..{int(t.max())}")
+    t = t.to(torch.int32).contiguous()
+    return t if device is None else t.to(device)
+
+
+def balance_sums(pos, seed, counters, table, tactics, coef, max_plies, over=None, history=True, grad_p=None, grad_t=None):
+    """The gradient sums of simulation balancing (bkt_balance_sums; include/bokego_train.h has the definition):
+    tactical_playouts -- pos, seed, counters, max_plies, over and history are its arguments, and the games its games -- with
+    either table optional (None: neutral), whose draw books coef[b] times every candidate's share of every draw of row b.
+    pos uint8 [B,192] with any B >= 1: one launch per BALANCE_MAX_ROWS rows.  coef: integers [B] on any device; a
+    coefficient beyond BALANCE_MAX_COEF in magnitude is a ValueError before any launch, as is every other argument out of
+    its domain.  grad_p, grad_t: None (zeroed here) or int64 [PATTERN_ENTRIES] / [TACTIC_ENTRIES] on the device of pos, added
+    to; the sums of one launch stay below 2^61, and B * max_plies * max|coef| * 2^25 -- what all the launches of this call can
+    add up to -- must stay below 2^63 (ValueError otherwise: split the rows); what the accumulators held before is the
+    caller's to bound.
+    -> (grad_p, grad_t, over uint8 [B], plies int32 [B], moves int16 [B,max_plies] or None, status int32 [B])."""
+    if not isinstance(pos, torch.Tensor) or pos.dim() != 2 or pos.shape[1] != POS_BYTES or pos.shape[0] < 1:
+        raise ValueError(f"pos must be [B, {POS_BYTES}] with B >= 1")
+    if coef is None:
+        raise ValueError("coef must be integers [B]")
+    B, dev, max_plies = int(pos.shape[0]), pos.device, int(max_plies)
+    if not 1 <= max_plies <= MAX_PLAYOUT_PLIES:
+        raise ValueError(f"max_plies must be 1..{MAX_PLAYOUT_PLIES}, got {max_plies}")
+    pp, cp = _dev(pos, "pos", dtype=torch.uint8), _dev(counters, "counters", (B, 4), torch.int32)
+    if counters.device != dev:
+        raise ValueError("counters must be on the device of pos")
+    tables = _weight_tables(pos, table, tactics)
+    coef = balance_coef(coef, B, dev)
+    top = int(coef.abs().max())
+    if B * max_plies * top * (2 << BALANCE_Q) >= 2 ** 63:               # every launch adds into the same accumulators
+        raise ValueError(f"{B} rows of {max_plies} plies with |coef| up to {top} could pass 2^63 in the accumulators: split the rows")
+    if over is not None and over.device != dev:
+        raise ValueError("over must be on the device of pos")
+    over_p = None if over is None else _dev(over, "over", (B,), torch.uint8)
+    for g, n, name in ((grad_p, PATTERN_ENTRIES, "grad_p"), (grad_t, TACTIC_ENTRIES, "grad_t")):
+        if g is not None and (_dev(g, name, (n,), torch.int64) == 0 or g.device != dev):
+            raise ValueError(f"{name} must be on the device of pos")
+    grad_p = torch.zeros((PATTERN_ENTRIES,), dtype=torch.int64, device=dev) if grad_p is None else grad_p
+    grad_t = torch.zeros((TACTIC_ENTRIES,), dtype=torch.int64, device=dev) if grad_t is None else grad_t
+    if over is None:
+        over = torch.zeros((B,), dtype=torch.uint8, device=dev)
+        over_p = over.data_ptr()
+    plies = torch.empty((B,), dtype=torch.int32, device=dev)
+    status = torch.empty((B,), dtype=torch.int32, device=dev)
+    moves = torch.empty((B, max_plies), dtype=torch.int16, device=dev) if history else None
+    lib, stream, key = load(), _stream(pos), seed_u64(seed)
+    for s in range(0, B, BALANCE_MAX_ROWS):
+        n = min(BALANCE_MAX_ROWS, B - s)
+        _check(lib.bkt_balance_sums(pp + s * POS_BYTES, n, key, cp + s * 16, *tables, coef.data_ptr() + s * 4, grad_p.data_ptr(),
+                                    grad_t.data_ptr(), max_plies, over_p + s, plies.data_ptr() + s * 4,
+                                    None if moves is None else moves.data_ptr() + s * max_plies * 2,
+                                    status.data_ptr() + s * 4, stream), "bkt_balance_sums")
+    return grad_p, grad_t, over, plies, moves, status

@@ -487,6 +487,40 @@ int bkt_reply2_update_tables(const void *pos, const int16_t *moves, int max_plie
 int bkt_mm_sums(const uint32_t *codes, const int32_t *moves, int rows, const uint32_t *gp, const uint32_t *gt,
                 uint64_t *den_p, uint64_t *den_t, uint64_t *total, uint64_t *chosen, int32_t *rank, void *stream);
 
+/* The gradient sums of simulation balancing, in ONE launch: bkt_tactical_playouts whose draw also books, at every ply of
+ * every playout, each candidate's share of the draw against its pattern index and its tactical code (bokego_amd/balance.py,
+ * whose sums_host is the definition in numpy).  pos, batch, seed, counters, max_plies, over, plies, moves and
+ * status are bkt_tactical_playouts'; table and tactics may each be NULL as in bkt_reply_playouts (a NULL pattern table is
+ * 256 everywhere, a NULL tactics table likewise).  The games are untouched: records, over, plies, moves and status come
+ * out byte for byte as bkt_tactical_playouts writes them for the same seed, counters and tables (with neither table, as
+ * bkt_random_playouts writes them).
+ *   coef    int32 [batch] on the device: one signed coefficient per row, |coef| <= BKT_BALANCE_MAX_COEF.  The caller
+ *           guarantees the range (the Python binding checks it); outside it nothing goes out of bounds, but the sums may
+ *           wrap.  A row whose coef is 0 books nothing.
+ *   grad_p  int64 [BKT_PATTERN_ENTRIES], grad_t int64 [BKT_TACTIC_ENTRIES] on the device, 8-byte aligned: accumulated with
+ *           +=; the caller zeroes them, and several calls add up.
+ * With Q = BKT_BALANCE_Q: for every row b and every ply at which the row is not over and the total S of the draw's weights
+ * is positive (a pass books nothing), with m the point the draw picks, every playable point j of weight w_j (the weight
+ * bkt_move_weights defines), pattern index i_j (bkt_pattern_codes') and tactical code c_j (bkt_tactical_codes') books
+ *       d_j = (j == m ? 2^Q : 0) - floor(w_j * 2^Q / S)
+ *       grad_p[i_j] += coef[b] * d_j        grad_t[c_j] += coef[b] * d_j
+ * d_j / 2^Q is the derivative of log(w_m / S) by the logarithm of either table entry of j, to within 2^-Q.  Integer sums
+ * mod 2^64 (a signed accumulator through unsigned adds): the result does not depend on the scheduling, and the host mirror
+ * gives the same integers.
+ * No wrap.  Within one ply of one row the floors sum to at most 2^Q (they are the floors of shares that sum to 1) and the
+ * picked point adds 2^Q once, so a ply changes any one entry by at most |coef| * 2^(Q+1) <= 2^12 * 2^25 = 2^37 in
+ * magnitude; a row of at most BKT_MAX_PLAYOUT_PLIES = 2^10 plies by at most 2^47; a call of BKT_BALANCE_MAX_ROWS = 2^14 rows
+ * by at most 2^61.  Sums over several calls belong in wider arithmetic than the accumulator (balance.py adds them up on the
+ * host).  Inside a ply: w_j < 2^24, so w_j * 2^Q < 2^48, and S < 2^31.
+ * 1 <= batch <= BKT_BALANCE_MAX_ROWS; coef, grad_p, grad_t and what bkt_tactical_playouts requires (but for the tables)
+ * must not be NULL; else BKT_ERR_ARG, nothing is launched and nothing written. */
+#define BKT_BALANCE_Q 24
+#define BKT_BALANCE_MAX_ROWS 16384
+#define BKT_BALANCE_MAX_COEF 4096
+int bkt_balance_sums(void *pos, int batch, uint64_t seed, const uint32_t *counters, const uint16_t *table,
+                     const uint16_t *tactics, const int32_t *coef, int64_t *grad_p, int64_t *grad_t, int max_plies,
+                     uint8_t *over, int32_t *plies, int16_t *moves, int32_t *status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
