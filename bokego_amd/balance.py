@@ -37,6 +37,7 @@ from . import _trainlib as T
 from . import lockstep as L
 from . import mmfit as MM
 from . import patterns as PT
+from . import replay as RP
 from . import rollout as RO
 from . import tactics as TC
 
@@ -126,7 +127,7 @@ def sums_host(recs, seed, counters, coef, patterns=None, tactics=None, max_plies
     if len(rows_of):
         fin = RO._playout_host(recs[rows_of], L.seed_u64(seed), ctr[rows_of], max_plies, L.KOMI, choose, "selected")
         records[rows_of], over_out[rows_of], plies[rows_of] = fin.records, fin.over, fin.plies
-        moves[rows_of, :fin.moves.shape[1]] = fin.moves
+        moves[rows_of, :fin.moves.shape[-1]] = fin.moves
     return Sums(grad_p, grad_t, records, over_out, plies, moves)
 
 
@@ -296,18 +297,14 @@ def labelled_positions(start_recs, moves, plies=(40,), komi=L.KOMI):
     uint8 [G,192] and moves [G,L] as patterns.counts takes them; the games are replayed on the host rules, a game gives
     its position before ply k for every k of `plies` it reaches, and its final record is scored by area (black wins a
     score > 0).  The label is noisy and unbiased for the games' own policy: DESIGN 18's and 28's yardstick."""
-    start, moves = PT._check_games(start_recs, moves)
+    start, moves = RP.check_games(start_recs, moves)
     want = sorted(set(int(k) for k in plies))
     if not want or want[0] < 0:
         raise ValueError("plies must name at least one ply, none negative")
-    recs, taken = start.copy(), []
-    for k in range(moves.shape[1]):
-        live = np.nonzero(moves[:, k] > MM.MOVE_NONE)[0]
-        if k in want and len(live):
+    recs, taken = start, []           # one batch: recs is the walker's array of all games, and holds the final records at the end
+    for k, _, live, recs, _, _ in RP.replay_host(start, moves, playable=False):
+        if k in want:
             taken.append((recs[live].copy(), live, np.full(len(live), k, np.int64)))
-        if len(live):
-            L.play_host(recs, live, moves[live, k].astype(np.int64), lambda g, m: f"game {g}: the recorded move {m} is illegal",
-                        liberties=True)
     if not taken:
         return np.zeros((0, L.POS_BYTES), np.uint8), np.zeros(0), np.zeros(0, np.int64), np.zeros(0, np.int64)
     black_won = L.area_score_host(recs, komi) > 0
@@ -384,16 +381,16 @@ def main(argv=None):
     torch.cuda.set_device(args.device)
     dev = torch.device("cuda", args.device)
     if args.command == "eval":
-        pos, tgt, _, _ = labelled_positions(*MM._policy_games(args.p, args.games, args.seed, dev), plies=args.plies)
+        pos, tgt, _, _ = labelled_positions(*RP.policy_games(args.p, args.games, args.seed, dev), plies=args.plies)
         r = value_error(pos, tgt, args.patterns, args.tactics, args.playouts, args.seed, device=dev)
         print(f"{r['positions']} positions at plies {args.plies}, N = {args.playouts}: mse {r['mse']:.4f}, sign agreement "
               f"{100 * r['agreement']:.1f} % (ties {100 * r['ties']:.1f} %)")
         return
     parts = []
     if args.games:
-        parts.append(labelled_positions(*MM._policy_games(args.p, args.games, args.seed, dev), plies=args.plies))
+        parts.append(labelled_positions(*RP.policy_games(args.p, args.games, args.seed, dev), plies=args.plies))
     if args.records:
-        parts.append(labelled_positions(*PT.record_games(args.records), plies=args.plies))
+        parts.append(labelled_positions(*RP.record_games(args.records), plies=args.plies))
     pos, tgt = np.concatenate([p[0] for p in parts]), np.concatenate([p[1] for p in parts])
     start = strengths_of_tables(args.start_patterns, args.start_tactics, args.scale)
     f = fit(pos, tgt, args.iterations, args.lr, args.playouts, args.samples, start, args.prior, seed=args.seed, scale=args.scale,

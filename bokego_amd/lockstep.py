@@ -192,6 +192,21 @@ def area_score_host(recs, komi):
     return np.array([lib.bk_pos_area_score(pos_ptr(recs[i]), komi) for i in range(len(recs))], np.float64)
 
 
+def playable_host(recs):
+    """bool [n,81]: bk_pos_is_legal(p, s) and bk_pos_possible_eye(p, s) != the colour to move (black on an even turn)."""
+    lib = go.golib()
+    out = np.zeros((len(recs), 81), bool)
+    buf = (ctypes.c_uint8 * 81)()
+    for i in range(len(recs)):
+        p = pos_ptr(recs[i])
+        lib.bk_pos_legal_moves(p, buf)
+        mover = 2 if p.contents.turn & 1 else 1
+        for s in range(81):
+            if buf[s] and lib.bk_pos_possible_eye(p, s) != mover:
+                out[i, s] = True
+    return out
+
+
 FEATURE_THREADS = 8        # bk_features_batch_u8 calls in flight per ply (ctypes releases the GIL during each)
 FEATURE_CHUNK = 512        # positions per call
 _POOL = None

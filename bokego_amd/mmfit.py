@@ -35,6 +35,8 @@ import torch
 from . import _trainlib as T
 from . import lockstep as L
 from . import patterns as PT
+from . import replay as RP
+from . import rollout as RO
 from . import tactics as TC
 
 G_ONE = 1 << 16                                    # gamma = 1
@@ -75,70 +77,35 @@ def pack(start_recs, moves, rules="device", device=None):
     tactics.counts do.  rules="device": bkt_playout_step, bkt_pattern_codes, bkt_tactical_codes and torch bit operations;
     rules="host": the mirror on the host rules, the same integers."""
     L.check_rules(rules)
-    start, moves = PT._check_games(start_recs, moves)
-    played = np.zeros(PT.ENTRIES, np.int64), np.zeros(TC.ENTRIES, np.int64)
+    start, moves = RP.check_games(start_recs, moves)
     parts = []
-    if rules == "device":
-        from . import rollout
-        dev = rollout._device(device, None, start_recs)
-    for s in range(0, len(start), T.MAX_BATCH):
-        if rules == "host":
-            parts += _pack_host(start[s:s + T.MAX_BATCH], moves[s:s + T.MAX_BATCH], played)
-        else:
-            parts += _pack_device(torch.from_numpy(start[s:s + T.MAX_BATCH]).to(dev),
-                                  torch.from_numpy(moves[s:s + T.MAX_BATCH]).to(dev), played)
     if rules == "host":
-        codes = np.concatenate([c for c, _ in parts]) if parts else np.zeros((0, 81), np.uint32)
-        mv = np.concatenate([m for _, m in parts]) if parts else np.zeros(0, np.int32)
-    else:
-        codes = torch.cat([c for c, _ in parts]) if parts else torch.zeros((0, 81), dtype=torch.int32, device=dev)
-        mv = torch.cat([m for _, m in parts]) if parts else torch.zeros((0,), dtype=torch.int32, device=dev)
-    return Packed(codes, mv, *played)
-
-
-def _pack_host(start, moves, played):
-    from . import rollout
-    recs, parts = start.copy(), []
-    for k in range(moves.shape[1]):
-        live = np.nonzero(moves[:, k] > MOVE_NONE)[0]
-        if len(live) == 0:
-            continue
-        mv = moves[live, k]
-        ok = rollout.playable_host(recs[live])
-        index, code = PT.codes_host(recs[live]), TC.codes_host(recs[live])
-        parts.append((pack_word(index, code, ok), mv.astype(np.int32)))
-        at, rows = np.clip(mv, 0, 80), np.arange(len(live))
-        good = (mv >= 0) & ok[rows, at]
-        played[0][:] += np.bincount(index[rows, at][good], minlength=PT.ENTRIES)
-        played[1][:] += np.bincount(code[rows, at][good], minlength=TC.ENTRIES)
-        L.play_host(recs, live, mv, lambda g, m: f"game {g}: the recorded move {m} is illegal", liberties=True)
-    return parts
-
-
-def _pack_device(pos, hist, played):
-    G, parts = len(pos), []
-    playable = torch.empty((G, 81), dtype=torch.uint8, device=pos.device)
-    none = torch.full((G,), MOVE_NONE, dtype=torch.int32, device=pos.device)
-    counts = (torch.zeros(PT.ENTRIES, dtype=torch.int64, device=pos.device),
-              torch.zeros(TC.ENTRIES, dtype=torch.int64, device=pos.device))
-    status = T.playout_step(pos, none, None, None, playable)             # the playable sets of the start records
-    for k in range(hist.shape[1]):
-        mv = hist[:, k].contiguous()
-        live = mv > MOVE_NONE
+        played = np.zeros(PT.ENTRIES, np.int64), np.zeros(TC.ENTRIES, np.int64)
+        for _, _, live, recs, mv, ok in RP.replay_host(start, moves, T.MAX_BATCH):
+            index, code = PT.codes_host(recs[live]), TC.codes_host(recs[live])
+            parts.append((pack_word(index, code, ok), mv))
+            at, good = RP.counted(mv, ok)
+            for p, codes in zip(played, (index, code)):
+                p += np.bincount(RP.at_move(codes, at)[good], minlength=len(p))
+        if parts:
+            return Packed(np.concatenate([c for c, _ in parts]), np.concatenate([m for _, m in parts]), *played)
+        return Packed(np.zeros((0, 81), np.uint32), np.zeros(0, np.int32), *played)
+    dev = RO._device(device, None, start_recs)
+    played = (torch.zeros(PT.ENTRIES, dtype=torch.int64, device=dev), torch.zeros(TC.ENTRIES, dtype=torch.int64, device=dev))
+    for _, _, pos, mv, live, playable in RP.replay_device(start, moves, dev):
         index, code = T.pattern_codes(pos), T.tactical_codes(pos)
         ok = playable != 0
         word = index | code << 17
         word = torch.where(ok, word | -(1 << 31), word)                  # bit 31 of the int32 that carries the uint32
         parts.append((word[live], mv[live]))
-        at = mv.clamp(0, 80).to(torch.int64)[:, None]
-        good = live & (mv >= 0) & ok.gather(1, at)[:, 0]
-        for c, codes in zip(counts, (index, code)):
-            c += torch.bincount(codes.gather(1, at)[:, 0][good].to(torch.int64), minlength=len(c))
-        status |= T.playout_step(pos, mv, None, None, playable)
-    L.check_status(status, lambda g, st: f"game {g}: a recorded move is illegal (status {st})")
-    for c, p in zip(counts, played):
-        p += c.cpu().numpy()
-    return parts
+        at, good = RP.counted(mv, ok)
+        good = live & good
+        for p, codes in zip(played, (index, code)):
+            p += torch.bincount(RP.at_move(codes, at)[good].to(torch.int64), minlength=len(p))
+    played = (p.cpu().numpy() for p in played)
+    if parts:
+        return Packed(torch.cat([c for c, _ in parts]), torch.cat([m for _, m in parts]), *played)
+    return Packed(torch.zeros((0, 81), dtype=torch.int32, device=dev), torch.zeros((0,), dtype=torch.int32, device=dev), *played)
 
 
 def host(data):
@@ -181,11 +148,10 @@ def sums_host(codes, moves, gp, gt):
     if codes.ndim != 2 or codes.shape[1] != 81 or codes.dtype != np.uint32 or moves.shape != (len(codes),):
         raise ValueError("sums_host takes codes uint32 [R,81] and moves [R]")
     gp, gt = _strengths(gp, PT.ENTRIES, "gp"), _strengths(gt, TC.ENTRIES, "gt")
-    R = len(codes)
+    n = len(codes)
     den_p, den_t = np.zeros(PT.ENTRIES, np.uint64), np.zeros(TC.ENTRIES, np.uint64)
-    total, chosen, rank = np.zeros(R, np.uint64), np.zeros(R, np.uint64), np.full(R, -1, np.int32)
-    point = np.arange(81)
-    for a in range(0, R, MAX_ROWS):
+    total, chosen, rank = np.zeros(n, np.uint64), np.zeros(n, np.uint64), np.full(n, -1, np.int32)
+    for a in range(0, n, MAX_ROWS):
         word, mv = codes[a:a + MAX_ROWS], moves[a:a + MAX_ROWS].astype(np.int64)
         ok = (word >> np.uint32(31)) != 0
         index = (word & np.uint32(PT.ENTRIES - 1)).astype(np.int64)
@@ -195,9 +161,8 @@ def sums_host(codes, moves, gp, gt):
         at, rows = np.clip(mv, 0, 80), np.arange(len(word))
         valid = (mv >= 0) & (mv <= 80) & ok[rows, at]
         s_m = np.where(valid, s[rows, at], np.uint64(0))
-        above = ok & ((s > s_m[:, None]) | ((s == s_m[:, None]) & (point[None, :] < mv[:, None])))
         total[a:a + MAX_ROWS], chosen[a:a + MAX_ROWS] = E, s_m
-        rank[a:a + MAX_ROWS] = np.where(valid, above.sum(1), -1)
+        rank[a:a + MAX_ROWS] = np.where(valid, RP.move_rank(s, s_m, mv, ok), -1)
         adds = ok & valid[:, None]
         Er = np.broadcast_to(np.maximum(E, np.uint64(1))[:, None], s.shape)[adds]   # E >= 1 on every row that adds
         _add_at(den_p, index[adds], (gt[code[adds]] << np.uint64(32)) // Er)
@@ -328,47 +293,39 @@ def tables(gp, gt, scale=64):
 
 # ---- the tables under the draw itself ---------------------------------------------------------------------------------------------
 def evaluate(start_recs, moves, patterns=None, tactics=None, rules="device", device=None, plies=None):
-    """How well a pair of TABLES predicts the recorded moves under the playouts' own draw -> dict(moves, mean_ll, top1,
+    """How well a pair of TABLES predicts the moves of the games under the playouts' own draw -> dict(moves, mean_ll, top1,
     top5).  The games are replayed in lock-step and every position's weights come from rollout.move_weights (the existing
     kernel or its host mirror), so pairs from any fit compare directly, and so does a pair before and after tables()
     rounded it.  patterns, tactics: as rollout.move_weights takes them (None: none; both None is the uniform draw).  A ply
     counts when its move is a playable point; plies: None for all, or the ply numbers to count."""
-    from . import rollout
     L.check_rules(rules)
-    start, moves = PT._check_games(start_recs, moves)
-    table, tac = rollout._table(patterns), rollout._tactics(tactics)
+    start, moves = RP.check_games(start_recs, moves)
+    table, tac = RO._table(patterns), RO._tactics(tactics)
     want = None if plies is None else set(int(k) for k in plies)
-    n, ll, top1, top5 = 0, 0.0, 0, 0
-    for s in range(0, len(start), T.MAX_BATCH):
-        recs, hist = start[s:s + T.MAX_BATCH].copy(), moves[s:s + T.MAX_BATCH]
-        if rules == "device":
-            dev = rollout._device(device, None, start_recs)
-            recs, hist_d, status = torch.from_numpy(recs).to(dev), torch.from_numpy(hist).to(dev), 0
-        for k in range(hist.shape[1]):
-            live = np.nonzero(hist[:, k] > MOVE_NONE)[0]
-            if len(live) == 0:
-                continue
-            mv = hist[live, k].astype(np.int64)
+    tally = dict(moves=0, ll=0.0, top1=0, top5=0)
+
+    def count(w, mv):
+        """The plies of one yield: w int64 [n,81] the weights of the draw before the moves mv [n]."""
+        at, good = RP.counted(mv, w > 0)
+        w_m = RP.at_move(w, at)
+        rank = RP.move_rank(w, w_m, mv, w > 0)[good]
+        tally["moves"] += int(good.sum())
+        tally["ll"] += float(np.sum(np.log(w_m[good].astype(np.float64)) - np.log(w[good].sum(1).astype(np.float64))))
+        tally["top1"] += int((rank < 1).sum())
+        tally["top5"] += int((rank < 5).sum())
+
+    if rules == "host":
+        for k, _, live, recs, mv, _ in RP.replay_host(start, moves, T.MAX_BATCH, playable=False):
             if want is None or k in want:
-                if rules == "device":
-                    w = rollout._move_weights_device(recs, table, tac).cpu().numpy()[live].astype(np.int64)
-                else:
-                    w = rollout.move_weights_host(recs[live], table, tac).astype(np.int64)
-                at, rows = np.clip(mv, 0, 80), np.arange(len(live))
-                w_m = np.where(mv >= 0, w[rows, at], 0)
-                good = w_m > 0
-                above = ((w > w_m[:, None]) | ((w == w_m[:, None]) & (np.arange(81)[None, :] < mv[:, None]))) & (w > 0)
-                rank = above.sum(1)[good]
-                n += int(good.sum())
-                ll += float(np.sum(np.log(w_m[good].astype(np.float64)) - np.log(w[good].sum(1).astype(np.float64))))
-                top1, top5 = top1 + int((rank < 1).sum()), top5 + int((rank < 5).sum())
-            if rules == "device":
-                status = status | T.playout_step(recs, hist_d[:, k].contiguous())
-            else:
-                L.play_host(recs, live, mv, lambda g, m: f"game {g}: the recorded move {m} is illegal", liberties=True)
-        if rules == "device":
-            L.check_status(status, lambda g, st: f"game {g}: a recorded move is illegal (status {st})")
-    return dict(moves=n, mean_ll=ll / max(n, 1), top1=top1 / max(n, 1), top5=top5 / max(n, 1))
+                count(RO.move_weights_host(recs[live], table, tac).astype(np.int64), mv.astype(np.int64))
+    else:
+        for k, first, pos, _, _, _ in RP.replay_device(start, moves, RO._device(device, None, start_recs), playable=False):
+            live = np.nonzero(moves[first:first + len(pos), k] > MOVE_NONE)[0]
+            if len(live) and (want is None or k in want):
+                count(RO._move_weights_device(pos, table, tac).cpu().numpy()[live].astype(np.int64),
+                      moves[first + live, k].astype(np.int64))
+    n = max(tally["moves"], 1)
+    return dict(moves=tally["moves"], mean_ll=tally["ll"] / n, top1=tally["top1"] / n, top5=tally["top5"] / n)
 
 
 # ---- the command line -----------------------------------------------------------------------------------------------------------
@@ -417,31 +374,19 @@ def parse_args(argv=None):
     return args
 
 
-def _policy_games(policy, games, seed, device):
-    from . import rollout
-    from .reinforce import policy_engine
-    from .train import load_weights
-    eng = policy_engine(load_weights(policy), device.index, min(games, 4096))
-    try:
-        start = L.initial_positions(games)
-        return start, rollout.finish_games(start, eng, seed, device=device).moves
-    finally:
-        eng.close()
-
-
 def main(argv=None):
     args = parse_args(argv)
     torch.cuda.set_device(args.device)
     dev = torch.device("cuda", args.device)
     if args.command == "eval":
-        r = evaluate(*_policy_games(args.p, args.games, args.seed, dev), args.patterns, args.tactics, device=dev)
+        r = evaluate(*RP.policy_games(args.p, args.games, args.seed, dev), args.patterns, args.tactics, device=dev)
         print(f"{r['moves']} moves: mean log-likelihood {r['mean_ll']:.4f}, top-1 {100 * r['top1']:.1f} %, top-5 {100 * r['top5']:.1f} %")
         return
     parts = []
     if args.games:
-        parts.append(pack(*_policy_games(args.p, args.games, args.seed, dev), device=dev))
+        parts.append(pack(*RP.policy_games(args.p, args.games, args.seed, dev), device=dev))
     if args.records:
-        parts.append(pack(*PT.record_games(args.records), device=dev))
+        parts.append(pack(*RP.record_games(args.records), device=dev))
     data = Packed(torch.cat([p.codes for p in parts]), torch.cat([p.moves for p in parts]),
                   sum(p.played_p for p in parts), sum(p.played_t for p in parts))
     f = fit(data, args.iterations, args.prior)

@@ -33,11 +33,13 @@ import torch
 from . import _trainlib as T
 from . import go
 from . import lockstep as L
+from . import replay as RP
+from . import rollout as RO
+from .replay import record_games  # noqa: F401  (its name here, as the command lines of the fits know it)
 
 ENTRIES = T.PATTERN_ENTRIES                                            # 2 * 4^8
 NEAR = 1 << 16
 NEIGHBOURS = ((-1, 0), (1, 0), (0, -1), (0, 1), (-1, -1), (-1, 1), (1, -1), (1, 1))      # slot i: (dr, dc)
-MOVE_NONE = T.MOVE_NONE
 # The dihedral group of the square as integer matrices (a, b, c, d): (dr, dc) -> (a dr + b dc, c dr + d dc).
 SYMMETRIES = ((1, 0, 0, 1), (0, -1, 1, 0), (-1, 0, 0, -1), (0, 1, -1, 0), (1, 0, 0, -1), (-1, 0, 0, 1), (0, 1, 1, 0),
               (0, -1, -1, 0))
@@ -117,25 +119,28 @@ def select_weighted(x0, entries, playable):
 
 
 # ---- the table ------------------------------------------------------------------------------------------------------------------
-class PatternTable:
-    """uint16 [ENTRIES] weights, indexed by the pattern index; device(dev) is a cached copy for bkt_pattern_playouts."""
+class WeightTable:
+    """uint16 [ENTRIES] weights of the playouts' draw; a subclass names its ENTRIES and its NOUN.  device(dev) is a cached
+    copy for the playout kernels."""
+    ENTRIES = NOUN = None
 
     def __init__(self, array):
         array = np.asarray(array)
-        if array.shape != (ENTRIES,) or array.dtype != np.uint16:
-            raise ValueError(f"a pattern table is uint16 [{ENTRIES}], got {array.dtype} {array.shape}")
+        if array.shape != (self.ENTRIES,) or array.dtype != np.uint16:
+            raise ValueError(f"a {self.NOUN} table is uint16 [{self.ENTRIES}], got {array.dtype} {array.shape}")
         self.array = np.ascontiguousarray(array)
         self._device = {}
 
     @classmethod
-    def constant(cls, c):
-        if not 0 <= int(c) <= 65535:
-            raise ValueError("a weight is 0..65535")
-        return cls(np.full(ENTRIES, int(c), np.uint16))
-
-    @classmethod
     def load(cls, path):
         return cls(np.load(path, allow_pickle=False))
+
+    @classmethod
+    def coerce(cls, table):
+        """None, a table of this class, a uint16 [ENTRIES] array or the path of a saved table -> None or a table."""
+        if table is None or isinstance(table, cls):
+            return table
+        return cls(table) if isinstance(table, np.ndarray) else cls.load(table)
 
     def save(self, path):
         with open(path, "wb") as f:                                   # an open file: np.save appends no suffix
@@ -146,7 +151,7 @@ class PatternTable:
         return self.array[codes]
 
     def device(self, dev):
-        """int16 [ENTRIES] on dev holding the bits of the weights (what _trainlib.pattern_playouts takes)."""
+        """int16 [ENTRIES] on dev holding the bits of the weights (what _trainlib's playouts take)."""
         dev = torch.device(dev)
         if dev.type == "cuda" and dev.index is None:
             dev = torch.device("cuda", torch.cuda.current_device())
@@ -155,28 +160,21 @@ class PatternTable:
         return self._device[dev]
 
 
-def as_table(patterns):
-    """None, a PatternTable, a uint16 [ENTRIES] array or the path of a saved table -> None or a PatternTable."""
-    if patterns is None or isinstance(patterns, PatternTable):
-        return patterns
-    if isinstance(patterns, np.ndarray):
-        return PatternTable(patterns)
-    return PatternTable.load(patterns)
+class PatternTable(WeightTable):
+    """The weights indexed by the pattern index (bkt_pattern_playouts)."""
+    ENTRIES, NOUN = ENTRIES, "pattern"
+
+    @classmethod
+    def constant(cls, c):
+        if not 0 <= int(c) <= 65535:
+            raise ValueError("a weight is 0..65535")
+        return cls(np.full(ENTRIES, int(c), np.uint16))
+
+
+as_table = PatternTable.coerce          # None, a PatternTable, a uint16 [ENTRIES] array or the path of a saved table
 
 
 # ---- the fit --------------------------------------------------------------------------------------------------------------------
-def _numpy(x):
-    return x.cpu().numpy() if isinstance(x, torch.Tensor) else x
-
-
-def _check_games(start_recs, moves):
-    start = np.ascontiguousarray(_numpy(start_recs), np.uint8)
-    moves = np.asarray(moves)
-    if start.ndim != 2 or start.shape[1] != L.POS_BYTES or moves.ndim != 2 or len(moves) != len(start):
-        raise ValueError("counts takes records uint8 [G,192] and their moves [G,L]")
-    return start, moves.astype(np.int32)
-
-
 def counts(start_recs, moves, rules="device", device=None):
     """Replay the games in lock-step and count patterns -> (seen, played), both int64 [ENTRIES] (numpy).
     start_recs uint8 [G,192]; moves [G,L]: the move of each ply, a point, go.PASS, or MOVE_NONE once a game is over (the
@@ -185,55 +183,25 @@ def counts(start_recs, moves, rules="device", device=None):
     eye, and such a ply adds to seen only.  rules="device": bkt_playout_step, bkt_pattern_codes and torch.bincount;
     rules="host": the mirror on the host rules, the same integers."""
     L.check_rules(rules)
-    start, moves = _check_games(start_recs, moves)
+    start, moves = RP.check_games(start_recs, moves)
     if rules == "host":
-        return _counts_host(start, moves)
-    from . import rollout
-    dev = rollout._device(device, None, start_recs)
+        seen, played = np.zeros(ENTRIES, np.int64), np.zeros(ENTRIES, np.int64)
+        for _, _, live, recs, mv, ok in RP.replay_host(start, moves):
+            codes = codes_host(recs[live])
+            seen += np.bincount(codes[ok], minlength=ENTRIES)
+            at, good = RP.counted(mv, ok)
+            played += np.bincount(RP.at_move(codes, at)[good], minlength=ENTRIES)
+        return seen, played
+    dev = RO._device(device, None, start_recs)
     seen = torch.zeros(ENTRIES, dtype=torch.int64, device=dev)
     played = torch.zeros(ENTRIES, dtype=torch.int64, device=dev)
-    for s in range(0, len(start), T.MAX_BATCH):
-        _counts_device(torch.from_numpy(start[s:s + T.MAX_BATCH]).to(dev), torch.from_numpy(moves[s:s + T.MAX_BATCH]).to(dev),
-                       seen, played)
-    return seen.cpu().numpy(), played.cpu().numpy()
-
-
-def _counts_device(pos, hist, seen, played):
-    G = len(pos)
-    playable = torch.empty((G, 81), dtype=torch.uint8, device=pos.device)
-    none = torch.full((G,), MOVE_NONE, dtype=torch.int32, device=pos.device)
-    status = T.playout_step(pos, none, None, None, playable)             # the playable sets of the start records
-    for k in range(hist.shape[1]):
-        mv = hist[:, k].contiguous()
-        live = mv > MOVE_NONE
+    for _, _, pos, mv, live, playable in RP.replay_device(start, moves, dev):
         codes = T.pattern_codes(pos).to(torch.int64)
         ok = (playable != 0) & live[:, None]
         seen += torch.bincount(codes[ok], minlength=ENTRIES)
-        at = mv.clamp(0, 80).to(torch.int64)[:, None]
-        good = (mv >= 0) & ok.gather(1, at)[:, 0]
-        played += torch.bincount(codes.gather(1, at)[:, 0][good], minlength=ENTRIES)
-        status |= T.playout_step(pos, mv, None, None, playable)
-    L.check_status(status, lambda g, st: f"game {g}: a recorded move is illegal (status {st})")
-
-
-def _counts_host(start, moves):
-    from . import rollout
-    recs = start.copy()
-    seen, played = np.zeros(ENTRIES, np.int64), np.zeros(ENTRIES, np.int64)
-    for k in range(moves.shape[1]):
-        live = np.nonzero(moves[:, k] > MOVE_NONE)[0]
-        if len(live) == 0:
-            continue
-        mv = moves[live, k]
-        ok = rollout.playable_host(recs[live])
-        codes = codes_host(recs[live])
-        seen += np.bincount(codes[ok], minlength=ENTRIES)
-        at = np.clip(mv, 0, 80)
-        rows = np.arange(len(live))
-        good = (mv >= 0) & ok[rows, at]
-        played += np.bincount(codes[rows, at][good], minlength=ENTRIES)
-        L.play_host(recs, live, mv, lambda g, m: f"game {g}: the recorded move {m} is illegal", liberties=True)
-    return seen, played
+        at, good = RP.counted(mv, ok)                # (launched while the bincount runs; before it, the ply waits 20 us longer)
+        played += torch.bincount(RP.at_move(codes, at)[good], minlength=ENTRIES)
+    return seen.cpu().numpy(), played.cpu().numpy()
 
 
 _CANONICAL = None
@@ -276,22 +244,6 @@ def weights(seen, played, scale=1024, prior_played=1, prior_seen=32):
 def fit(start_recs, moves, rules="device", device=None, **kw):
     """counts -> symmetrise -> weights -> a PatternTable."""
     return PatternTable(weights(*symmetrise(*counts(start_recs, moves, rules, device)), **kw))
-
-
-def record_games(paths):
-    """The games of selfplay --out records (train.find_records) -> (start records uint8 [G,192], moves int16 [G,L])."""
-    import json
-
-    from .train import find_records
-    games = []
-    for path in find_records(paths):
-        with open(path) as f:
-            rec = json.load(f)
-        games += [rec[g]["moves"] for g in sorted(rec, key=int)]
-    moves = np.full((len(games), max(max(len(m) for m in games), 1)), MOVE_NONE, np.int16)
-    for i, m in enumerate(games):
-        moves[i, :len(m)] = m
-    return L.initial_positions(len(games)), moves
 
 
 # ---- the command line -----------------------------------------------------------------------------------------------------------
@@ -354,21 +306,11 @@ def main(argv=None):
     if args.command == "show":
         print(show(PatternTable.load(args.table), args.n))
         return
-    from . import rollout
-    from .reinforce import policy_engine
-    from .train import load_weights
-
     torch.cuda.set_device(args.device)
     dev = torch.device("cuda", args.device)
     seen, played = np.zeros(ENTRIES, np.int64), np.zeros(ENTRIES, np.int64)
     if args.games:
-        eng = policy_engine(load_weights(args.p), args.device, min(args.games, 4096))
-        try:
-            start = L.initial_positions(args.games)
-            fin = rollout.finish_games(start, eng, args.seed, device=dev)
-        finally:
-            eng.close()
-        seen, played = counts(start, fin.moves, device=dev)
+        seen, played = counts(*RP.policy_games(args.p, args.games, args.seed, dev), device=dev)
     if args.records:
         more = counts(*record_games(args.records), device=dev)
         seen, played = seen + more[0], played + more[1]

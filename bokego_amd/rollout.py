@@ -90,7 +90,7 @@ import torch
 from . import _trainlib as T
 from . import go
 from . import lockstep as L
-from .lockstep import record_turns  # noqa: F401  (public here: see __all__)
+from .lockstep import playable_host, record_turns  # noqa: F401  (public here: see __all__)
 from .replies import (ReplyTable, ReplyTable2, ReplyTables, ReplyTables2, reply2_moves, reply2_plies_of, reply2_update_host, reply_moves, reply_plies_of,
                       reply_update_host, slots_of)
 
@@ -129,21 +129,6 @@ class Finished:
 def default_counters(n, turns):
     """(g mod 2^32, turn, g >> 32, 2) for the games g = 0 .. n-1, int32 [n, 4]."""
     return L.game_counters(np.arange(n, dtype=np.uint64), turns, L.STREAM_ROLLOUT)
-
-
-def playable_host(recs):
-    """bool [n,81]: bk_pos_is_legal(p, s) and bk_pos_possible_eye(p, s) != the colour to move (black on an even turn)."""
-    lib = go.golib()
-    out = np.zeros((len(recs), 81), bool)
-    buf = (ctypes.c_uint8 * 81)()
-    for i in range(len(recs)):
-        p = L.pos_ptr(recs[i])
-        lib.bk_pos_legal_moves(p, buf)
-        mover = 2 if p.contents.turn & 1 else 1
-        for s in range(81):
-            if buf[s] and lib.bk_pos_possible_eye(p, s) != mover:
-                out[i, s] = True
-    return out
 
 
 def _engines(engine, sides, G):

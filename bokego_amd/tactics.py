@@ -38,10 +38,11 @@ import torch
 from . import _trainlib as T
 from . import lockstep as L
 from . import patterns as PT
+from . import replay as RP
+from . import rollout as RO
 
 ENTRIES = T.TACTIC_ENTRIES
 NEUTRAL = 256
-MOVE_NONE = T.MOVE_NONE
 
 __all__ = ["ENTRIES", "NEUTRAL", "TacticTable", "as_tactics", "codes_host", "combine", "counts", "describe", "fit",
            "select_tactical", "weights"]
@@ -107,50 +108,16 @@ def select_tactical(x0, pattern_entries, tactic_entries, playable):
 
 
 # ---- the table ------------------------------------------------------------------------------------------------------------------
-class TacticTable:
-    """uint16 [ENTRIES] weights indexed by the tactical code, 256 = neutral; device(dev) is a cached copy for
-    bkt_tactical_playouts."""
-
-    def __init__(self, array):
-        array = np.asarray(array)
-        if array.shape != (ENTRIES,) or array.dtype != np.uint16:
-            raise ValueError(f"a tactics table is uint16 [{ENTRIES}], got {array.dtype} {array.shape}")
-        self.array = np.ascontiguousarray(array)
-        self._device = {}
+class TacticTable(PT.WeightTable):
+    """The weights indexed by the tactical code, 256 = neutral (bkt_tactical_playouts)."""
+    ENTRIES, NOUN = ENTRIES, "tactics"
 
     @classmethod
     def neutral(cls):
         return cls(np.full(ENTRIES, NEUTRAL, np.uint16))
 
-    @classmethod
-    def load(cls, path):
-        return cls(np.load(path, allow_pickle=False))
 
-    def save(self, path):
-        with open(path, "wb") as f:                                   # an open file: np.save appends no suffix
-            np.save(f, self.array, allow_pickle=False)
-
-    def entries(self, codes):
-        """The table entry of every code of codes (numpy)."""
-        return self.array[codes]
-
-    def device(self, dev):
-        """int16 [ENTRIES] on dev holding the bits of the weights (what _trainlib.tactical_playouts takes)."""
-        dev = torch.device(dev)
-        if dev.type == "cuda" and dev.index is None:
-            dev = torch.device("cuda", torch.cuda.current_device())
-        if dev not in self._device:
-            self._device[dev] = torch.from_numpy(self.array.view(np.int16).copy()).to(dev)
-        return self._device[dev]
-
-
-def as_tactics(tactics):
-    """None, a TacticTable, a uint16 [ENTRIES] array or the path of a saved table -> None or a TacticTable."""
-    if tactics is None or isinstance(tactics, TacticTable):
-        return tactics
-    if isinstance(tactics, np.ndarray):
-        return TacticTable(tactics)
-    return TacticTable.load(tactics)
+as_tactics = TacticTable.coerce         # None, a TacticTable, a uint16 [ENTRIES] array or the path of a saved table
 
 
 # ---- the fit --------------------------------------------------------------------------------------------------------------------
@@ -164,62 +131,32 @@ def counts(start_recs, moves, patterns=None, rules="device", device=None):
     in another order."""
     L.check_rules(rules)
     table = PT.as_table(patterns)
-    start, moves = PT._check_games(start_recs, moves)
+    start, moves = RP.check_games(start_recs, moves)
     if rules == "host":
-        return _counts_host(start, moves, table)
-    from . import rollout
-    dev = rollout._device(device, None, start_recs)
+        mass, played = np.zeros(ENTRIES, np.float64), np.zeros(ENTRIES, np.int64)
+        for _, _, live, recs, mv, ok in RP.replay_host(start, moves):
+            codes = codes_host(recs[live])
+            P = ok.astype(np.float64)
+            if table is not None:
+                P = P * np.maximum(table.entries(PT.codes_host(recs[live])), 1).astype(np.float64)
+            share = P / np.maximum(P.sum(1, keepdims=True), 1.0)
+            mass += np.bincount(codes[ok], weights=share[ok], minlength=ENTRIES)
+            at, good = RP.counted(mv, ok)
+            played += np.bincount(RP.at_move(codes, at)[good], minlength=ENTRIES)
+        return mass, played
+    dev = RO._device(device, None, start_recs)
     mass = torch.zeros(ENTRIES, dtype=torch.float64, device=dev)
     played = torch.zeros(ENTRIES, dtype=torch.int64, device=dev)
-    for s in range(0, len(start), T.MAX_BATCH):
-        _counts_device(torch.from_numpy(start[s:s + T.MAX_BATCH]).to(dev), torch.from_numpy(moves[s:s + T.MAX_BATCH]).to(dev),
-                       table, mass, played)
-    return mass.cpu().numpy(), played.cpu().numpy()
-
-
-def _counts_device(pos, hist, table, mass, played):
-    G = len(pos)
-    playable = torch.empty((G, 81), dtype=torch.uint8, device=pos.device)
-    none = torch.full((G,), MOVE_NONE, dtype=torch.int32, device=pos.device)
-    w = None if table is None else (table.device(pos.device).to(torch.int64) & 0xFFFF).clamp_(min=1).to(torch.float64)
-    status = T.playout_step(pos, none, None, None, playable)             # the playable sets of the start records
-    for k in range(hist.shape[1]):
-        mv = hist[:, k].contiguous()
-        live = mv > MOVE_NONE
+    w = None if table is None else (table.device(dev).to(torch.int64) & 0xFFFF).clamp_(min=1).to(torch.float64)
+    for _, _, pos, mv, live, playable in RP.replay_device(start, moves, dev):
         codes = T.tactical_codes(pos).to(torch.int64)
         ok = (playable != 0) & live[:, None]
         P = ok.to(torch.float64) if w is None else w[T.pattern_codes(pos).to(torch.int64)] * ok
-        share = P / P.sum(1, keepdim=True).clamp_(min=1.0)               # a row without a playable point adds nothing
+        share = P / P.sum(1, keepdim=True).clamp_(min=1.0)                   # a row without a playable point adds nothing
         mass += torch.bincount(codes[ok], weights=share[ok], minlength=ENTRIES)
-        at = mv.clamp(0, 80).to(torch.int64)[:, None]
-        good = (mv >= 0) & ok.gather(1, at)[:, 0]
-        played += torch.bincount(codes.gather(1, at)[:, 0][good], minlength=ENTRIES)
-        status |= T.playout_step(pos, mv, None, None, playable)
-    L.check_status(status, lambda g, st: f"game {g}: a recorded move is illegal (status {st})")
-
-
-def _counts_host(start, moves, table):
-    from . import rollout
-    recs = start.copy()
-    mass, played = np.zeros(ENTRIES, np.float64), np.zeros(ENTRIES, np.int64)
-    for k in range(moves.shape[1]):
-        live = np.nonzero(moves[:, k] > MOVE_NONE)[0]
-        if len(live) == 0:
-            continue
-        mv = moves[live, k]
-        ok = rollout.playable_host(recs[live])
-        codes = codes_host(recs[live])
-        P = ok.astype(np.float64)
-        if table is not None:
-            P = P * np.maximum(table.entries(PT.codes_host(recs[live])), 1).astype(np.float64)
-        share = P / np.maximum(P.sum(1, keepdims=True), 1.0)
-        mass += np.bincount(codes[ok], weights=share[ok], minlength=ENTRIES)
-        at = np.clip(mv, 0, 80)
-        rows = np.arange(len(live))
-        good = (mv >= 0) & ok[rows, at]
-        played += np.bincount(codes[rows, at][good], minlength=ENTRIES)
-        L.play_host(recs, live, mv, lambda g, m: f"game {g}: the recorded move {m} is illegal", liberties=True)
-    return mass, played
+        at, good = RP.counted(mv, ok)
+        played += torch.bincount(RP.at_move(codes, at)[good], minlength=ENTRIES)
+    return mass.cpu().numpy(), played.cpu().numpy()
 
 
 def weights(mass, played, prior=16.0):
@@ -282,19 +219,9 @@ def main(argv=None):
     if args.command == "show":
         print(show(TacticTable.load(args.table)))
         return
-    from . import rollout
-    from .reinforce import policy_engine
-    from .train import load_weights
-
     torch.cuda.set_device(args.device)
     dev = torch.device("cuda", args.device)
-    eng = policy_engine(load_weights(args.p), args.device, min(args.games, 4096))
-    try:
-        start = L.initial_positions(args.games)
-        fin = rollout.finish_games(start, eng, args.seed, device=dev)
-    finally:
-        eng.close()
-    mass, played = counts(start, fin.moves, args.patterns, device=dev)
+    mass, played = counts(*RP.policy_games(args.p, args.games, args.seed, dev), args.patterns, device=dev)
     table = TacticTable(weights(mass, played, prior=args.prior))
     table.save(args.o)
     print(f"{int(played.sum())} moves, {int((played > 0).sum())} codes played -> {args.o}")
