@@ -320,7 +320,8 @@ def _sample(name, logits, mask_args, seed, counters):
 
 def sample_moves(logits, planes, seed, counters):
     """One move per row: logits [B,81] f32, planes uint8 [B,27,9,9] (plane 5: legal points), counters int32 [B,4]
-    (the Philox counter words, read as uint32) -> (moves int32 [B], -1 where no point is legal; logp f32 [B])."""
+    (the Philox counter words, read as uint32) -> (moves int32 [B], -1 where no point is legal; logp f32 [B], NaN on a
+    row whose logits are not finite: bokego_train.h, "Degenerate rows")."""
     return _sample("bkt_sample_moves", logits, lambda B: (_dev(planes, "planes", (B, 27, 9, 9), torch.uint8),), seed,
                    counters)
 

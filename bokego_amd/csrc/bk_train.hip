@@ -441,8 +441,15 @@ __device__ __forceinline__ void philox4x32_10(uint32_t (&c)[4], uint32_t k0, uin
     }
 }
 
+// The bit tests of the degenerate-row contract (bokego_train.h): integer logic, which no float comparison can defeat.
+__device__ __forceinline__ bool is_nan_bits(float v) { return (__float_as_uint(v) & 0x7FFFFFFFu) > 0x7F800000u; }
+__device__ __forceinline__ bool is_nan_or_pinf(float v) { return is_nan_bits(v) || __float_as_uint(v) == 0x7F800000u; }
+
 // Lane l holds points l and 64 + l (the second only for l < 17).  Every branch below is uniform over the wave.
 // mask[row * mask_stride + i] != 0: point i may be played (bkt_sample_moves: the legal plane inside the feature planes).
+// xa / xb are the logits with NaN replaced by -inf (an ordinary row keeps its bits), so every comparison below is total;
+// `deg` marks a degenerate row, whose draw is discarded.  The stored move is -1 or in 0..80 on every path: a drawn mv comes
+// from a ballot bit (0..63, 64..80) or is 0, and the replacement's index passes an unsigned bound before it is used.
 __global__ __launch_bounds__(64 * SAMPLE_WAVES) void sample_moves_kernel(const float *__restrict__ logits,
                                                                          const uint8_t *__restrict__ mask,
                                                                          size_t mask_stride, int batch,
@@ -456,10 +463,13 @@ __global__ __launch_bounds__(64 * SAMPLE_WAVES) void sample_moves_kernel(const f
     const float *x = logits + (size_t)row * P;
     const uint8_t *legal = mask + (size_t)row * mask_stride;
     const bool has1 = lane < P - 64;
-    const float xa = x[lane], xb = has1 ? x[64 + lane] : -INFINITY;
+    const float ra = x[lane], rb = has1 ? x[64 + lane] : -INFINITY;
+    const float xa = is_nan_bits(ra) ? -INFINITY : ra, xb = is_nan_bits(rb) ? -INFINITY : rb;
     float m = fmaxf(xa, xb);
 #pragma unroll
     for (int d = 32; d > 0; d >>= 1) m = fmaxf(m, __shfl_xor(m, d));
+    // degenerate: a NaN or +inf logit, or all 81 at -inf (m is free of NaN: its bits say so)
+    const bool deg = __ballot(is_nan_or_pinf(ra) || is_nan_or_pinf(rb)) != 0ull || __float_as_uint(m) == 0xFF800000u;
     const float pa = expf(xa - m), pb = has1 ? expf(xb - m) : 0.f;
     float sa = pa, sb = pb;  // inclusive prefixes of p over points 0..63 and 64..80
 #pragma unroll
@@ -489,11 +499,11 @@ __global__ __launch_bounds__(64 * SAMPLE_WAVES) void sample_moves_kernel(const f
         mv = zb ? 64 + 63 - __clzll(zb) : (za ? 63 - __clzll(za) : 0);
     }
     const unsigned long long la = __ballot(legal[lane] != 0), lb = __ballot(has1 && legal[64 + lane] != 0);
-    const bool ok = mv < 64 ? (la >> mv) & 1ull : (lb >> (mv - 64)) & 1ull;
-    if (!ok) {
+    const bool ok = !deg && (mv < 64 ? (la >> mv) & 1ull : (lb >> (mv - 64)) & 1ull);
+    if (!ok) {  // an illegal sample, or a degenerate row (no draw counts there)
         if (!(la | lb)) {
             mv = -1;
-        } else {  // the legal point of the largest logit, lowest index on ties
+        } else {  // the legal point of the largest logit (NaN ordered as -inf), lowest index on ties
             float bv = -INFINITY;
             int bi = 1 << 30;
             if ((la >> lane) & 1ull) bv = xa, bi = lane;
@@ -504,12 +514,12 @@ __global__ __launch_bounds__(64 * SAMPLE_WAVES) void sample_moves_kernel(const f
                 const int oi = __shfl_xor(bi, d);
                 if (ov > bv || (ov == bv && oi < bi)) bv = ov, bi = oi;
             }
-            mv = bi;
+            mv = (unsigned)bi < (unsigned)P ? bi : -1;
         }
     }
     if (lane == 0) {
         moves[row] = mv;
-        logp[row] = mv >= 0 ? (x[mv] - m) - logf(S) : 0.f;
+        logp[row] = deg ? __uint_as_float(0x7FC00000u) : (mv >= 0 ? (x[mv] - m) - logf(S) : 0.f);
     }
 }
 

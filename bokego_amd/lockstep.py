@@ -56,21 +56,34 @@ def uniform(x0):
 def sample_host(logits, legal, u):
     """bkt_sample_moves in float64: logits [B,81], legal bool [B,81], u [B] -> (moves int32 [B], logp float64 [B]).
     The move is the first point whose inclusive prefix of p = exp(x - max) exceeds u * sum p; an illegal sample becomes
-    the legal point of the largest logit (lowest index on ties); -1 when no point is legal."""
-    x = np.asarray(logits, np.float64)
+    the legal point of the largest logit (lowest index on ties); -1 when no point is legal.
+    A degenerate row (degenerate_rows) makes no draw: its move is that replacement with NaN ordered as -inf, whatever u
+    is, and its logp is NaN (bokego_train.h)."""
+    with np.errstate(invalid="ignore"):                              # widening a signalling NaN raises the flag
+        raw = np.asarray(logits, np.float64)
     legal = np.asarray(legal, bool)
-    m = x.max(1, keepdims=True)
-    c = np.cumsum(np.exp(x - m), 1)
+    deg = degenerate_rows(raw)
+    x = np.where(np.isnan(raw), -np.inf, raw)
+    xo = np.where(deg[:, None], 0.0, x)                              # the draw of an ordinary row; a degenerate one's is unused
+    m = xo.max(1, keepdims=True)
+    c = np.cumsum(np.exp(xo - m), 1)
     S = c[:, -1]
     mv = np.argmax(c > (np.asarray(u, np.float64) * S)[:, None], 1)
     rows = np.arange(len(x))
-    bad = ~legal[rows, mv]
-    fix = np.argmax(np.where(legal, x, -np.inf), 1)
+    bad = deg | ~legal[rows, mv]
+    best = np.where(legal, x, -np.inf)
+    fix = np.argmax(legal & (best == best.max(1, keepdims=True)), 1)  # the lowest legal index also when every legal logit is -inf
     mv = np.where(bad, fix, mv)
     none = ~legal.any(1)
     mv[none] = -1
-    logp = np.where(none, 0.0, x[rows, np.maximum(mv, 0)] - m[:, 0] - np.log(S))
-    return mv.astype(np.int32), logp
+    logp = np.where(none, 0.0, xo[rows, np.maximum(mv, 0)] - m[:, 0] - np.log(S))
+    return mv.astype(np.int32), np.where(deg, np.nan, logp)
+
+
+def degenerate_rows(logits):
+    """bool [B]: the rows bkt_sample_moves makes no draw on: a NaN or +inf logit, or all 81 at -inf."""
+    x = np.asarray(logits)
+    return np.isnan(x).any(1) | (x == np.inf).any(1) | (x == -np.inf).all(1)
 
 
 def cdf_margin(logits, u):

@@ -51,8 +51,8 @@ from . import _trainlib as T
 from . import go
 from . import lockstep as L
 from .lockstep import (KOMI, LEGAL_PLANE, PLANE_BYTES, POS_BYTES, _play_fn, cdf_margin,  # noqa: F401  (the shared
-                       features_batch, initial_positions, philox4x32_10, sample_host,    # pieces, under the names the
-                       seed_key, uniform)                                                # tests and tools know)
+                       degenerate_rows, features_batch, initial_positions, philox4x32_10,  # pieces, under the names the
+                       sample_host, seed_key, uniform)                                   # tests and tools know)
 from .selfplay import POLICY_MAX_TURNS
 
 UPDATE_CHUNK = 32768       # rows per forward/backward of the update (libbktrain's trunk takes up to 65536)
@@ -158,6 +158,13 @@ def _start_positions(start, G):
     return start
 
 
+def _check_logp(games):
+    """games: the games with a kept row whose logp is NaN (bkt_sample_moves' mark of a degenerate row)."""
+    if len(games):
+        raise FloatingPointError(f"game {int(np.min(games))}: the policy's logits are not finite (a NaN, a +inf or a "
+                                 f"row of -inf: the sampler drew nothing there), in {len(np.unique(games))} game(s)")
+
+
 def _finish(recs, perm, nb, plies, learner, opponent, key, iteration, epoch, dev, rules):
     """play_games(finish=True): play out the records recs (slot order: perm[slot] = game, the learner black in slots
     [0, nb)) whose turn is `plies` -> (the slots played out, rollout.Finished)."""
@@ -222,9 +229,15 @@ def _play_games_device(learner, opponent, n_batches, batch_size, key, iteration,
             score[torch.from_numpy(sel).to(dev)] = torch.from_numpy(fin.score).to(dev)
         finished = (perm[sel], fin)
         t = lap("finish", t)
-    back = torch.cat([hist, score.view(torch.int16).view(G, 2), status.view(torch.int16).view(G, 2)], 1).cpu().numpy()
+    # per slot, the kept rows (a move was played) whose logp is NaN: one more column of the one download
+    row_slot = torch.from_numpy(np.concatenate([np.arange(G)[side[p % 2]] for p in range(T_)])).to(dev)
+    nan_rows = torch.zeros(G, dtype=torch.int32, device=dev).index_add_(
+        0, row_slot, (torch.isnan(rows_logp) & (rows_moves >= 0)).to(torch.int32))
+    back = torch.cat([hist, score.view(torch.int16).view(G, 2), status.view(torch.int16).view(G, 2),
+                      nan_rows.to(torch.int16).view(G, 1)], 1).cpu().numpy()
     t = lap("download", t)
-    st = np.ascontiguousarray(back[:, T_ + 2:]).view(np.int32)[:, 0]
+    _check_logp(perm[np.nonzero(back[:, T_ + 4])[0]])
+    st = np.ascontiguousarray(back[:, T_ + 2:T_ + 4]).view(np.int32)[:, 0]
     L.check_status(st, lambda s, v: f"game {perm[s]}: a sampled move is illegal (status {v}); the legal plane and the "
                    "rules disagree")
     out = Playouts()
@@ -263,7 +276,9 @@ def play_games(learner, opponent, n_batches, batch_size, seed, iteration=0, epoc
     finish=True: the games are then played out to the end (rollout.finish_games with the same rules, phase 'finish') and
     black_wins / reward come from the finished boards; moves, length and the learner's rows are what they are without
     it.  The Playouts then also has finished_games (the games played out: all but those whose turn lags) and finished
-    (their rollout.Finished, or None when there is none)."""
+    (their rollout.Finished, or None when there is none).
+    FloatingPointError when the logp of a kept row is NaN, bkt_sample_moves' mark of a row whose logits are not finite
+    (a diverged learner, a bad checkpoint): found where the results come to the host anyway, with no wait per ply."""
     L.check_rules(rules)
     G = n_batches * batch_size
     pos = _start_positions(start, G)
@@ -337,6 +352,7 @@ def play_games(learner, opponent, n_batches, batch_size, seed, iteration=0, epoc
         out.played = torch.cat(rows_moves).long()
         out.logp = torch.cat(rows_logp)
         out.row_game = np.concatenate(rows_game).astype(np.int64)
+        _check_logp(out.row_game[torch.isnan(out.logp).cpu().numpy()])      # once per call, after the last ply
     else:
         out.planes = torch.empty((0, 27, 9, 9), dtype=torch.uint8, device=dev)
         out.played = torch.empty((0,), dtype=torch.int64, device=dev)

@@ -152,6 +152,13 @@ int bkt_bn_relu_eval_backward(const float *dy, const float *y, const float *x, c
  * 5 of the uint8 feature planes [B, 27, 9, 9] (nnet.features' "legal" plane): a sample that is not legal is replaced by
  * the legal point of the largest logit (lowest index on ties), and a row with no legal point gets -1.
  * moves [B] (int32) and logp [B] = log softmax(x) at the move (0 where the move is -1).
+ * Degenerate rows.  A row is degenerate when any of its 81 logits is NaN or +inf, or when all 81 are -inf; a row of
+ * finite and -inf logits with at least one finite is an ordinary row (a -inf point has p = 0 and is never drawn; when
+ * every legal logit is -inf the draw lands outside the set and the replacement gives the lowest legal index).  On a
+ * degenerate row no draw is made: the move is the replacement rule's -- the legal point of the largest logit, with NaN
+ * ordered as -inf and the lowest index on ties, or -1 with no legal point -- whatever the counter, and logp[b] is NaN
+ * (also where the move is -1), which is how the caller sees that the policy's logits were not finite.  On every row, of
+ * either kind, moves[b] is -1 or a point of the set in 0..80, and no logit outside the row's 81 is read.
  * 1 <= B <= BKT_MAX_SAMPLE_ROWS (rows are independent: no trunk batch limit applies). */
 int bkt_sample_moves(const float *logits, const uint8_t *planes, int batch, uint64_t seed, const uint32_t *counters,
                      int32_t *moves, float *logp, void *stream);

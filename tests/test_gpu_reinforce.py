@@ -1,5 +1,6 @@
 """-m gpu: the REINFORCE learner on the MI355X (bkt_bn_relu_eval_backward, bkt_sample_moves, bokego_amd/reinforce.py)
 against float64 torch on the CPU, the float64 host mirrors and go.Game."""
+import ctypes
 import math
 import os
 import shutil
@@ -9,8 +10,9 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import sampler_cases as SC
 from bokego_amd import _trainlib as T
-from bokego_amd import go, nnet, train
+from bokego_amd import go, lockstep, nnet, train
 from bokego_amd import reinforce as R
 from conftest import GOLDEN
 
@@ -198,6 +200,140 @@ def test_sampler_chi_square(engine_logits):
         e[-1] += exp[~big].sum()
     stat = float(((o - e) ** 2 / e).sum())
     assert _chi2_sf(stat, len(o) - 1) > 1e-6, stat
+
+
+# ---- the sampler at the float edges (sampler_cases.py; test_reinforce_cpu.py holds the mirror to the same rows) -----------
+def _sample_checked(x, mask, c):
+    """bkt_sample_moves of logits x (numpy f32 [n,81], or a device tensor) with the legal plane = mask (numpy bool [n,81],
+    or None: every point), counters c -> (moves, logp) as numpy.  On the way: a second call and one call of
+    bkt_sample_moves_masked with mask_stride 81 give the same bits, and every move is a point of its row's set, -1
+    exactly where the set is empty."""
+    d_lg = x if isinstance(x, torch.Tensor) else torch.from_numpy(x).to(DEV)
+    n = len(d_lg)
+    d_mask = (torch.ones((n, 81), dtype=torch.uint8, device=DEV) if mask is None else
+              torch.from_numpy(mask.astype(np.uint8)).to(DEV))
+    planes = torch.zeros((n, 27, 81), dtype=torch.uint8, device=DEV)
+    planes[:, R.LEGAL_PLANE] = d_mask
+    planes, d_c = planes.view(n, 27, 9, 9), torch.from_numpy(c).to(DEV)
+    mv, lp = T.sample_moves(d_lg, planes, SC.SEED, d_c)
+    for amv, alp in (T.sample_moves(d_lg, planes, SC.SEED, d_c), T.sample_moves_masked(d_lg, d_mask, SC.SEED, d_c)):
+        assert torch.equal(amv, mv) and torch.equal(alp.view(torch.int32), lp.view(torch.int32))
+    mv, lp = mv.cpu().numpy(), lp.cpu().numpy()
+    assert ((mv >= -1) & (mv <= 80)).all(), mv[(mv < -1) | (mv > 80)][:10]
+    some = np.ones(n, bool) if mask is None else mask.any(1)
+    assert np.array_equal(mv >= 0, some)
+    assert mask is None or mask[np.arange(n)[some], mv[some]].all()
+    return mv, lp
+
+
+def test_sampler_indicator_rows_are_exact():
+    """Family A.  Logits in {0, -inf}: p is 0 or 1, every prefix an exact integer, S = n, and the threshold has one
+    rounding that numpy's float32 reproduces (sampler_cases.indicator_moves), so the move is s_floor(thr) on every one of
+    the 74 x 4096 rows, none excused: the prefix scan inside a register, across the lanes, and across the split between
+    points 63 and 64."""
+    x, sup, rs = SC.indicator_rows()
+    c, x0 = SC.draws(len(rs))
+    want, wlp = SC.indicator_moves(sup, rs, x0)
+    d_lg = torch.from_numpy(x).to(DEV)[torch.from_numpy(rs).to(DEV)].contiguous()
+    mv, lp = _sample_checked(d_lg, None, c)
+    bad = np.nonzero(mv != want)[0]
+    assert len(bad) == 0, [(sup[rs[r]].tolist(), int(x0[r]), int(mv[r]), int(want[r])) for r in bad[:3]]
+    assert np.abs(lp - wlp).max() <= 1e-6
+
+
+def test_sampler_replacement_tie_breaks():
+    """Family B.  The sample is one illegal point for every draw (k > 0 asserted), below and above the split; the move
+    is the case's: ties inside a lane, across lanes, against the lane order, and a best point at 63, 64 or 80."""
+    x, legal, want, names = SC.replacement_rows()
+    c, x0 = SC.draws(len(x))
+    assert ((x0 >> 8) > 0).all()
+    mv, lp = _sample_checked(x, legal, c)
+    assert mv.tolist() == want.tolist(), [(n, int(a), int(b)) for n, a, b in zip(names, mv, want) if a != b][:3]
+    assert np.abs(lp - R.sample_host(x, legal, R.uniform(x0))[1]).max() <= 1e-5
+
+
+@pytest.mark.parametrize("s", SC.SPREADS)
+def test_sampler_spreads(s):
+    """Family C.  x = s * z on 40 000 rows, every point legal, by the rule of the mirror test: at most 0.5 % of the rows
+    have u within 1e-5 of a CDF boundary, and no row outside them differs.  logp within 1e-5 + 2^-22 * max |x| (the second
+    term: the one rounding of x[mv] - m, half an ulp of a value up to 2 * max |x|)."""
+    x = SC.spread_rows(s)
+    c, x0 = SC.draws(len(x))
+    u = R.uniform(x0)
+    mv, lp = _sample_checked(x, None, c)
+    want, wlp = R.sample_host(x, np.ones(x.shape, bool), u)
+    near = R.cdf_margin(x, u) < 1e-5
+    diff = mv != want
+    same = ~diff
+    err = np.abs(lp[same] - wlp[same]) / (1e-5 + 2.0 ** -22 * np.abs(x).max(1)[same])
+    print(f"spread {s}: near share {100 * near.mean():.4f} %, differing rows {int(diff.sum())}, "
+          f"largest logp error / tolerance {err.max():.3f}")
+    assert near.mean() <= 0.005
+    assert not (diff & ~near).any(), np.nonzero(diff & ~near)[0][:10]
+    assert err.max() <= 1.0
+
+
+def test_sampler_degenerate_rows():
+    """Family D.  Rows with a NaN, a +inf or nothing but -inf, and their ordinary neighbours, each with point 0 legal,
+    illegal and with no legal point: the move is the contract's (sampler_cases.contract, a plain loop) and the
+    mirror's, logp is NaN exactly on the degenerate rows, 0 on an ordinary row without a legal point."""
+    x, legal, names = SC.degenerate_rows()
+    want, deg = SC.contract(x, legal)
+    c, x0 = SC.draws(len(x))
+    mv, lp = _sample_checked(x, legal, c)
+    hmv, hlp = R.sample_host(x, legal, R.uniform(x0))
+    assert mv.tolist() == want.tolist(), [(n, int(a), int(b)) for n, a, b in zip(names, mv, want) if a != b][:3]
+    assert mv.tolist() == hmv.tolist()
+    assert np.array_equal(np.isnan(lp), deg), [n for n, a, b in zip(names, np.isnan(lp), deg) if a != b][:3]
+    assert (lp[(mv == -1) & ~deg] == 0.0).all()
+    inf = np.isinf(hlp)                                          # an ordinary row whose move has the logit -inf
+    assert np.array_equal(lp[inf], hlp[inf].astype(np.float32)) and inf.any()
+    fin = ~deg & ~inf
+    assert np.abs(lp[fin] - hlp[fin]).max() <= 1e-5
+
+
+def test_sampler_degenerate_rows_write_only_their_outputs():
+    """The C entry points on family D with 64 sentinel elements before and behind moves and logp: untouched, and the
+    elements between them are what the binding returns."""
+    x, legal, _ = SC.degenerate_rows()
+    n, guard = len(x), 64
+    c, _ = SC.draws(n)
+    d_lg, d_c = torch.from_numpy(x).to(DEV), torch.from_numpy(c).to(DEV)
+    d_mask = torch.from_numpy(legal.astype(np.uint8)).to(DEV)
+    want_mv, want_lp = T.sample_moves_masked(d_lg, d_mask, SC.SEED, d_c)
+    planes = torch.zeros((n, 27, 81), dtype=torch.uint8, device=DEV)
+    planes[:, R.LEGAL_PLANE] = d_mask
+    stream = ctypes.c_void_p(torch.cuda.current_stream(DEV).cuda_stream)
+    lib = T.load()
+    for call in (lambda m, l: lib.bkt_sample_moves_masked(d_lg.data_ptr(), d_mask.data_ptr(), 81, n, SC.SEED,
+                                                          d_c.data_ptr(), m, l, stream),
+                 lambda m, l: lib.bkt_sample_moves(d_lg.data_ptr(), planes.data_ptr(), n, SC.SEED, d_c.data_ptr(), m, l,
+                                                   stream)):
+        moves = torch.full((n + 2 * guard,), -77, dtype=torch.int32, device=DEV)
+        logp = torch.full((n + 2 * guard,), -77.0, dtype=torch.float32, device=DEV)
+        assert call(moves.data_ptr() + 4 * guard, logp.data_ptr() + 4 * guard) == 0
+        torch.cuda.synchronize(DEV)
+        for buf in (moves, logp):
+            assert (buf[:guard] == -77).all().item() and (buf[-guard:] == -77).all().item()
+        assert torch.equal(moves[guard:-guard], want_mv)
+        assert torch.equal(logp[guard:-guard].view(torch.int32), want_lp.view(torch.int32))
+
+
+def test_play_games_reports_logits_that_are_not_finite(engines, monkeypatch):
+    """One row of every ply's logits poisoned with NaN (row 0: game 0 on its first ply, the learner's): the sampler
+    still gives legal moves, so the games run to their end, and play_games raises when the results reach the host."""
+    a, b = engines
+    real = lockstep.engine_logits
+
+    def poisoned(pairs):
+        lg = real(pairs).clone()
+        lg[0] = float("nan")
+        return lg
+
+    monkeypatch.setattr(lockstep, "engine_logits", poisoned)
+    for rules in ("device", "host"):
+        with pytest.raises(FloatingPointError, match=r"game 0: the policy's logits are not finite"):
+            R.play_games(a, b, 2, 4, seed=7, rules=rules)
 
 
 # ---- playouts --------------------------------------------------------------------------------------------------------

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+import sampler_cases as SC
 from bokego_amd import go
 from bokego_amd import reinforce as R
 from conftest import GOLDEN
@@ -89,6 +90,80 @@ def test_sampler_no_legal_point():
 def test_cdf_margin():
     x = np.log(np.full((1, 81), 1.0 / 81))
     assert abs(R.cdf_margin(x, [1 / 81 + 1e-7])[0] - 1e-7) < 1e-12
+
+
+# ---- the mirror at the float edges (sampler_cases.py: the kernel meets the same rows in test_gpu_reinforce.py) ------------
+def test_indicator_formula_agrees_with_the_mirror():
+    """Family A's closed form (the float32 threshold, j = floor(thr)) against the float64 CDF wherever u is not within
+    1e-5 of a boundary; the GPU test then holds the kernel to the closed form on every row."""
+    x, sup, rs = SC.indicator_rows()
+    _, x0 = SC.draws(len(rs))
+    want, wlp = SC.indicator_moves(sup, rs, x0)
+    u = R.uniform(x0)
+    far_rows = 0
+    for i, s in enumerate(sup):
+        a, b = i * SC.DRAWS_A, (i + 1) * SC.DRAWS_A
+        lg = np.repeat(x[i:i + 1], SC.DRAWS_A, 0)
+        mv, lp = R.sample_host(lg, np.ones((SC.DRAWS_A, 81), bool), u[a:b])
+        far = R.cdf_margin(lg, u[a:b]) >= 1e-5
+        far_rows += int(far.sum())
+        assert np.array_equal(mv[far], want[a:b][far]), s
+        assert np.isin(want[a:b], s).all() and np.abs(lp - wlp[a:b]).max() <= 1e-12
+    assert far_rows >= 0.995 * len(rs)
+    assert [len(s) for s in sup[:10]] == [1, 1, 1, 1, 2, 2, 64, 17, 81, 27] and len(sup) == 74
+
+
+def test_replacement_cases_on_the_mirror():
+    x, legal, want, names = SC.replacement_rows()
+    _, x0 = SC.draws(len(x))
+    assert ((x0 >> 8) > 0).all()                                # the premise of family B: then the sample is s for every u
+    mv, lp = R.sample_host(x, legal, R.uniform(x0))
+    assert mv.tolist() == want.tolist(), [n for n, a, b in zip(names, mv, want) if a != b][:3]
+    assert np.array_equal(SC.contract(x, legal)[0], want)       # the cases expect what the plain loop gives
+    sampled = np.argmax(x, 1)
+    assert set(sampled.tolist()) == set(SC.SAMPLED) and not legal[np.arange(len(x)), sampled].any()
+    assert np.isfinite(lp).all()
+
+
+def test_degenerate_rows_on_the_mirror():
+    x, legal, names = SC.degenerate_rows()
+    want, deg = SC.contract(x, legal)
+    assert np.array_equal(R.degenerate_rows(x), deg)
+    for u in (0.0, 0.3, 1 - 2.0 ** -24):                        # no draw: the move is the same for every u
+        with np.errstate(all="raise"):                          # and the mirror computes nothing undefined on the way
+            mv, lp = R.sample_host(x, legal, np.full(len(x), u))
+        assert mv.tolist() == want.tolist(), [n for n, a, b in zip(names, mv, want) if a != b][:3]
+        assert np.array_equal(np.isnan(lp), deg), [n for n, a, b in zip(names, np.isnan(lp), deg) if a != b][:3]
+        assert (lp[(mv == -1) & ~deg] == 0.0).all()
+    by = {n: (int(m), bool(d)) for n, m, d in zip(names, want, deg)}
+    assert by["all NaN; point 0 legal"] == (0, True) and by["all NaN; point 0 illegal"] == (7, True)
+    assert by["all NaN; no legal point"] == (-1, True)
+    assert by["all -inf; point 0 illegal"] == (7, True)
+    assert by["one NaN at the legal point 40; point 0 illegal"][1] and by["+inf at the legal point 64; point 0 legal"] == (64, True)
+    assert by["NaN at exactly the legal points; point 0 illegal"] == (7, True)
+    assert by["NaN at exactly the legal points; no legal point"] == (-1, False)
+    assert by["legal logits all -inf among finite illegal ones; point 0 illegal"] == (7, False)
+    assert by["legal logits all -inf among finite illegal ones; point 0 legal"] == (0, False)
+
+
+def test_mirror_takes_the_lowest_legal_index_when_every_legal_logit_is_minus_inf():
+    x = np.zeros((2, 81))
+    legal = np.zeros((2, 81), bool)
+    legal[:, [33, 50]] = True
+    x[:, [33, 50]] = -np.inf
+    x[1, 0] = np.nan                                            # the same set on a degenerate row
+    mv, lp = R.sample_host(x, legal, [0.2, 0.7])
+    assert mv.tolist() == [33, 33] and lp[0] == -np.inf and np.isnan(lp[1])
+
+
+def test_mirror_is_unchanged_on_ordinary_rows():
+    """An ordinary row's -inf entries have no mass and are never drawn; the draw is the float64 CDF's as before."""
+    with np.errstate(divide="ignore"):
+        x = np.log(np.array([0.25, 0.0, 0.25, 0.5] + [0.0] * 77))
+    legal = np.ones((1, 81), bool)
+    for u, want in ((0.0, 0), (0.25, 2), (0.49, 2), (0.5, 3), (1 - 2.0 ** -24, 3)):
+        mv, lp = R.sample_host(x[None], legal, [u])
+        assert mv[0] == want and abs(lp[0] - x[want]) < 1e-12
 
 
 # ---- the legal plane -------------------------------------------------------------------------------------------------
