@@ -66,6 +66,9 @@ SYMBOLS = {
     "bkt_reply2_update_tables": (_I, [_P, _P, _I, _P, _I, _I, _P, _I, _P, _P, _P]),
     "bkt_mm_sums": (_I, [_P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "bkt_balance_sums": (_I, [_P, _I, _U64, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P]),
+    "bkt_move_value_playouts": (_I, [_P, _I, _U64, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P]),
+    "bkt_move_value_scratch_bytes": (_Z, [_I]),
+    "bkt_move_value_update": (_I, [_P, _P, _I, _P, _I, _I, _P, _P, _P, _I, _I, _P, _P]),
 }
 MAX_BATCH = 65536          # BKT_MAX_BATCH
 PRECISIONS = ("fp32", "bf16")
@@ -81,6 +84,8 @@ MM_G_MIN, MM_G_MAX = 1 << 8, 1 << 24   # BKT_MM_G_MIN, BKT_MM_G_MAX: the domain 
 BALANCE_Q = 24             # BKT_BALANCE_Q: a share of the draw is booked in units of 2^-24
 BALANCE_MAX_ROWS = 16384   # BKT_BALANCE_MAX_ROWS
 BALANCE_MAX_COEF = 4096    # BKT_BALANCE_MAX_COEF
+MOVE_VALUE_MAX_K = 65536   # BKT_MOVE_VALUE_MAX_K
+MOVE_VALUE_MAX_LIMIT = 1 << 30   # BKT_MOVE_VALUE_MAX_LIMIT
 
 _lib = None
 
@@ -663,6 +668,62 @@ def reply2_update(pos, moves, won, records, playouts, replies2, scratch=None, sl
                                  _dev(won, "won", (records * playouts,), torch.uint8), records, playouts, *tables,
                                  _dev(scratch, "scratch", dtype=torch.uint8), _stream(moves)), name)
     return replies2
+
+
+def _move_values(values, dev, what):
+    if not isinstance(values, torch.Tensor) or values.device != dev:
+        raise ValueError(f"values must be int16 [2, 81] (the bits of the uint16 entries) on the device of {what}")
+    return _dev(values, "values", (2, 81), torch.int16)
+
+
+def move_value_playouts(pos, seed, counters, table, tactics, values, max_plies, over=None, history=True, replies=None,
+                        replies2=None):
+    """tactical_playouts whose weights are multiplied by a per-(colour, point) factor (bkt_move_value_playouts;
+    include/bokego_train.h has the rule): values int16 [2,81] on the device of pos, the bits of the uint16 entries (256:
+    neutral), read only; table and tactics: tactical_playouts' tables, each of which may be None.  replies: None or
+    reply_playouts' table, uint8 [2,81]; replies2: None or reply2_playouts' table, uint8 [2,82,81]; at most one of the two
+    (ValueError): a playable reply overrules the draw as in those calls."""
+    weights = _weight_tables(pos, table, tactics)
+    v = _move_values(values, pos.device, "pos")
+    if replies is not None and replies2 is not None:
+        raise ValueError("at most one of replies and replies2 may be given: a pair table contains the single one")
+    r1 = None if replies is None else _reply_tables(replies, None, _pos_batch(pos), pos.device, "pos")[1][0]
+    r2 = None if replies2 is None else _reply2_table(replies2, pos.device, "pos")
+    return _playouts("bkt_move_value_playouts", pos, seed, counters, (*weights, v, r1, r2), max_plies, over, history)
+
+
+def move_value_update(pos, moves, won, records, playouts, counts, values, lut, k, limit, scratch=None):
+    """Fold a batch of playouts into a move-value table, in place (bkt_move_value_update; include/bokego_train.h has the
+    rule): pos uint8 [records,192], the starting records (read only); moves and won as reply_update takes them; counts int64
+    [2,81,2], values int16 [2,81] and lut int16 [65] (the bits of the uint16 entries) on the device of moves; 1 <= k <=
+    MOVE_VALUE_MAX_K; limit 0 or 2..MOVE_VALUE_MAX_LIMIT; playouts * max_plies < 2^31.  scratch: None (allocated here) or a
+    uint8 tensor of at least bkt_move_value_scratch_bytes(records) bytes.  Two launches on the current stream; nothing
+    waits.  -> (counts, values)."""
+    records, playouts, max_plies = _amaf_args(moves, won, records, playouts)
+    if not isinstance(pos, torch.Tensor) or tuple(pos.shape) != (records, POS_BYTES) or pos.device != moves.device:
+        raise ValueError(f"pos must be [{records}, {POS_BYTES}] on the device of moves")
+    k, limit = int(k), int(limit)
+    if not 1 <= k <= MOVE_VALUE_MAX_K:
+        raise ValueError(f"k must be 1..{MOVE_VALUE_MAX_K}, got {k}")
+    if limit != 0 and not 2 <= limit <= MOVE_VALUE_MAX_LIMIT:
+        raise ValueError(f"limit must be 0 or 2..{MOVE_VALUE_MAX_LIMIT}, got {limit}")
+    if playouts * max_plies >= 2 ** 31:
+        raise ValueError("playouts * max_plies must be below 2^31: a record's partial counts are int32")
+    for t, name in ((counts, "counts"), (lut, "lut")):
+        if not isinstance(t, torch.Tensor) or t.device != moves.device:
+            raise ValueError(f"{name} must be on the device of moves")
+    v = _move_values(values, moves.device, "moves")
+    need = load().bkt_move_value_scratch_bytes(records)
+    if scratch is None:
+        scratch = torch.empty((need,), dtype=torch.uint8, device=moves.device)
+    elif not isinstance(scratch, torch.Tensor) or scratch.device != moves.device or scratch.dim() != 1 or scratch.numel() < need:
+        raise ValueError(f"scratch must be uint8 [>= {need}] on the device of moves")
+    _check(load().bkt_move_value_update(_dev(pos, "pos", dtype=torch.uint8), _dev(moves, "moves", dtype=torch.int16), max_plies,
+                                        _dev(won, "won", (records * playouts,), torch.uint8), records, playouts,
+                                        _dev(counts, "counts", (2, 81, 2), torch.int64), v, _dev(lut, "lut", (65,), torch.int16),
+                                        k, limit, _dev(scratch, "scratch", dtype=torch.uint8), _stream(moves)),
+           "bkt_move_value_update")
+    return counts, values
 
 
 def mm_strengths(g, entries, name, device=None):

@@ -203,3 +203,5 @@ extern "C" int bkt_reply2_update_tables(const void* pos, const int16_t* moves, i
     hipLaunchKernelGGL(gamepairs_finish_kernel, dim3((entries + 255) / 256), dim3(256), 0, s, keys, flags, replies2, entries);
     return hipGetLastError() == hipSuccess ? BKT_OK : BKT_ERR_HIP;
 }
+
+#include "bk_playout_mast.hip" // MAST playouts, a per-(colour, point) factor the playouts learn: text likewise

@@ -193,6 +193,9 @@ class _GTPProtocol:
         replies = getattr(getattr(self, "evaluator", None), "replies", None)
         if replies is not None:                                      # --playout-replies: a new game learns its own replies
             replies.clear()
+        move_values = getattr(getattr(self, "evaluator", None), "move_values", None)
+        if move_values is not None:                                  # --playout-move-values: and its own move values
+            move_values.clear()
         return True, ""
 
     def _c_komi(self, args, turn):

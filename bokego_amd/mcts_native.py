@@ -152,7 +152,11 @@ class NativeMCTS:
     with it an empty table, on first use;
     `playout_reply_pairs=True` (with playout_value): the same with a table keyed by the last two moves, a ReplyTable2 whose
     plane 81 is the single-move table (untuned); with or without playout_replies, since pairs contain singles.
-    Determinism, deepcopy and pickle are as for playout_replies."""
+    Determinism, deepcopy and pickle are as for playout_replies;
+    `playout_move_values=tau` (> 0, with playout_value): MAST -- the evaluator keeps a movevalues.MoveValueTable of that
+    temperature, `evaluator.move_values`, a win rate per colour and point that the playouts of this search's requests draw
+    with and update in submit order (untuned); with or without either reply table.  Determinism, deepcopy and
+    pickle are as for playout_replies."""
 
     def __init__(self, root=None, policy_net=None, value_net=None, **kwargs):
         # OPT-IN, not the reference's search: playout_value=N > 0 -- no value net; a leaf's value is the share of N uniformly
@@ -306,8 +310,9 @@ class NativeMCTS:
             if k not in self._NOT_STATE:
                 setattr(new, k, copy.deepcopy(v, memo))
         new.policy_net, new.value_net, new.evaluator = self.policy_net, self.value_net, self.evaluator
-        if getattr(self, "playout_replies", False) or getattr(self, "playout_reply_pairs", False):
-            # a reply table of its own, empty (class docstring)
+        if getattr(self, "playout_replies", False) or getattr(self, "playout_reply_pairs", False) \
+                or getattr(self, "playout_move_values", 0.0):
+            # a reply table, a move-value table of its own, empty (class docstring)
             new.evaluator = new._playout_evaluator(self.policy_net)
             new.evaluator.komi = self.evaluator.komi
         new._adopt(self._pool.snapshot(0), self._cap)

@@ -6,7 +6,8 @@ and NativeMCTS as keywords, declared once, checked once, and turned into the key
     PlayoutOptions.from_keywords(kwargs)        the record of NativeMCTS's keywords; TypeError / ValueError
     .search_keywords()                          the keywords of NativeMCTS / NativeGTP: only the options that are set
     .evaluator_keywords()                       the keywords of rollout.PlayoutEvaluator
-    .name_suffix()                              what match calls such an engine: -mc64-pat-amaf1-rave4-lgr (-lgr2 with pairs)
+    .name_suffix()                              what match calls such an engine: -mc64-pat-amaf1-rave4-lgr (-lgr2 with pairs,
+                                                -mast with move values)
 
 Nothing here imports torch or rollout: a front end parses its command line before it loads either.
 """
@@ -46,7 +47,13 @@ FLAGS = {  # field -> (flag, what argparse needs, help)
     "playout_reply_pairs": ("--playout-reply-pairs", dict(action="store_true"),
                             "with --playout-value: as --playout-replies with replies keyed by the last two moves as well, the "
                             "single-move table being the fallback (LGRF-2; untuned; default off, DESIGN 26)"),
+    "playout_move_values": ("--playout-move-values", dict(type=float, nargs="?", const=0.25, default=0.0, metavar="TAU"),
+                            "with --playout-value: MAST -- the playouts of a search learn a win rate per colour and point from "
+                            "each other, and a point's weight in their draw is multiplied by exp((rate - 1/2) / TAU) (0.25 when "
+                            "no value is given, with 16 virtual plays and counts halved at 16384: plausible and untuned; "
+                            "default 0: off, DESIGN 30)"),
 }
+LATE = ("playout_move_values", "playout_reply_pairs", "playout_replies")   # the fields that are none of the constructor's
 
 
 @dataclasses.dataclass
@@ -62,6 +69,9 @@ class PlayoutOptions:
     playout_pattern_prior: float = 0.0  # 0: no pattern term in the prior
     prior_patterns: object = None       # the tables of that term; None: the playouts' own
     prior_tactics: object = None
+    # 0: no move-value table, else its temperature tau; in playout_replies' form, and in front of the two reply
+    # fields so that the order of the fields before and the last two are what they were.
+    playout_move_values: float = dataclasses.field(default=0.0, init=False)
     # False: no replies keyed by the last two moves; in playout_replies' form, and in front of it so that the
     # order of the fields before and the last field are what they were.
     playout_reply_pairs: bool = dataclasses.field(default=False, init=False)
@@ -82,9 +92,10 @@ class PlayoutOptions:
         """rave=False, replies=False: a front end whose one evaluator serves many games at once (selfplay) takes neither --
         there are no per-game RAVE records there, and the games would mix their reply tables.  selfplay has two flags of
         its own instead, --game-rave and --game-replies (RAVE records and a reply table per game), and
-        --game-reply-pairs (a pair reply table per game)."""
+        --game-reply-pairs (a pair reply table per game).  The move-value table goes with the reply tables: one
+        per search, so not where one evaluator serves many games."""
         for field, (flag, kw, text) in FLAGS.items():
-            if (rave or field != "playout_rave") and (replies or field not in ("playout_replies", "playout_reply_pairs")):
+            if (rave or field != "playout_rave") and (replies or field not in LATE):
                 if field == "playout_value" and not (rave and replies):
                     text += "; RAVE and last-good-reply tables are per game here: --game-rave, --game-replies, --game-reply-pairs"
                 parser.add_argument(flag, help=text, **kw)
@@ -92,11 +103,10 @@ class PlayoutOptions:
     @classmethod
     def from_args(cls, parser, args):
         """The record of a parsed command line; a refused combination ends in parser.error, which names the flag."""
-        late = ("playout_replies", "playout_reply_pairs")
-        self = cls(**{f: getattr(args, f) for f in FLAGS if hasattr(args, f) and f not in late})
-        for f in late:
+        self = cls(**{f: getattr(args, f) for f in FLAGS if hasattr(args, f) and f not in LATE})
+        for f in LATE:
             if hasattr(args, f):
-                setattr(self, f, bool(getattr(args, f)))
+                setattr(self, f, type(getattr(cls, f))(getattr(args, f)))
         self.check(lambda field: FLAGS[field][0], lambda kind, text: parser.error(text), command_line=True)
         return self
 
@@ -114,6 +124,7 @@ class PlayoutOptions:
                    kwargs.get("prior_patterns"), kwargs.get("prior_tactics"))
         self.playout_replies = bool(kwargs.get("playout_replies"))
         self.playout_reply_pairs = bool(kwargs.get("playout_reply_pairs"))
+        self.playout_move_values = float(kwargs.get("playout_move_values") or 0.0)
         self.check(str, fail)
         return self
 
@@ -123,8 +134,10 @@ class PlayoutOptions:
         value, prior = name("playout_value"), name("playout_prior")
         if self.playout_value < 0:
             fail(ValueError, f"{value} must not be negative")
+        if not 0.0 <= self.playout_move_values < float("inf"):               # (before `given`: a NaN is truthy)
+            fail(ValueError, f"{name('playout_move_values')} must be a finite number, 0 or more")
         for field in ("playout_patterns", "playout_tactics", "playout_prior", "playout_rave", "playout_replies",
-                      "playout_reply_pairs"):
+                      "playout_reply_pairs", "playout_move_values"):
             if self.given(field) and not self.playout_value:
                 fail(TypeError, f"{name(field)} goes with the playouts of {value}: it needs {value}")
         if not 0.0 <= self.playout_prior <= 1.0:
@@ -149,7 +162,7 @@ class PlayoutOptions:
         """The keywords of NativeMCTS / NativeGTP: the options that are set, and no others."""
         more = {f: getattr(self, f) for f in ("playout_value", "playout_patterns", "playout_tactics", "playout_prior",
                                               "playout_rave", "playout_criticality", "playout_replies",
-                                              "playout_reply_pairs") if self.given(f)}
+                                              "playout_reply_pairs", "playout_move_values") if self.given(f)}
         if self.playout_pattern_prior:
             more.update(playout_pattern_prior=self.playout_pattern_prior, prior_patterns=self.prior_patterns,
                         prior_tactics=self.prior_tactics)
@@ -164,6 +177,8 @@ class PlayoutOptions:
             more["rave"] = True
         if self.playout_replies or self.playout_reply_pairs:
             more["replies"] = 2 if self.playout_reply_pairs else True        # pairs contain singles
+        if self.playout_move_values:
+            more["move_values"] = self.playout_move_values
         if self.playout_pattern_prior:
             more.update(pattern_prior=self.playout_pattern_prior, prior_patterns=self.prior_patterns,
                         prior_tactics=self.prior_tactics)
@@ -171,9 +186,10 @@ class PlayoutOptions:
 
     def name_suffix(self):
         """-mc64, then -pat with a playout table, -amaf, -rave, -crit, -pp with their parameters for the terms that are on, and
-        -lgr with the reply table, -lgr2 when it is keyed by the last two moves."""
+        -lgr with the reply table, -lgr2 when it is keyed by the last two moves, -mast with the move-value table."""
         name = f"-mc{self.playout_value}" + ("-pat" if self.given("playout_patterns") or self.given("playout_tactics") else "")
         for tag, x in (("amaf", self.playout_prior), ("rave", self.playout_rave), ("crit", self.playout_criticality),
                        ("pp", self.playout_pattern_prior)):
             name += f"-{tag}{x:g}" if x else ""
-        return name + ("-lgr2" if self.playout_reply_pairs else "-lgr" if self.playout_replies else "")
+        name += "-lgr2" if self.playout_reply_pairs else "-lgr" if self.playout_replies else ""
+        return name + ("-mast" if self.playout_move_values else "")

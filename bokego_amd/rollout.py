@@ -75,6 +75,12 @@ DESIGN 26); PlayoutEvaluator(replies=2) keeps one.  A ReplyTables2 with slots= i
     python -m bokego_amd.rollout --sgf FILE [--move K] --random --reply-pairs [-n 256] [--chunk 16]   # the same with a ReplyTable2:
                                                                           # replies keyed by the last two moves
 
+move_values= (a MoveValueTable, bokego_amd/movevalues.py) is the soft counterpart (MAST): a win rate per colour
+and point, learned from the same histories and multiplied into the draw's weights (bkt_move_value_playouts,
+bkt_move_value_update), alone or under either reply table; PlayoutEvaluator(move_values=True) keeps one (opt-in, untuned).
+
+    python -m bokego_amd.rollout --sgf FILE [--move K] --random --move-values [-n 256] [--chunk 16]   # what the table learned
+
 rules="host" is one loop (_playout_host) on the host rules with the same draws (lockstep's play_host, features_batch
 and area_score_host, bk_pos_is_legal, bk_pos_possible_eye, lockstep.sample_host in float64): the reference the tests
 compare the device with.  With engine=None it needs no GPU.
@@ -91,6 +97,7 @@ from . import _trainlib as T
 from . import go
 from . import lockstep as L
 from .lockstep import playable_host, record_turns  # noqa: F401  (public here: see __all__)
+from .movevalues import MoveValueTable, move_value_update_host, move_value_weights
 from .replies import (ReplyTable, ReplyTable2, ReplyTables, ReplyTables2, reply2_moves, reply2_plies_of, reply2_update_host, reply_moves, reply_plies_of,
                       reply_update_host, slots_of)
 
@@ -339,7 +346,7 @@ def select_index(x0, n):
 
 
 
-def _random_host(pos, key, ctr, max_plies, komi, history, table=None, tactics=None, replies=None, slots=None):
+def _random_host(pos, key, ctr, max_plies, komi, history, table=None, tactics=None, replies=None, slots=None, move_values=None):
     """random_playouts on the host: the select_index-th playable point in ascending order, a pass when there is none; with
     a table (a patterns.PatternTable), patterns.select_weighted on the entries of the points' pattern indices; with tactics
     (a tactics.TacticTable), tactics.select_tactical on those entries (or none) and the entries of the tactical codes.
@@ -348,7 +355,9 @@ def _random_host(pos, key, ctr, max_plies, komi, history, table=None, tactics=No
     the number of plies the table decided.  slots: with tables [count,2,81] (a ReplyTables), the table of every row.
     With a ReplyTable2 the use rule is reply2_moves': the move two plies back is kept per row across the plies here (none at
     ply 0, the record's last move at ply 1), and reply_pair_plies is the pair entries' share of reply_plies; with a
-    ReplyTables2 likewise, slots naming the pair table of every row."""
+    ReplyTables2 likewise, slots naming the pair table of every row.
+    move_values (a MoveValueTable, read only here): the weights of the draw above -- 256 everywhere without
+    tables -- go through movevalues.move_value_weights with the values as they stand on entry and the colour to move."""
     def choose(k, recs, live, ok, x0):
         n = ok.sum(1)
         pick = np.argmax(np.cumsum(ok, 1) > select_index(x0, n).astype(np.int64)[:, None], 1)
@@ -362,10 +371,20 @@ def _random_host(pos, key, ctr, max_plies, komi, history, table=None, tactics=No
         entries = None if table is None else table.entries(PT.codes_host(part))
         return TC.select_tactical(x0, entries, tactics.entries(TC.codes_host(part)), ok)
 
-    if table is not None:
+    def choose_valued(k, recs, live, ok, x0):
+        part = recs[live]
+        entries = None if table is None else table.entries(PT.codes_host(part))
+        t = np.full(ok.shape, TC.NEUTRAL, np.uint16) if tactics is None else tactics.entries(TC.codes_host(part))
+        return PT.select_weighted(x0, move_value_weights(TC.combine(entries, t), values, record_turns(part) & 1), ok)
+
+    if table is not None or move_values is not None:
         from . import patterns as PT
-    if tactics is not None:
+    if tactics is not None or move_values is not None:
         from . import tactics as TC
+    if move_values is not None:
+        values = move_values.values.copy()
+        choose = choose_valued
+    elif tactics is not None:
         choose = choose_tactical
     elif table is not None:
         choose = choose_weighted
@@ -408,7 +427,7 @@ def _tactics(tactics):
 
 
 def random_playouts(pos, seed, counters=None, max_plies=MAX_PLIES, rules="device", komi=L.KOMI, history=True, device=None,
-                    patterns=None, tactics=None, replies=None, slots=None):
+                    patterns=None, tactics=None, replies=None, slots=None, move_values=None):
     """Play the records pos (uint8 [G,192], numpy or a tensor; not modified) to the end of the game with uniformly random
     eye-safe moves -> Finished, the fields finish_games returns (moves is None with history=False; no min_margin: nothing
     is rounded).  rules="device": one bkt_random_playouts launch per T.MAX_BATCH rows, then bkt_area_score.  rules="host":
@@ -426,10 +445,16 @@ def random_playouts(pos, seed, counters=None, max_plies=MAX_PLIES, rules="device
     game whose score is > 0.  The games then depend on the table too.
     slots: with a ReplyTables (a table per game of a batch), an int array [G], the table of every game: required
     with a ReplyTables and refused with a ReplyTable.  A ReplyTables2 takes them likewise (a pair table per game),
-    and a ReplyTable2 refuses them."""
+    and a ReplyTable2 refuses them.
+    move_values: None, or a movevalues.MoveValueTable (MAST): every game here draws with the table's values as
+    they stand multiplied into the weights (bkt_move_value_playouts, with replies= composed as above), and the table is
+    then updated in place with all G games, after the reply table if any (bkt_move_value_update).  Not with slots=
+    (TypeError): there are no move-value tables per game."""
     L.check_rules(rules)
     table, tactics = _table(patterns), _tactics(tactics)
     slots = _check_replies(replies, slots, len(pos))
+    _check_move_values(move_values, slots)
+    learns = replies is not None or move_values is not None
     max_plies = int(max_plies)
     if not 1 <= max_plies <= 1024:
         raise ValueError("max_plies must be 1..1024 (BKT_MAX_PLAYOUT_PLIES)")
@@ -439,23 +464,31 @@ def random_playouts(pos, seed, counters=None, max_plies=MAX_PLIES, rules="device
         counters = default_counters(G, record_turns(_numpy(pos)))
     key = L.seed_u64(seed)
     if rules == "host":
-        fin = _random_host(pos, key, L.counters_to_host(counters, G), max_plies, komi, history or replies is not None, table,
-                           tactics, replies, slots)
-        if replies is not None:
+        fin = _random_host(pos, key, L.counters_to_host(counters, G), max_plies, komi, history or learns, table,
+                           tactics, replies, slots, move_values)
+        if learns:
             start = np.asarray(_numpy(pos))                               # (moves is cut to the longest game: the same fold)
-            _update_host(replies, start, fin.moves, (fin.score > 0) == L.black_to_move(start), G, 1, slots)
-            fin.moves = fin.moves if history else None
+            won, moves = (fin.score > 0) == L.black_to_move(start), fin.moves
+            if replies is not None:
+                _update_host(replies, start, moves, won, G, 1, slots)
+            if move_values is not None:
+                move_value_update_host(move_values, start, moves, won, G, 1)
+            fin.moves = moves if history else None
         return fin
     dev = _device(device, None, pos)
     start = L.records_to_device(pos, dev, clone=False)
     pos = start.clone()
     ctr = L.counters_to_device(counters, G, dev, clone=False)
     slots = _slots_device(slots, dev)
-    over, plies, moves, status = _play_random_device(pos, key, ctr, max_plies, history or replies is not None, table, tactics,
-                                                     replies, slots)
+    over, plies, moves, status = _play_random_device(pos, key, ctr, max_plies, history or learns, table, tactics,
+                                                     replies, slots, move_values)
     score, owner = _area_score_device(pos, komi, True)
-    if replies is not None:
-        _update_device(start, moves, ((score > 0) == L.black_to_move(start)).to(torch.uint8), G, 1, replies, slots)
+    if learns:
+        won = ((score > 0) == L.black_to_move(start)).to(torch.uint8)
+        if replies is not None:
+            _update_device(start, moves, won, G, 1, replies, slots)
+        if move_values is not None:
+            _update_move_values_device(start, moves, won, G, 1, move_values)
     _check_status(status, "selected")
     fin = _finished(pos, moves if history else None, plies.cpu().numpy().astype(np.int64), over.cpu().numpy() != 0,
                     score.cpu().numpy(), owner.cpu().numpy())
@@ -476,6 +509,20 @@ def _update_device(recs, moves, won, records, playouts, replies, slots):
     if isinstance(replies, _PAIRS):
         return T.reply2_update(recs, moves, won, records, playouts, replies.device(recs.device), slots=slots)
     return T.reply_update(recs, moves, won, records, playouts, replies.device(recs.device), slots=slots)
+
+
+def _update_move_values_device(recs, moves, won, records, playouts, move_values):
+    """bkt_move_value_update on the current stream: the table's tensors on the device of recs are the table from here on."""
+    counts, values, lut = move_values.device(recs.device)
+    return T.move_value_update(recs, moves, won, records, playouts, counts, values, lut, move_values.k, move_values.limit)
+
+
+def _check_move_values(move_values, slots):
+    """move_values= of the callers here: None or a MoveValueTable, and never with slots= (there are no tables per game)."""
+    if move_values is not None and not isinstance(move_values, MoveValueTable):
+        raise TypeError("move_values must be a MoveValueTable (it is updated in place) or None")
+    if move_values is not None and slots is not None:
+        raise TypeError("move_values= keeps one table for all records: not with slots= (a table per game)")
 
 
 _PAIRS = (ReplyTable2, ReplyTables2)                                      # the tables keyed by the last two moves
@@ -504,12 +551,18 @@ def _per_batch(call, *rows):
     return tuple(None if col[0] is None else torch.cat(col) for col in zip(*parts))
 
 
-def _play_random_device(pos, key, ctr, max_plies, history, table=None, tactics=None, replies=None, slots=None):
+def _play_random_device(pos, key, ctr, max_plies, history, table=None, tactics=None, replies=None, slots=None, move_values=None):
     """pos uint8 [G,192] and ctr int32 [G,4] on the device; pos is played on in place; table: None or a PatternTable;
     tactics: None or a TacticTable; replies: None or a ReplyTable, which every launch reads as it stands, or a ReplyTables or
-    a ReplyTables2 with slots int32 [G] on the device, the table of every row.
+    a ReplyTables2 with slots int32 [G] on the device, the table of every row; move_values: None or a MoveValueTable, whose
+    values every launch reads as they stand (bkt_move_value_playouts, with a ReplyTable or a ReplyTable2 put in; no slots).
     -> (over uint8 [G], plies int32 [G], moves int16 [G,max_plies] or None, status int32 [G]), T.MAX_BATCH rows per launch."""
     w, tac = (None if t is None else t.device(pos.device) for t in (table, tactics))
+    if move_values is not None:
+        put = {} if replies is None else {"replies2" if isinstance(replies, _PAIRS) else "replies": replies.device(pos.device)}
+        values = move_values.device(pos.device)[1]
+        return _per_batch(lambda p, c: T.move_value_playouts(p, key, c, w, tac, values, max_plies, history=history, **put),
+                          pos, ctr)
     if replies is not None:
         play = T.reply2_playouts if isinstance(replies, _PAIRS) else T.reply_playouts
         tables = (w, tac, replies.device(pos.device))
@@ -549,7 +602,7 @@ def _value_of_wins(w, n):
 
 
 def _playouts(recs, n, key, rules, komi=L.KOMI, table=None, tactics=None, max_plies=MAX_PLIES, score=True, history=False,
-              final=False, counted=0, sides=1, owned=0, replies=None, slots=None):
+              final=False, counted=0, sides=1, owned=0, replies=None, slots=None, move_values=None):
     """The one playout run: n playouts of each record of recs -- a uint8 [R,192] tensor on the device with
     rules="device", where nothing here waits for it; an array with "host", the mirror -- and what is asked of them, as a
     namespace whose fields are None when they were not asked for:
@@ -571,23 +624,30 @@ def _playouts(recs, n, key, rules, komi=L.KOMI, table=None, tactics=None, max_pl
                                      the launches are bkt_reply2_playouts and bkt_reply2_update, slots is
                                     refused, and reply_pair_plies is the pair entries' share of reply_plies (host rules).
                                     With a ReplyTables2 slots is required again, and the launches are
-                                    bkt_reply2_playouts_tables and bkt_reply2_update_tables."""
+                                    bkt_reply2_playouts_tables and bkt_reply2_update_tables.
+    move_values=                    a MoveValueTable: every playout draws with its values as they stand
+                                    (bkt_move_value_playouts, with history; replies= a ReplyTable or a ReplyTable2 composes),
+                                    and after the score and the reply update one bkt_move_value_update folds all R * n of
+                                    them into it, in place and on the same stream.  It needs score=True, and refuses slots."""
     R, host = len(recs), rules == "host"
     counted, owned = (R if x is True else int(x) for x in (counted, owned))
     slots = _check_replies(replies, slots, R)
+    _check_move_values(move_values, slots)
     if replies is not None and not score:
         raise ValueError("a reply table learns from who won each playout: it needs the scored run (not playout_ownership's)")
-    history = history or counted > 0 or replies is not None
+    if move_values is not None and not score:
+        raise ValueError("a move-value table learns from who won each playout: it needs the scored run (not playout_ownership's)")
+    history = history or counted > 0 or replies is not None or move_values is not None
     if host:
         recs = np.array(_numpy(recs), np.uint8, order="C")
         fin = _random_host(np.repeat(recs, n, 0), key, value_counters(recs, n), max_plies, komi, history, table, tactics, replies,
-                           None if slots is None else np.repeat(slots, n))
+                           None if slots is None else np.repeat(slots, n), move_values)
         pos, moves, black_wins = fin.records, fin.moves, fin.score.reshape(R, n) > 0
     else:
         pos = recs.repeat_interleave(n, 0)                                 # a copy: the caller's records stay
         slots = _slots_device(slots, recs.device)
         moves = _play_random_device(pos, key, L.value_counters_device(recs, n), max_plies, history, table, tactics, replies,
-                                    None if slots is None else slots.repeat_interleave(n))[2]
+                                    None if slots is None else slots.repeat_interleave(n), move_values)[2]
         black_wins = _area_score_device(pos, komi, False).view(R, n) > 0 if score else None
     run = SimpleNamespace(value=None, wins=None, won=None, moves=moves, final=pos if final else None, played=None, won_at=None,
                           owner=None, reply_plies=None, reply_pair_plies=None)
@@ -600,6 +660,11 @@ def _playouts(recs, n, key, rules, komi=L.KOMI, table=None, tactics=None, max_pl
             _update_host(replies, recs, moves, run.won.reshape(-1), R, n, slots)
         else:
             _update_device(recs, moves, run.won.reshape(-1).to(torch.uint8), R, n, replies, slots)
+    if move_values is not None:                                            # ... then the move values, on the same stream
+        if host:
+            move_value_update_host(move_values, recs, moves, run.won.reshape(-1), R, n)
+        else:
+            _update_move_values_device(recs, moves, run.won.reshape(-1).to(torch.uint8), R, n, move_values)
     if counted:
         reduce = ((T.amaf_counts, T.amaf_counts_sides), (amaf_counts_host, amaf_counts_sides_host))[host][sides - 1]
         won = run.won[:counted].reshape(-1)
@@ -613,7 +678,7 @@ def _playouts(recs, n, key, rules, komi=L.KOMI, table=None, tactics=None, max_pl
     return run
 
 
-def _run(recs, n, seed, rules, komi, device, patterns, tactics, replies=None, slots=None, **ask):
+def _run(recs, n, seed, rules, komi, device, patterns, tactics, replies=None, slots=None, move_values=None, **ask):
     """What playout_value, playout_amaf and playout_ownership share: the checks, the upload and _playouts(**ask)."""
     L.check_rules(rules)
     table, tactics = _table(patterns), _tactics(tactics)
@@ -621,18 +686,20 @@ def _run(recs, n, seed, rules, komi, device, patterns, tactics, replies=None, sl
     _check_records(recs)
     if rules == "device":
         recs = L.records_to_device(recs, _device(device, None, recs), clone=False)
-    return _playouts(recs, n, L.seed_u64(seed), rules, komi, table, tactics, replies=replies, slots=slots, **ask)
+    return _playouts(recs, n, L.seed_u64(seed), rules, komi, table, tactics, replies=replies, slots=slots,
+                     move_values=move_values, **ask)
 
 
 def playout_value(recs, n, seed, rules="device", komi=L.KOMI, device=None, patterns=None, tactics=None, replies=None,
-                  slots=None):
+                  slots=None, move_values=None):
     """The Monte-Carlo value of each record, float32 [R] (numpy): (2 w - n) / n, w = the number of n uniformly random
     eye-safe playouts (random_playouts, capped at MAX_PLIES and then scored as they stand) that the side to move wins --
     black wins iff the area score is > 0.  A pure function of the record, `seed` and `n` (value_counters): the row index
     and the rest of the batch do not enter.  recs: uint8 [R,192], numpy or a tensor.  patterns, tactics: as random_playouts.
     replies: None, or a ReplyTable the playouts read and this call then updates in place with all R * n of them:
-    the value is then a function of the table as well.  slots: with a ReplyTables, the table of every record (random_playouts)."""
-    return _numpy(_run(recs, n, seed, rules, komi, device, patterns, tactics, replies, slots).value)
+    the value is then a function of the table as well.  slots: with a ReplyTables, the table of every record (random_playouts).
+    move_values: None, or a MoveValueTable the playouts draw with and this call then updates in place."""
+    return _numpy(_run(recs, n, seed, rules, komi, device, patterns, tactics, replies, slots, move_values).value)
 
 
 class Amaf:
@@ -693,16 +760,16 @@ def amaf_counts_sides_host(moves, won, records, playouts):
 
 
 def playout_amaf(recs, n, seed, rules="device", komi=L.KOMI, device=None, patterns=None, tactics=None, sides=1, replies=None,
-                 slots=None):
+                 slots=None, move_values=None):
     """playout_value's n playouts of each record with what else they tell -> Amaf: the value (the history does not enter a
     game: the same bits), the wins, and the all-moves-as-first counts of every point (amaf_counts_host has the definition).
     rules="device": the playout launches with their history, `won` built in torch, one bkt_amaf_counts; rules="host": the
     mirror end to end, the same integers.  recs, patterns, tactics: as playout_value.
     sides=2: the counts of both sides, [R,2,81] (one bkt_amaf_counts_sides; amaf_counts_sides_host); value and wins are the
-    same either way.  replies, slots: as playout_value."""
+    same either way.  replies, slots, move_values: as playout_value."""
     if sides not in (1, 2):
         raise ValueError("sides must be 1 or 2")
-    run = _run(recs, n, seed, rules, komi, device, patterns, tactics, replies, slots, counted=True, sides=sides)
+    run = _run(recs, n, seed, rules, komi, device, patterns, tactics, replies, slots, move_values, counted=True, sides=sides)
     return Amaf(_numpy(run.value), _numpy(run.wins).astype(np.int32), _numpy(run.played), _numpy(run.won_at), n)
 
 
@@ -770,13 +837,14 @@ def owner_counts_host(final_recs, records, playouts, komi=L.KOMI):
     return black, white, agree, hist, bw.reshape(records, playouts).sum(1).astype(np.int32)
 
 
-def playout_ownership(recs, n, seed, rules="device", komi=L.KOMI, device=None, patterns=None, tactics=None, replies=None):
+def playout_ownership(recs, n, seed, rules="device", komi=L.KOMI, device=None, patterns=None, tactics=None, replies=None,
+                      move_values=None):
     """playout_value's n playouts of each record -- the same counters, draws and cap -- with what their final boards tell
     -> Ownership: the value (the same bits), the wins, and the ownership, agreement and margin counts of every record
     (owner_counts_host has the definition).  rules="device": the playout launch without history and one bkt_owner_counts;
     rules="host": the mirror end to end, the same integers.  recs, patterns, tactics: as playout_value.
-    replies must be None: this run launches no score, and a reply table learns from who won (ValueError)."""
-    run = _run(recs, n, seed, rules, komi, device, patterns, tactics, replies, score=False, owned=True)
+    replies and move_values must be None: this run launches no score, and either table learns from who won (ValueError)."""
+    run = _run(recs, n, seed, rules, komi, device, patterns, tactics, replies, move_values=move_values, score=False, owned=True)
     return Ownership(_numpy(run.value), _numpy(run.wins).astype(np.int32), *(_numpy(c) for c in run.owner), n)
 
 
@@ -948,6 +1016,12 @@ class PlayoutEvaluator:
     pair_games=G (default None: exactly the above; without replies= and games=, TypeError with either): `.replies` is a
     ReplyTables2(G), a pair table per game, and submit takes games= as with games=G; one bkt_reply2_playouts_tables and one
     bkt_reply2_update_tables serve all games of a request.  A one-game pool is then replies=2 bit for bit.
+    move_values=True or a temperature tau > 0 (default False: exactly the above, the same launches): the evaluator
+    owns one movevalues.MoveValueTable, created empty (tau; True: DEFAULT_TAU; k and limit the module's defaults),
+    `.move_values`, which reset_move_values() clears.  The playouts of every request draw with its values
+    (bkt_move_value_playouts, composed with replies=True or replies=2) and are folded into it after their score and the
+    reply update (bkt_move_value_update), all on the one stream.  A fresh table is neutral: the first request equals the
+    evaluator without the option bit for bit.  With games= or pair_games= it is a TypeError: no move-value tables per game.
     The engine is kept as `policy_engine`, not `engine`: selfplay.run_pools_native hands an evaluator's `engine` to the C
     step loop as its own bk_evaluator, which would compute no playouts -- this class goes through callback_evaluator."""
     wants_positions = True
@@ -955,8 +1029,13 @@ class PlayoutEvaluator:
 
     def __init__(self, engine, playouts=64, seed=0, rules="device", komi=L.KOMI, patterns=None, tactics=None, prior=0.0,
                  prior_k=PRIOR_K, prior_temperature=PRIOR_TEMPERATURE, rave=False, criticality=0.0, pattern_prior=0.0,
-                 prior_patterns=None, prior_tactics=None, replies=False, games=None, pair_games=None):
+                 prior_patterns=None, prior_tactics=None, move_values=False, replies=False, games=None, pair_games=None):
         L.check_rules(rules)
+        if move_values and (games is not None or pair_games is not None):
+            raise TypeError("move_values= keeps one table for all rows: it goes without games= and pair_games= (a table per game)")
+        # True: the default temperature; a number: tau; False, None or 0: no table
+        self.move_values = (MoveValueTable.empty() if move_values is True else MoveValueTable.empty(tau=move_values)) \
+            if move_values else None
         if pair_games is not None and (replies or games is not None):
             raise TypeError("pair_games= is the number of pair reply tables, a ReplyTables2: it goes without replies= and games=")
         if games is not None and not replies:
@@ -1018,7 +1097,8 @@ class PlayoutEvaluator:
         # rave: every row with its history, both sides counted, and the prior reads side 0 of the first rows of those counts
         run = _playouts(t, self.playouts, self.seed, self.rules, self.komi, self.patterns, self.tactics,
                         counted=len(recs) if self.rave else counted, sides=2 if self.rave else 1,
-                        owned=counted if self.criticality > 0.0 else 0, replies=self.replies, slots=games)
+                        owned=counted if self.criticality > 0.0 else 0, replies=self.replies, slots=games,
+                        move_values=self.move_values)
         if counted and self.pattern_prior > 0.0:                          # (the device's launch: nothing waits for it)
             weights = (move_weights_host if host else _move_weights_device)(t[:counted], self.prior_patterns, self.prior_tactics)
         return SimpleNamespace(ticket=ticket, run=run, n_policy=counted, weights=weights, recs=recs[:counted])
@@ -1028,6 +1108,12 @@ class PlayoutEvaluator:
         if self.replies is None:
             raise TypeError("this evaluator keeps no reply table: replies=True")
         self.replies.clear()
+
+    def reset_move_values(self):
+        """An empty move-value table again (move_values=True or tau): what a new game starts with."""
+        if self.move_values is None:
+            raise TypeError("this evaluator keeps no move-value table: move_values=True")
+        self.move_values.clear()
 
     def finish(self, handle, normalise=None):
         run, n = handle.run, handle.n_policy
@@ -1184,7 +1270,12 @@ def _parse(argv):
     ap.add_argument("--reply-pairs", action="store_true",
                     help="with --random: as --replies with a table keyed by the last two moves (LGRF-2): print the shares of "
                          "plies its pair entries and its single entries decided, and the occupancy of both parts")
-    ap.add_argument("--chunk", type=int, default=16, metavar="C", help="with --replies or --reply-pairs: playouts per chunk")
+    ap.add_argument("--move-values", action="store_true",
+                    help="with --random: play the playouts in chunks that learn a move-value table from each other (MAST), and "
+                         "print the share of its entries that were played, its smallest and largest value and its ten "
+                         "heaviest points instead of the score")
+    ap.add_argument("--chunk", type=int, default=16, metavar="C",
+                    help="with --replies, --reply-pairs or --move-values: playouts per chunk")
     ap.add_argument("--sides", type=int, default=1, choices=(1, 2),
                     help="with --amaf: 2 also prints the opponent's heaviest points (the two-sided counts RAVE is fed with)")
     ap.add_argument("-n", dest="n", type=int, default=256, help="playouts")
@@ -1203,6 +1294,9 @@ def _parse(argv):
     if args.reply_pairs and (not args.random or args.amaf or args.ownership or args.weights or args.replies):
         ap.error("--reply-pairs reads the one-launch playouts: it needs --random, and not --amaf, --ownership, --weights or "
                  "--replies (pairs contain singles)")
+    if args.move_values and (not args.random or args.amaf or args.ownership or args.weights or args.replies or args.reply_pairs):
+        ap.error("--move-values reads the one-launch playouts: it needs --random, and not --amaf, --ownership, --weights, "
+                 "--replies or --reply-pairs")
     if args.chunk < 1:
         ap.error("--chunk must be at least 1")
     if args.sides != 1 and not args.amaf:
@@ -1270,6 +1364,26 @@ def reply_pairs_report(recs, n, seed, chunk, rules="device", komi=L.KOMI, **kw):
             "pair_occupancy": table.pairs_occupancy(), "single_occupancy": table.singles().occupancy(), "black_win": black / n}
 
 
+def move_values_report(recs, n, seed, chunk, rules="device", komi=L.KOMI, **kw):
+    """reply_report with a MoveValueTable of the default parameters -> a dict: the plies played, the share of
+    the table's 162 entries with a play, its smallest and largest value, the ten heaviest entries and black's share of the
+    wins."""
+    table, plies, black = MoveValueTable.empty(), 0, 0
+    ctr = default_counters(n, np.repeat(record_turns(recs), n))
+    for s in range(0, n, chunk):
+        c = min(chunk, n - s)
+        fin = random_playouts(np.repeat(recs, c, 0), seed, counters=ctr[s:s + c], rules=rules, komi=komi, move_values=table, **kw)
+        plies += int(fin.plies.sum())
+        black += int((fin.score > 0).sum())
+    values, counts = table.values.reshape(-1), table.counts.reshape(162, 2)
+    return {"playouts": n, "chunk": chunk, "plies": plies, "played_share": table.occupancy() / 162,
+            "min_value": int(values.min()), "max_value": int(values.max()),
+            "heaviest": [{"colour": "bw"[e // 81], "move": go.unsquash(e % 81), "value": int(values[e]),
+                          "played": int(counts[e, 0]), "won": int(counts[e, 1])}
+                         for e in np.argsort(-values.astype(np.int64), kind="stable")[:10].tolist()],
+            "black_win": black / n}
+
+
 def main(argv=None):
     args = _parse(argv)
     game = sgf_position(args.sgf, args.move)
@@ -1302,6 +1416,11 @@ def main(argv=None):
         return
     if args.reply_pairs:
         print(json.dumps(reply_pairs_report(_as_records(game), args.n, args.seed, args.chunk, komi=args.komi,
+                                            patterns=args.patterns, tactics=args.tactics,
+                                            device=torch.device("cuda", args.device))))
+        return
+    if args.move_values:
+        print(json.dumps(move_values_report(_as_records(game), args.n, args.seed, args.chunk, komi=args.komi,
                                             patterns=args.patterns, tactics=args.tactics,
                                             device=torch.device("cuda", args.device))))
         return

@@ -528,6 +528,63 @@ int bkt_balance_sums(void *pos, int batch, uint64_t seed, const uint32_t *counte
                      const uint16_t *tactics, const int32_t *coef, int64_t *grad_p, int64_t *grad_t, int max_plies,
                      uint8_t *over, int32_t *plies, int16_t *moves, int32_t *status, void *stream);
 
+/* MAST playouts: per-move win rates the playouts of a search learn (the move-average sampling technique, Finnsson &
+ * Bjornsson 2008; bokego_amd/movevalues.py MoveValueTable).  A move-value table has three parts, all integers:
+ *   counts  int64 [2][81][2] on the device, 8-byte aligned: counts[c][m] = {played, won} of colour c (0 black = the mover
+ *           on an even turn, 1 white) on point m, 0 <= won <= played;
+ *   values  uint16 [2][81]: the factor of the draw's weight in units of 1/256, every entry >= 1, 256 = neutral;
+ *   lut     uint16 [65], every entry >= 1, supplied by the caller: the value of a win rate i / 64.
+ *
+ * Use (in a playout).  bkt_move_value_playouts is bkt_tactical_playouts' contract in every respect, draw included, except
+ * the weight.  table and tactics may each be NULL (a NULL tactics table is 256 everywhere, as in bkt_reply_playouts; both
+ * NULL: w_in = 256).  With w_in the weight that draw gives a playable point q (bkt_move_weights defines it) and c the
+ * colour to move at the ply,
+ *   w = min(2^24 - 1, max(1, ((uint64_t)w_in * values[c][q]) >> 8))
+ * so a row's sum S < 2^31 as before; the Philox word, t = ((x0 >> 8) * S) >> 24 and the prefix rule are the same.  With
+ * values all 256 the records, over, plies, moves and status are bkt_tactical_playouts' byte for byte, and with table NULL
+ * as well bkt_random_playouts'.  replies is NULL or bkt_reply_playouts' table, uint8 [2][81]; replies2 is NULL or
+ * bkt_reply2_playouts' table, uint8 [2][82][81], 4-byte aligned; at most one of the two may be given.  A playable reply
+ * overrules the draw exactly as in bkt_reply_playouts / bkt_reply2_playouts, and with values all 256 the games are those
+ * entry points' games byte for byte.  One launch; values is read before the first ply and staged in LDS.
+ * values == NULL, both reply tables given, a misaligned replies2, or any argument bkt_tactical_playouts refuses (but for the
+ * tables) returns BKT_ERR_ARG; nothing is launched and nothing is written.
+ *
+ * Update (after a batch of playouts).  pos [records, 192], moves [records * playouts, max_plies] and won[row] are exactly
+ * what bkt_reply_update takes: the starting records, and rows r * playouts .. (r + 1) * playouts - 1 belonging to record r.
+ * For a row and every ply t before the first entry <= BKT_MOVE_NONE (or max_plies), with m = moves[row, t] in 0..80:
+ *   c = (colour to move at record r) xor (t & 1);
+ *   counts[c][m].played += 1;   counts[c][m].won += ((won[row] != 0) == (t even)).
+ * Passes are skipped; an entry above 80 is ignored (entries are compared, never used as an index).  Every play counts:
+ * there is no first-play rule, so a point retaken after a capture counts again.  After all rows are added, every entry:
+ *   1. if limit > 0 and played >= limit, both fields are shifted right by the smallest s with played >> s < limit (old
+ *      counts are forgotten, so the table follows the search as the game moves on);
+ *   2. i = floor(64 * (2 * won + k) / (2 * (played + k))), in 0..64 because won <= played (k virtual plays at one half:
+ *      an entry never played has i = 32);
+ *   3. values[c][m] = lut[i].
+ * Every entry of values is written.  The sums do not depend on any order, and the shift depends only on the sequence of
+ * calls.  Two launches on `stream`, nothing waits on the host: the first, one workgroup per record, writes the record's
+ * int32 partial counts to scratch by plain stores; the second sums them over the records, adds them into counts and applies
+ * the shift and the lut.  Integers only, no atomics: the result is the definition's for every input, whatever the scheduling.
+ * No wrap.  A record's partial counts are at most playouts * max_plies < 2^31.  A call adds at most records * playouts *
+ * max_plies <= 2^24 * 2^10 = 2^34 to an entry.  With limit > 0 an entry is below limit <= 2^30 after every call, so it
+ * never exceeds 2^30 + 2^34.  With limit == 0 the counts only grow, and the caller keeps played below 2^54 (more than 2^20
+ * calls of the largest size): 64 * (2 * won + k) then stays below 2^62.
+ * scratch: bkt_move_value_scratch_bytes(records) = records * 1296 bytes on the device, 4-byte aligned (0 when records < 1);
+ * its contents on entry do not matter.
+ * Domain: 1 <= k <= BKT_MOVE_VALUE_MAX_K; limit == 0 or 2 <= limit <= BKT_MOVE_VALUE_MAX_LIMIT; playouts * max_plies <
+ * 2^31; no pointer but stream may be NULL; counts 8-byte aligned; otherwise bkt_reply_update's checks.  Else BKT_ERR_ARG:
+ * a refused call launches nothing and writes nothing. */
+#define BKT_MOVE_VALUE_NEUTRAL 256
+#define BKT_MOVE_VALUE_MAX_K 65536
+#define BKT_MOVE_VALUE_MAX_LIMIT (1 << 30)
+int bkt_move_value_playouts(void *pos, int batch, uint64_t seed, const uint32_t *counters, const uint16_t *table,
+                            const uint16_t *tactics, const uint16_t *values, const uint8_t *replies, const uint8_t *replies2,
+                            int max_plies, uint8_t *over, int32_t *plies, int16_t *moves, int32_t *status, void *stream);
+size_t bkt_move_value_scratch_bytes(int records);
+int bkt_move_value_update(const void *pos, const int16_t *moves, int max_plies, const uint8_t *won, int records, int playouts,
+                          int64_t *counts, uint16_t *values, const uint16_t *lut, int k, int limit, void *scratch,
+                          void *stream);
+
 #ifdef __cplusplus
 }
 #endif
