@@ -69,6 +69,9 @@ SYMBOLS = {
     "bkt_move_value_playouts": (_I, [_P, _I, _U64, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P]),
     "bkt_move_value_scratch_bytes": (_Z, [_I]),
     "bkt_move_value_update": (_I, [_P, _P, _I, _P, _I, _I, _P, _P, _P, _I, _I, _P, _P]),
+    "bkt_move_value_playouts_tables": (_I, [_P, _I, _U64, _P, _P, _P, _P, _P, _P, _I, _P, _I, _P, _P, _P, _P, _P]),
+    "bkt_move_value_tables_scratch_bytes": (_Z, [_I, _I]),
+    "bkt_move_value_update_tables": (_I, [_P, _P, _I, _P, _I, _I, _P, _P, _P, _I, _I, _I, _P, _P, _P]),
 }
 MAX_BATCH = 65536          # BKT_MAX_BATCH
 PRECISIONS = ("fp32", "bf16")
@@ -670,35 +673,68 @@ def reply2_update(pos, moves, won, records, playouts, replies2, scratch=None, sl
     return replies2
 
 
+MAX_MOVE_VALUE_TABLES = 4096   # BKT_MAX_MOVE_VALUE_TABLES
+
+
 def _move_values(values, dev, what):
     if not isinstance(values, torch.Tensor) or values.device != dev:
         raise ValueError(f"values must be int16 [2, 81] (the bits of the uint16 entries) on the device of {what}")
     return _dev(values, "values", (2, 81), torch.int16)
 
 
+def _move_value_tables(values, slots, n, dev, what):
+    """values int16 [tables,2,81] and slots int32 [n] as the *_tables calls take them -> (values, tables, slots)."""
+    if not isinstance(values, torch.Tensor) or values.device != dev or values.dim() != 3:
+        raise ValueError(f"values must with slots be int16 [tables, 2, 81] (the bits of the uint16 entries) on the device of {what}")
+    tables = int(values.shape[0])
+    if not 1 <= tables <= MAX_MOVE_VALUE_TABLES:
+        raise ValueError(f"the number of move-value tables must be 1..{MAX_MOVE_VALUE_TABLES}, got {tables}")
+    if not isinstance(slots, torch.Tensor) or slots.device != dev:
+        raise ValueError(f"slots must be int32 [{n}] on the device of {what}")
+    return _dev(values, "values", (tables, 2, 81), torch.int16), tables, _dev(slots, "slots", (n,), torch.int32)
+
+
 def move_value_playouts(pos, seed, counters, table, tactics, values, max_plies, over=None, history=True, replies=None,
-                        replies2=None):
+                        replies2=None, slots=None):
     """tactical_playouts whose weights are multiplied by a per-(colour, point) factor (bkt_move_value_playouts;
     include/bokego_train.h has the rule): values int16 [2,81] on the device of pos, the bits of the uint16 entries (256:
     neutral), read only; table and tactics: tactical_playouts' tables, each of which may be None.  replies: None or
     reply_playouts' table, uint8 [2,81]; replies2: None or reply2_playouts' table, uint8 [2,82,81]; at most one of the two
-    (ValueError): a playable reply overrules the draw as in those calls."""
+    (ValueError): a playable reply overrules the draw as in those calls.
+    With slots, many tables in the same launch (bkt_move_value_playouts_tables): values int16 [tables,2,81] and slots int32
+    [B] on the device of pos, both read only; row i draws with table slots[i], and a slot outside 0..tables-1 plays as if
+    every value were 256.  replies is then uint8 [tables,2,81] and replies2 uint8 [tables,2,82,81], with the same number of
+    tables: the same slot names the reply table and the move-value table of a row."""
     weights = _weight_tables(pos, table, tactics)
-    v = _move_values(values, pos.device, "pos")
     if replies is not None and replies2 is not None:
         raise ValueError("at most one of replies and replies2 may be given: a pair table contains the single one")
+    if slots is not None:
+        B = _pos_batch(pos)
+        v, tables, sl = _move_value_tables(values, slots, B, pos.device, "pos")
+        r1 = None if replies is None else _reply_tables(replies, slots, B, pos.device, "pos")[1]
+        r2 = None if replies2 is None else _reply2_tables(replies2, slots, B, pos.device, "pos")[1]
+        for r in (r1, r2):
+            if r is not None and r[1] != tables:
+                raise ValueError(f"the reply tables and the move-value tables must be equally many, got {r[1]} and {tables}")
+        return _playouts("bkt_move_value_playouts_tables", pos, seed, counters,
+                         (*weights, v, None if r1 is None else r1[0], None if r2 is None else r2[0], tables, sl), max_plies,
+                         over, history)
+    v = _move_values(values, pos.device, "pos")
     r1 = None if replies is None else _reply_tables(replies, None, _pos_batch(pos), pos.device, "pos")[1][0]
     r2 = None if replies2 is None else _reply2_table(replies2, pos.device, "pos")
     return _playouts("bkt_move_value_playouts", pos, seed, counters, (*weights, v, r1, r2), max_plies, over, history)
 
 
-def move_value_update(pos, moves, won, records, playouts, counts, values, lut, k, limit, scratch=None):
+def move_value_update(pos, moves, won, records, playouts, counts, values, lut, k, limit, scratch=None, slots=None):
     """Fold a batch of playouts into a move-value table, in place (bkt_move_value_update; include/bokego_train.h has the
     rule): pos uint8 [records,192], the starting records (read only); moves and won as reply_update takes them; counts int64
     [2,81,2], values int16 [2,81] and lut int16 [65] (the bits of the uint16 entries) on the device of moves; 1 <= k <=
     MOVE_VALUE_MAX_K; limit 0 or 2..MOVE_VALUE_MAX_LIMIT; playouts * max_plies < 2^31.  scratch: None (allocated here) or a
     uint8 tensor of at least bkt_move_value_scratch_bytes(records) bytes.  Two launches on the current stream; nothing
-    waits.  -> (counts, values)."""
+    waits.
+    With slots, many tables (bkt_move_value_update_tables): counts int64 [tables,2,81,2] and values int16 [tables,2,81];
+    slots int32 [records], the table of every record -- table t is updated with the records whose slot is t, a table that
+    no record names keeps every byte, and a slot outside 0..tables-1 updates nothing.  -> (counts, values)."""
     records, playouts, max_plies = _amaf_args(moves, won, records, playouts)
     if not isinstance(pos, torch.Tensor) or tuple(pos.shape) != (records, POS_BYTES) or pos.device != moves.device:
         raise ValueError(f"pos must be [{records}, {POS_BYTES}] on the device of moves")
@@ -712,17 +748,21 @@ def move_value_update(pos, moves, won, records, playouts, counts, values, lut, k
     for t, name in ((counts, "counts"), (lut, "lut")):
         if not isinstance(t, torch.Tensor) or t.device != moves.device:
             raise ValueError(f"{name} must be on the device of moves")
-    v = _move_values(values, moves.device, "moves")
-    need = load().bkt_move_value_scratch_bytes(records)
+    if slots is None:
+        v, extra, shape, name = _move_values(values, moves.device, "moves"), (), (2, 81, 2), "bkt_move_value_update"
+        need = load().bkt_move_value_scratch_bytes(records)
+    else:
+        v, tables, sl = _move_value_tables(values, slots, records, moves.device, "moves")
+        extra, shape, name = (tables, sl), (tables, 2, 81, 2), "bkt_move_value_update_tables"
+        need = load().bkt_move_value_tables_scratch_bytes(records, tables)
     if scratch is None:
         scratch = torch.empty((need,), dtype=torch.uint8, device=moves.device)
     elif not isinstance(scratch, torch.Tensor) or scratch.device != moves.device or scratch.dim() != 1 or scratch.numel() < need:
         raise ValueError(f"scratch must be uint8 [>= {need}] on the device of moves")
-    _check(load().bkt_move_value_update(_dev(pos, "pos", dtype=torch.uint8), _dev(moves, "moves", dtype=torch.int16), max_plies,
-                                        _dev(won, "won", (records * playouts,), torch.uint8), records, playouts,
-                                        _dev(counts, "counts", (2, 81, 2), torch.int64), v, _dev(lut, "lut", (65,), torch.int16),
-                                        k, limit, _dev(scratch, "scratch", dtype=torch.uint8), _stream(moves)),
-           "bkt_move_value_update")
+    _check(getattr(load(), name)(_dev(pos, "pos", dtype=torch.uint8), _dev(moves, "moves", dtype=torch.int16), max_plies,
+                                 _dev(won, "won", (records * playouts,), torch.uint8), records, playouts,
+                                 _dev(counts, "counts", shape, torch.int64), v, _dev(lut, "lut", (65,), torch.int16),
+                                 k, limit, *extra, _dev(scratch, "scratch", dtype=torch.uint8), _stream(moves)), name)
     return counts, values
 
 

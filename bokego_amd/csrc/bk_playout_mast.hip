@@ -93,3 +93,5 @@ extern "C" int bkt_move_value_playouts(void* pos, int batch, uint64_t seed, cons
     if (replies2) return launch(movevalue_pairs_kernel, reinterpret_cast<const uint32_t*>(replies2));
     return launch(movevalue_draw_kernel);
 }
+
+#include "bk_playout_mast_tables.hip" // a move-value table per game of a self-play batch: text likewise

@@ -15,6 +15,11 @@ share:
 Everything is an integer: the device computes the same bits.  rollout.py's playouts take a MoveValueTable as move_values=
 and update it in place; with rules="device" the live copies are tensors on the device (bkt_move_value_playouts reads
 values, bkt_move_value_update writes counts and values) and `.counts` / `.values` download them when asked.
+
+MoveValueTables is a table per game of a self-play batch: counts [count,2,81,2] and values [count,2,81] with one
+lut, k and limit; slots= names the table of every row (bkt_move_value_playouts_tables) or record
+(bkt_move_value_update_tables).  A slot outside 0..count-1 plays with neutral values and updates nothing, and a table that
+no record names keeps every byte.
 """
 import numpy as np
 
@@ -25,11 +30,12 @@ MAX_K = 65536              # BKT_MOVE_VALUE_MAX_K
 MAX_LIMIT = 1 << 30        # BKT_MOVE_VALUE_MAX_LIMIT
 MOVE_NONE = -2             # BKT_MOVE_NONE
 WEIGHT_CAP = (1 << 24) - 1
+MAX_TABLES = 4096          # BKT_MAX_MOVE_VALUE_TABLES
 # the defaults of --playout-move-values: plausible and untuned
 DEFAULT_TAU, DEFAULT_K, DEFAULT_LIMIT = 0.25, 16, 16384
 
-__all__ = ["NEUTRAL", "MAX_K", "MAX_LIMIT", "DEFAULT_TAU", "DEFAULT_K", "DEFAULT_LIMIT", "MoveValueTable", "lut_of", "check_tau",
-           "check_k_limit", "rate_index", "move_value_weights", "move_value_update_host"]
+__all__ = ["NEUTRAL", "MAX_K", "MAX_LIMIT", "MAX_TABLES", "DEFAULT_TAU", "DEFAULT_K", "DEFAULT_LIMIT", "MoveValueTable",
+           "MoveValueTables", "lut_of", "check_tau", "check_k_limit", "rate_index", "move_value_weights", "move_value_update_host"]
 
 
 def check_tau(tau):
@@ -151,31 +157,109 @@ class MoveValueTable:
         self.__init__(state["counts"], state["values"], state["lut"], state["k"], state["limit"])
 
 
+class MoveValueTables(MoveValueTable):
+    """A move-value table per game of a batch: counts int64 [count,2,81,2] and values uint16 [count,2,81], with
+    one lut uint16 [65], one k and one limit for all of them; created empty (no play counted, every value 256).  slots= of
+    rollout.py's playouts names the table of every record.  `.counts`, `.values`, device(dev), clear(), deepcopy, pickle and
+    the host/device liveness rule are MoveValueTable's; occupancy() is per table, and table(i) a MoveValueTable copy of
+    table i."""
+
+    def __init__(self, count, tau=DEFAULT_TAU, k=DEFAULT_K, limit=DEFAULT_LIMIT):
+        if isinstance(count, bool) or not isinstance(count, (int, np.integer)):
+            raise TypeError(f"the number of move-value tables must be an int, got {type(count).__name__}")
+        if not 1 <= count <= MAX_TABLES:
+            raise ValueError(f"the number of move-value tables must be 1..{MAX_TABLES}, got {count}")
+        self._set(np.zeros((int(count), 2, 81, 2), np.int64), np.full((int(count), 2, 81), NEUTRAL, np.uint16), lut_of(tau), k, limit)
+
+    def _set(self, counts, values, lut, k, limit):
+        self.k, self.limit = check_k_limit(k, limit)
+        self._counts = np.array(counts, np.int64, order="C")
+        self._values = np.array(values, np.uint16, order="C")
+        self.lut = np.array(lut, np.uint16, order="C")
+        self.lut.setflags(write=False)
+        self._device = {}
+        self._live = None
+
+    @classmethod
+    def empty(cls, count=1, tau=DEFAULT_TAU, k=DEFAULT_K, limit=DEFAULT_LIMIT):
+        return cls(count, tau, k, limit)
+
+    @property
+    def count(self):
+        return len(self._counts)
+
+    def copy(self):
+        new = object.__new__(MoveValueTables)
+        new._set(self.counts, self.values, self.lut, self.k, self.limit)
+        return new
+
+    def occupancy(self):
+        """int64 [count]: the number of entries of each table with at least one play."""
+        return (self.counts[..., 0] > 0).sum((1, 2)).astype(np.int64)
+
+    def table(self, i):
+        """Table i as a MoveValueTable of its own (a copy)."""
+        i = int(i)
+        if not 0 <= i < self.count:
+            raise IndexError(f"table {i} of {self.count}")
+        return MoveValueTable(self.counts[i], self.values[i], self.lut, self.k, self.limit)
+
+    def __setstate__(self, state):
+        self._set(state["counts"], state["values"], state["lut"], state["k"], state["limit"])
+
+
 def _values_of(table):
     values = table.values if isinstance(table, MoveValueTable) else np.asarray(table)
-    if values.shape != (2, 81) or values.dtype != np.uint16:
-        raise ValueError("move values are uint16 [2, 81]")
+    if values.shape[-2:] != (2, 81) or values.ndim not in (2, 3) or values.dtype != np.uint16:
+        raise ValueError("move values are uint16 [2, 81], or with slots [count, 2, 81]")
     return values
 
 
-def move_value_weights(weights, values, colour):
+def _rows_values(values, slots, rows):
+    """uint16 [rows,2,81]: the values of every row -- the one table's without slots, else table slots[row]'s, and 256
+    everywhere for a slot outside 0..count-1 (compared before it indexes)."""
+    if slots is None:
+        if values.ndim != 2:
+            raise TypeError("move-value tables need slots: the table of every row")
+        return np.broadcast_to(values, (rows, 2, 81))
+    if values.ndim != 3:
+        raise TypeError("slots name the table of every row among many move-value tables: not with a single table")
+    slots = np.asarray(slots, np.int64)
+    if slots.shape != (rows,):
+        raise ValueError(f"slots must be an int array of one entry per row, [{rows}]")
+    ok = (slots >= 0) & (slots < len(values))
+    out = values[np.where(ok, slots, 0)]
+    out[~ok] = NEUTRAL
+    return out
+
+
+def move_value_weights(weights, values, colour, slots=None):
     """The weight rule for rows: weights [R,81] the weights w_in of the inner draw (rollout.move_weights_host's on the
     playable points; anything elsewhere), values a MoveValueTable or uint16 [2,81], colour int [R] the colour to move of
-    each row (0 black, 1 white) -> uint64 [R,81]: min(2^24 - 1, max(1, (w_in * values[colour, q]) >> 8))."""
+    each row (0 black, 1 white) -> uint64 [R,81]: min(2^24 - 1, max(1, (w_in * values[colour, q]) >> 8)).  With slots int
+    [R], values is a MoveValueTables or uint16 [count,2,81] and row r uses table slots[r] (a slot out of range: 256)."""
     w = np.asarray(weights).astype(np.uint64)
-    v = _values_of(values)[np.asarray(colour, np.int64)].astype(np.uint64)
+    colour = np.asarray(colour, np.int64)
+    v = _rows_values(_values_of(values), slots, len(w))[np.arange(len(w)), colour].astype(np.uint64)
     return np.minimum(np.maximum((w * v) >> np.uint64(8), np.uint64(1)), np.uint64(WEIGHT_CAP))
 
 
-def move_value_update_host(table, recs, moves, won, records, playouts):
+def move_value_update_host(table, recs, moves, won, records, playouts, slots=None):
     """bkt_move_value_update on the host: table a MoveValueTable, updated in place; recs uint8 [records,192], the starting
     records; moves int16 [records * playouts, max_plies] and won [records * playouts] as reply_update_host takes them.
     Every ply t of a row before the first entry <= MOVE_NONE whose move m is a board point adds a play to
     counts[c, m] with c = (the record's colour to move) xor (t & 1), and a win when (won[row] != 0) == (t even); then every
     entry is halved until played < limit (limit > 0), and values = lut[rate_index(played, won, k)].
+    With slots int [records], table is a MoveValueTables (bkt_move_value_update_tables): the rule applies per table, over the
+    records whose slot names it; a table that no record names keeps every byte, and a slot outside 0..count-1 updates
+    nothing.
     -> the number of plays added."""
+    many = isinstance(table, MoveValueTables)
     if not isinstance(table, MoveValueTable):
-        raise TypeError("move_value_update_host updates a MoveValueTable in place")
+        raise TypeError("move_value_update_host updates a MoveValueTable or a MoveValueTables in place")
+    if many != (slots is not None):
+        raise TypeError("slots name the table of every record among many move-value tables: required with a MoveValueTables, "
+                        "refused with a MoveValueTable")
     records, playouts = int(records), int(playouts)
     recs, moves, won = np.asarray(recs), np.asarray(moves), np.asarray(won).reshape(-1) != 0
     if records < 1 or playouts < 1 or moves.ndim != 2 or len(moves) != records * playouts or len(won) != len(moves) \
@@ -184,6 +268,11 @@ def move_value_update_host(table, recs, moves, won, records, playouts):
                          f"[{records} * {playouts}]")
     if not 1 <= moves.shape[1] <= 1024 or playouts * moves.shape[1] >= 2 ** 31:
         raise ValueError("max_plies must be 1..1024 (BKT_MAX_PLAYOUT_PLIES) and playouts * max_plies below 2^31")
+    if many:
+        slots = np.asarray(slots)
+        if slots.shape != (records,) or slots.dtype.kind not in "iu":
+            raise ValueError(f"slots must be an int array of one entry per record, [{records}]")
+        slots = slots.astype(np.int64)
     m = moves.astype(np.int64)
     live = np.cumsum(m <= MOVE_NONE, 1) == 0
     point = live & (m >= 0) & (m <= 80)
@@ -191,15 +280,21 @@ def move_value_update_host(table, recs, moves, won, records, playouts):
     c0 = np.repeat((L.record_turns(recs) & 1).astype(np.int64), playouts)
     c = c0[:, None] ^ (~even).astype(np.int64)[None, :]
     mover_won = won[:, None] == even[None, :]
-    flat = (c * 81 + np.clip(m, 0, 80))[point]
-    counts = table.counts
-    counts[..., 0] += np.bincount(flat, minlength=162).reshape(2, 81)
-    counts[..., 1] += np.bincount(flat[mover_won[point]], minlength=162).reshape(2, 81)
-    if table.limit > 0:
-        while True:
-            big = counts[..., 0] >= table.limit
-            if not big.any():
-                break
-            counts[big] >>= 1
-    table.values[...] = table.lut[np.minimum(rate_index(counts[..., 0], counts[..., 1], table.k), 64)]
-    return int(point.sum())
+    entry = c * 81 + np.clip(m, 0, 80)
+    all_counts, all_values = (table.counts, table.values) if many else (table.counts[None], table.values[None])
+    added = 0
+    for t in (np.unique(slots[(slots >= 0) & (slots < table.count)]) if many else (0,)):
+        mine = point if not many else point & np.repeat(slots == t, playouts)[:, None]
+        flat = entry[mine]
+        counts = all_counts[t]
+        counts[..., 0] += np.bincount(flat, minlength=162).reshape(2, 81)
+        counts[..., 1] += np.bincount(flat[mover_won[mine]], minlength=162).reshape(2, 81)
+        if table.limit > 0:
+            while True:
+                big = counts[..., 0] >= table.limit
+                if not big.any():
+                    break
+                counts[big] >>= 1
+        all_values[t][...] = table.lut[np.minimum(rate_index(counts[..., 0], counts[..., 1], table.k), 64)]
+        added += int(mine.sum())
+    return added

@@ -93,7 +93,8 @@ class PlayoutOptions:
         there are no per-game RAVE records there, and the games would mix their reply tables.  selfplay has two flags of
         its own instead, --game-rave and --game-replies (RAVE records and a reply table per game), and
         --game-reply-pairs (a pair reply table per game).  The move-value table goes with the reply tables: one
-        per search, so not where one evaluator serves many games."""
+        per search, so not where one evaluator serves many games; selfplay's own --game-move-values keeps one per game
+        (DESIGN 31)."""
         for field, (flag, kw, text) in FLAGS.items():
             if (rave or field != "playout_rave") and (replies or field not in LATE):
                 if field == "playout_value" and not (rave and replies):

@@ -78,6 +78,9 @@ DESIGN 26); PlayoutEvaluator(replies=2) keeps one.  A ReplyTables2 with slots= i
 move_values= (a MoveValueTable, bokego_amd/movevalues.py) is the soft counterpart (MAST): a win rate per colour
 and point, learned from the same histories and multiplied into the draw's weights (bkt_move_value_playouts,
 bkt_move_value_update), alone or under either reply table; PlayoutEvaluator(move_values=True) keeps one (opt-in, untuned).
+A movevalues.MoveValueTables with slots= is a move-value table per game of a batch (bkt_move_value_playouts_tables,
+bkt_move_value_update_tables; DESIGN 31), alone or beside a ReplyTables or a ReplyTables2 named by the same slots;
+PlayoutEvaluator(move_value_games=G) keeps G of them.
 
     python -m bokego_amd.rollout --sgf FILE [--move K] --random --move-values [-n 256] [--chunk 16]   # what the table learned
 
@@ -97,7 +100,7 @@ from . import _trainlib as T
 from . import go
 from . import lockstep as L
 from .lockstep import playable_host, record_turns  # noqa: F401  (public here: see __all__)
-from .movevalues import MoveValueTable, move_value_update_host, move_value_weights
+from .movevalues import DEFAULT_TAU, MoveValueTable, MoveValueTables, move_value_update_host, move_value_weights
 from .replies import (ReplyTable, ReplyTable2, ReplyTables, ReplyTables2, reply2_moves, reply2_plies_of, reply2_update_host, reply_moves, reply_plies_of,
                       reply_update_host, slots_of)
 
@@ -357,7 +360,8 @@ def _random_host(pos, key, ctr, max_plies, komi, history, table=None, tactics=No
     ply 0, the record's last move at ply 1), and reply_pair_plies is the pair entries' share of reply_plies; with a
     ReplyTables2 likewise, slots naming the pair table of every row.
     move_values (a MoveValueTable, read only here): the weights of the draw above -- 256 everywhere without
-    tables -- go through movevalues.move_value_weights with the values as they stand on entry and the colour to move."""
+    tables -- go through movevalues.move_value_weights with the values as they stand on entry and the colour to move; with a
+    MoveValueTables, slots names the table of every row, the same slot as its reply table's."""
     def choose(k, recs, live, ok, x0):
         n = ok.sum(1)
         pick = np.argmax(np.cumsum(ok, 1) > select_index(x0, n).astype(np.int64)[:, None], 1)
@@ -375,7 +379,8 @@ def _random_host(pos, key, ctr, max_plies, komi, history, table=None, tactics=No
         part = recs[live]
         entries = None if table is None else table.entries(PT.codes_host(part))
         t = np.full(ok.shape, TC.NEUTRAL, np.uint16) if tactics is None else tactics.entries(TC.codes_host(part))
-        return PT.select_weighted(x0, move_value_weights(TC.combine(entries, t), values, record_turns(part) & 1), ok)
+        return PT.select_weighted(x0, move_value_weights(TC.combine(entries, t), values, record_turns(part) & 1,
+                                                         None if value_slots is None else value_slots[live]), ok)
 
     if table is not None or move_values is not None:
         from . import patterns as PT
@@ -383,6 +388,7 @@ def _random_host(pos, key, ctr, max_plies, komi, history, table=None, tactics=No
         from . import tactics as TC
     if move_values is not None:
         values = move_values.values.copy()
+        value_slots = np.asarray(slots) if isinstance(move_values, MoveValueTables) else None   # the table of every row
         choose = choose_valued
     elif tactics is not None:
         choose = choose_tactical
@@ -449,11 +455,12 @@ def random_playouts(pos, seed, counters=None, max_plies=MAX_PLIES, rules="device
     move_values: None, or a movevalues.MoveValueTable (MAST): every game here draws with the table's values as
     they stand multiplied into the weights (bkt_move_value_playouts, with replies= composed as above), and the table is
     then updated in place with all G games, after the reply table if any (bkt_move_value_update).  Not with slots=
-    (TypeError): there are no move-value tables per game."""
+    (TypeError): a MoveValueTable is one table for all games.  A movevalues.MoveValueTables (a table per game)
+    needs slots= (TypeError without), alone or with a ReplyTables or a ReplyTables2 of the same count (ValueError), whose
+    tables the same slots name; a single ReplyTable or ReplyTable2 is refused with it (TypeError)."""
     L.check_rules(rules)
     table, tactics = _table(patterns), _tactics(tactics)
-    slots = _check_replies(replies, slots, len(pos))
-    _check_move_values(move_values, slots)
+    slots = _check_tables(replies, move_values, slots, len(pos))
     learns = replies is not None or move_values is not None
     max_plies = int(max_plies)
     if not 1 <= max_plies <= 1024:
@@ -472,7 +479,7 @@ def random_playouts(pos, seed, counters=None, max_plies=MAX_PLIES, rules="device
             if replies is not None:
                 _update_host(replies, start, moves, won, G, 1, slots)
             if move_values is not None:
-                move_value_update_host(move_values, start, moves, won, G, 1)
+                move_value_update_host(move_values, start, moves, won, G, 1, _value_slots(move_values, slots))
             fin.moves = moves if history else None
         return fin
     dev = _device(device, None, pos)
@@ -488,7 +495,7 @@ def random_playouts(pos, seed, counters=None, max_plies=MAX_PLIES, rules="device
         if replies is not None:
             _update_device(start, moves, won, G, 1, replies, slots)
         if move_values is not None:
-            _update_move_values_device(start, moves, won, G, 1, move_values)
+            _update_move_values_device(start, moves, won, G, 1, move_values, slots)
     _check_status(status, "selected")
     fin = _finished(pos, moves if history else None, plies.cpu().numpy().astype(np.int64), over.cpu().numpy() != 0,
                     score.cpu().numpy(), owner.cpu().numpy())
@@ -511,16 +518,45 @@ def _update_device(recs, moves, won, records, playouts, replies, slots):
     return T.reply_update(recs, moves, won, records, playouts, replies.device(recs.device), slots=slots)
 
 
-def _update_move_values_device(recs, moves, won, records, playouts, move_values):
-    """bkt_move_value_update on the current stream: the table's tensors on the device of recs are the table from here on."""
+def _update_move_values_device(recs, moves, won, records, playouts, move_values, slots=None):
+    """bkt_move_value_update on the current stream: the table's tensors on the device of recs are the table from here on.
+    With a MoveValueTables, bkt_move_value_update_tables with slots int32 [records] on the device."""
     counts, values, lut = move_values.device(recs.device)
-    return T.move_value_update(recs, moves, won, records, playouts, counts, values, lut, move_values.k, move_values.limit)
+    return T.move_value_update(recs, moves, won, records, playouts, counts, values, lut, move_values.k, move_values.limit,
+                               slots=_value_slots(move_values, slots))
+
+
+def _value_slots(move_values, slots):
+    """slots for the move-value calls: the checked slots with a MoveValueTables, None with a MoveValueTable."""
+    return slots if isinstance(move_values, MoveValueTables) else None
+
+
+def _check_tables(replies, move_values, slots, records):
+    """replies=, move_values= and slots= of the callers here -> slots as an int64 array [records], or None without tables
+    per game.  A MoveValueTables needs slots (TypeError), goes alone or with a ReplyTables or a ReplyTables2 of the same
+    count (ValueError), and not with a single reply table (TypeError); everything else is _check_replies' and
+    _check_move_values' rule."""
+    if not isinstance(move_values, MoveValueTables):
+        slots = _check_replies(replies, slots, records)
+        _check_move_values(move_values, slots)
+        return slots
+    if slots is None:
+        raise TypeError("move-value tables need slots: the table of every record")
+    if replies is None:
+        return slots_of(np.empty((1, 2, 81), np.uint8), _numpy(slots), records)
+    if not isinstance(replies, (ReplyTables, ReplyTables2)):
+        raise TypeError("a MoveValueTables keeps a table per game: with it replies= must be a ReplyTables or a ReplyTables2, "
+                        "not a single table")
+    if replies.count != move_values.count:
+        raise ValueError(f"the reply tables and the move-value tables must be equally many (the same slots name both), "
+                         f"got {replies.count} and {move_values.count}")
+    return _check_replies(replies, slots, records)
 
 
 def _check_move_values(move_values, slots):
     """move_values= of the callers here: None or a MoveValueTable, and never with slots= (there are no tables per game)."""
     if move_values is not None and not isinstance(move_values, MoveValueTable):
-        raise TypeError("move_values must be a MoveValueTable (it is updated in place) or None")
+        raise TypeError("move_values must be a MoveValueTable or a MoveValueTables (it is updated in place) or None")
     if move_values is not None and slots is not None:
         raise TypeError("move_values= keeps one table for all records: not with slots= (a table per game)")
 
@@ -555,14 +591,15 @@ def _play_random_device(pos, key, ctr, max_plies, history, table=None, tactics=N
     """pos uint8 [G,192] and ctr int32 [G,4] on the device; pos is played on in place; table: None or a PatternTable;
     tactics: None or a TacticTable; replies: None or a ReplyTable, which every launch reads as it stands, or a ReplyTables or
     a ReplyTables2 with slots int32 [G] on the device, the table of every row; move_values: None or a MoveValueTable, whose
-    values every launch reads as they stand (bkt_move_value_playouts, with a ReplyTable or a ReplyTable2 put in; no slots).
+    values every launch reads as they stand (bkt_move_value_playouts, with a ReplyTable or a ReplyTable2 put in; no slots),
+    or a MoveValueTables with the same slots (bkt_move_value_playouts_tables, with a ReplyTables or a ReplyTables2 put in).
     -> (over uint8 [G], plies int32 [G], moves int16 [G,max_plies] or None, status int32 [G]), T.MAX_BATCH rows per launch."""
     w, tac = (None if t is None else t.device(pos.device) for t in (table, tactics))
     if move_values is not None:
         put = {} if replies is None else {"replies2" if isinstance(replies, _PAIRS) else "replies": replies.device(pos.device)}
         values = move_values.device(pos.device)[1]
-        return _per_batch(lambda p, c: T.move_value_playouts(p, key, c, w, tac, values, max_plies, history=history, **put),
-                          pos, ctr)
+        return _per_batch(lambda p, c, s: T.move_value_playouts(p, key, c, w, tac, values, max_plies, history=history, slots=s,
+                                                                **put), pos, ctr, _value_slots(move_values, slots))
     if replies is not None:
         play = T.reply2_playouts if isinstance(replies, _PAIRS) else T.reply_playouts
         tables = (w, tac, replies.device(pos.device))
@@ -628,11 +665,13 @@ def _playouts(recs, n, key, rules, komi=L.KOMI, table=None, tactics=None, max_pl
     move_values=                    a MoveValueTable: every playout draws with its values as they stand
                                     (bkt_move_value_playouts, with history; replies= a ReplyTable or a ReplyTable2 composes),
                                     and after the score and the reply update one bkt_move_value_update folds all R * n of
-                                    them into it, in place and on the same stream.  It needs score=True, and refuses slots."""
+                                    them into it, in place and on the same stream.  It needs score=True, and refuses slots.
+                                    A MoveValueTables needs slots, the table of every record -- the same that
+                                    name a ReplyTables' or a ReplyTables2's -- and the launches are
+                                    bkt_move_value_playouts_tables and bkt_move_value_update_tables."""
     R, host = len(recs), rules == "host"
     counted, owned = (R if x is True else int(x) for x in (counted, owned))
-    slots = _check_replies(replies, slots, R)
-    _check_move_values(move_values, slots)
+    slots = _check_tables(replies, move_values, slots, R)
     if replies is not None and not score:
         raise ValueError("a reply table learns from who won each playout: it needs the scored run (not playout_ownership's)")
     if move_values is not None and not score:
@@ -662,9 +701,9 @@ def _playouts(recs, n, key, rules, komi=L.KOMI, table=None, tactics=None, max_pl
             _update_device(recs, moves, run.won.reshape(-1).to(torch.uint8), R, n, replies, slots)
     if move_values is not None:                                            # ... then the move values, on the same stream
         if host:
-            move_value_update_host(move_values, recs, moves, run.won.reshape(-1), R, n)
+            move_value_update_host(move_values, recs, moves, run.won.reshape(-1), R, n, _value_slots(move_values, slots))
         else:
-            _update_move_values_device(recs, moves, run.won.reshape(-1).to(torch.uint8), R, n, move_values)
+            _update_move_values_device(recs, moves, run.won.reshape(-1).to(torch.uint8), R, n, move_values, slots)
     if counted:
         reduce = ((T.amaf_counts, T.amaf_counts_sides), (amaf_counts_host, amaf_counts_sides_host))[host][sides - 1]
         won = run.won[:counted].reshape(-1)
@@ -1021,7 +1060,13 @@ class PlayoutEvaluator:
     `.move_values`, which reset_move_values() clears.  The playouts of every request draw with its values
     (bkt_move_value_playouts, composed with replies=True or replies=2) and are folded into it after their score and the
     reply update (bkt_move_value_update), all on the one stream.  A fresh table is neutral: the first request equals the
-    evaluator without the option bit for bit.  With games= or pair_games= it is a TypeError: no move-value tables per game.
+    evaluator without the option bit for bit.  With games= or pair_games= it is a TypeError: that is move_value_games=.
+    move_value_games=G (default None: exactly the above): `.move_values` is a movevalues.MoveValueTables(G,
+    tau=move_value_tau), a move-value table per game, wants_games is true and submit takes games=, the table of every row;
+    one bkt_move_value_playouts_tables and one bkt_move_value_update_tables serve all games of a request.  It goes alone,
+    with replies=True, games=G or with pair_games=G -- the same G (ValueError), the same games= naming both tables of a row
+    -- and not with move_values=, nor with replies=True or replies=2 without tables per game (TypeError).  A one-game pool
+    is then move_values=tau bit for bit.
     The engine is kept as `policy_engine`, not `engine`: selfplay.run_pools_native hands an evaluator's `engine` to the C
     step loop as its own bk_evaluator, which would compute no playouts -- this class goes through callback_evaluator."""
     wants_positions = True
@@ -1029,13 +1074,26 @@ class PlayoutEvaluator:
 
     def __init__(self, engine, playouts=64, seed=0, rules="device", komi=L.KOMI, patterns=None, tactics=None, prior=0.0,
                  prior_k=PRIOR_K, prior_temperature=PRIOR_TEMPERATURE, rave=False, criticality=0.0, pattern_prior=0.0,
-                 prior_patterns=None, prior_tactics=None, move_values=False, replies=False, games=None, pair_games=None):
+                 prior_patterns=None, prior_tactics=None, move_values=False, move_value_games=None, move_value_tau=DEFAULT_TAU,
+                 replies=False, games=None, pair_games=None):
         L.check_rules(rules)
         if move_values and (games is not None or pair_games is not None):
             raise TypeError("move_values= keeps one table for all rows: it goes without games= and pair_games= (a table per game)")
         # True: the default temperature; a number: tau; False, None or 0: no table
         self.move_values = (MoveValueTable.empty() if move_values is True else MoveValueTable.empty(tau=move_values)) \
             if move_values else None
+        if move_value_games is not None:
+            if move_values:
+                raise TypeError("move_value_games= is the number of move-value tables, a MoveValueTables: it goes without "
+                                "move_values= (one table for all rows)")
+            if replies and games is None:
+                raise TypeError("move_value_games= keeps a table per game: with it the reply tables are per game too "
+                                "(replies=True, games=G, or pair_games=G), not one for all rows")
+            for other in (games, pair_games):
+                if other is not None and int(other) != int(move_value_games):
+                    raise ValueError(f"the reply tables and the move-value tables must be equally many (games= names both "
+                                     f"tables of a row), got {other} and {move_value_games}")
+            self.move_values = MoveValueTables(move_value_games, tau=move_value_tau)
         if pair_games is not None and (replies or games is not None):
             raise TypeError("pair_games= is the number of pair reply tables, a ReplyTables2: it goes without replies= and games=")
         if games is not None and not replies:
@@ -1048,7 +1106,7 @@ class PlayoutEvaluator:
             self.replies = ReplyTables2(pair_games)
         else:
             self.replies = (ReplyTable.empty() if games is None else ReplyTables(games)) if replies else None
-        if games is not None or pair_games is not None:
+        if games is not None or pair_games is not None or move_value_games is not None:
             self.wants_games = True
         self.rave = bool(rave)
         self.criticality = _not_negative(criticality, "criticality")
@@ -1082,9 +1140,10 @@ class PlayoutEvaluator:
         if recs.ndim != 2 or recs.shape[1] != POS_BYTES:
             raise ValueError(f"a PlayoutEvaluator takes position records uint8 [B, {POS_BYTES}], got {recs.shape}")
         if self.wants_games and games is None:
-            raise TypeError("this evaluator keeps a reply table per game: submit needs games=, the table of every row")
+            raise TypeError("this evaluator keeps a table per game: submit needs games=, the table of every row")
         if not self.wants_games and games is not None:
-            raise TypeError("games= names reply tables: this evaluator keeps none per game (replies=True, games=G, or pair_games=G)")
+            raise TypeError("games= names the tables of the rows: this evaluator keeps none per game (replies=True, games=G, "
+                            "pair_games=G or move_value_games=G)")
         self.positions += len(recs)
         self.batches += 1
         ticket = None
@@ -1110,9 +1169,10 @@ class PlayoutEvaluator:
         self.replies.clear()
 
     def reset_move_values(self):
-        """An empty move-value table again (move_values=True or tau): what a new game starts with."""
+        """An empty move-value table again (move_values=True or tau; every table with move_value_games=G): what a new game
+        starts with."""
         if self.move_values is None:
-            raise TypeError("this evaluator keeps no move-value table: move_values=True")
+            raise TypeError("this evaluator keeps no move-value table: move_values=True or move_value_games=G")
         self.move_values.clear()
 
     def finish(self, handle, normalise=None):

@@ -714,7 +714,8 @@ def self_play(evaluator, n_games=512, rollouts=400, rank=0, world=1, seed_base=2
     rave: k > 0 = RAVE in every pool (GamePool.set_rave(k); it needs an evaluator whose finish returns the AMAF records,
     PlayoutEvaluator(rave=True)).  An evaluator with wants_games (PlayoutEvaluator(replies=True, games=G), or
     PlayoutEvaluator(pair_games=G) for tables keyed by the last two moves) gives every game a reply table of its own, slot = the game's place among this rank's games; the tables are cleared first and G must cover
-    the rank's games.  Either one needs the Python step loop (native_loop=True is a ValueError), and per-game tables need
+    the rank's games.  PlayoutEvaluator(move_value_games=G) gives every game a move-value table of its own in the same way,
+    alone or beside either kind of reply table.  Either one needs the Python step loop (native_loop=True is a ValueError), and per-game tables need
     de-duplication off (dedup=True is a ValueError: equal records of different games no longer have equal values).  A game
     stays a pure function of seed_base + gid: its table sees only its own requests, in its own row order."""
     rave = float(rave or 0.0)
@@ -766,11 +767,16 @@ def self_play(evaluator, n_games=512, rollouts=400, rank=0, world=1, seed_base=2
             at += k
     else:
         parts = [gids[i::n_pools] for i in range(n_pools)]
-    if per_game:
+    if per_game and getattr(evaluator, "replies", None) is not None:
         if evaluator.replies.count < len(gids):
             raise ValueError(f"the evaluator keeps {evaluator.replies.count} reply tables, this rank plays {len(gids)} games: "
                              "PlayoutEvaluator(games=) or (pair_games=) must cover them")
         evaluator.reset_replies()
+    if per_game and getattr(evaluator, "move_values", None) is not None:  # a move-value table per game
+        if evaluator.move_values.count < len(gids):
+            raise ValueError(f"the evaluator keeps {evaluator.move_values.count} move-value tables, this rank plays {len(gids)} "
+                             "games: PlayoutEvaluator(move_value_games=) must cover them")
+        evaluator.reset_move_values()
     pools = [GamePool([seed_base + g for g in part], prm, cap=cap, threads=threads) for part in parts]
     if rave > 0.0:
         for pool in pools:
@@ -940,7 +946,7 @@ def parse_args(argv=None):
                     help="re-play the games a failed rank owned (e.g. 3/8: the gids with gid %% 8 == 3) in this process")
     PlayoutOptions.add_arguments(ap, rave=False, replies=False)       # --playout-value N: not with --value or --host-encode
     # the pools' own forms of the options left out above: RAVE records per game, and a reply table per game, or
-    # a pair reply table per game
+    # a pair reply table per game, and a move-value table per game
     ap.add_argument("--game-rave", type=float, nargs="?", const=4.0, default=0.0, metavar="K",
                     help="with --playout-value and --playout-prior: RAVE in every game's search, equivalence parameter K (4 when "
                          "no value is given, as --playout-rave of gtp and match); the step loop runs in Python")
@@ -951,10 +957,17 @@ def parse_args(argv=None):
                     help="with --playout-value: as --game-replies with every game's replies keyed by the last two moves as well, "
                          "the single-move table being the fallback (LGRF-2 per game); with or without --game-replies, since "
                          "pairs contain singles")
+    ap.add_argument("--game-move-values", type=float, nargs="?", const=0.25, default=0.0, metavar="TAU",
+                    help="with --playout-value: every game's playouts learn a win rate per colour and point of their own (MAST "
+                         "per game) and lean their draw towards the points that win, temperature TAU (0.25 when no value is "
+                         "given, as --playout-move-values of gtp and match); it composes with --game-rave, --game-replies and "
+                         "--game-reply-pairs")
     args = ap.parse_args(argv)
     args.playout = PlayoutOptions.from_args(ap, args)
+    if not 0.0 <= args.game_move_values < float("inf"):                   # (a NaN fails the comparison)
+        ap.error("--game-move-values must be a finite number, 0 or more")
     for flag, on in (("--game-rave", args.game_rave != 0.0), ("--game-replies", args.game_replies),
-                     ("--game-reply-pairs", args.game_reply_pairs)):
+                     ("--game-reply-pairs", args.game_reply_pairs), ("--game-move-values", args.game_move_values != 0.0)):
         if on and not args.playout_value:
             ap.error(f"{flag} goes with the playouts of --playout-value: it needs --playout-value")
     if not 0.0 <= args.game_rave < float("inf"):
@@ -971,11 +984,13 @@ def parse_args(argv=None):
 
 
 def game_table_keywords(args, games):
-    """The PlayoutEvaluator keywords of --game-replies and --game-reply-pairs for `games` games of this rank: pairs contain
-    singles, so with both flags the tables are the pair tables."""
+    """The PlayoutEvaluator keywords of --game-replies, --game-reply-pairs and --game-move-values for `games` games of this
+    rank: pairs contain singles, so with both reply flags the tables are the pair tables; the move-value tables go beside
+    either kind, or alone."""
+    more = dict(move_value_games=games, move_value_tau=args.game_move_values) if getattr(args, "game_move_values", 0.0) else {}
     if args.game_reply_pairs:
-        return dict(pair_games=games)
-    return dict(replies=True, games=games) if args.game_replies else {}
+        return dict(pair_games=games, **more)
+    return dict(replies=True, games=games, **more) if args.game_replies else more
 
 
 def main(argv=None):
@@ -1016,7 +1031,7 @@ def main(argv=None):
             eng = LeafEngine(load(args.policy, "policy_19.bkw"), None, device_id=local_rank, max_batch=args.max_batch,
                              precision=args.precision)
         more = dict(rave=True) if args.game_rave else {}
-        if args.game_replies or args.game_reply_pairs:
+        if args.game_replies or args.game_reply_pairs or args.game_move_values:
             here = len(shard_game_ids(args.games, *(int(v) for v in args.replay_shard.split("/")))) if args.replay_shard \
                 else len(shard_game_ids(args.games, rank, world))
             more.update(game_table_keywords(args, max(1, here)))

@@ -585,6 +585,43 @@ int bkt_move_value_update(const void *pos, const int16_t *moves, int max_plies, 
                           int64_t *counts, uint16_t *values, const uint16_t *lut, int k, int limit, void *scratch,
                           void *stream);
 
+/* A move-value table per game of a self-play batch (bokego_amd/movevalues.py MoveValueTables): the two calls
+ * above over `tables` tables that share one lut, one k and one limit.
+ *   counts  int64 [tables][2][81][2] on the device, 8-byte aligned;
+ *   values  uint16 [tables][2][81];
+ *   lut     uint16 [65], k, limit: as above, one for all tables;
+ *   slots   int32 [batch] for the playouts, [records] for the update: the table of a row, or of a record.
+ * 1 <= tables <= BKT_MAX_MOVE_VALUE_TABLES.  A slot outside 0..tables-1 is compared before it indexes anything: such a row
+ * plays as if every value were 256, and such a record updates nothing.
+ * bkt_move_value_playouts_tables: one launch.  Row i draws by the weight rule above with values[slots[i]]; the values of a
+ * workgroup's three rows are staged in LDS before the first ply.  replies is NULL or uint8 [tables][162], a single reply
+ * table per game under bkt_reply_playouts_tables' rule; replies2 is NULL or uint8 [tables][2][82][81], 4-byte aligned, a
+ * pair table per game under bkt_reply2_playouts_tables' rule; at most one of replies and replies2 may be given.  The same
+ * slots and the same tables name the reply table and the move-value table of a row.  With tables == 1 and every slot 0 it is
+ * bkt_move_value_playouts byte for byte.  With every value 256 the games are those of bkt_tactical_playouts,
+ * bkt_reply_playouts_tables and bkt_reply2_playouts_tables byte for byte, their uniform forms included (table and tactics
+ * NULL).
+ * bkt_move_value_update_tables: the update rule above applies per table, over the records whose slot names that table.  A
+ * table that is named gets every entry of values written.  A table that no record names keeps every byte, even when its
+ * played is at or above limit and even when its values are not what its counts imply.  A record with a slot outside the
+ * range updates nothing.  Two launches on `stream`: the first is bkt_move_value_update's; the second, a workgroup per
+ * (16 entries, table), adds the partial counts of the records that name its table.  Integers only, no atomics: the result is
+ * the definition's, whatever the scheduling.  With tables == 1 and every slot 0 it is bkt_move_value_update byte for byte.
+ * scratch: bkt_move_value_tables_scratch_bytes(records, tables) = records * 1296 bytes on the device, 4-byte aligned (0 when
+ * records < 1 or tables is outside 1..BKT_MAX_MOVE_VALUE_TABLES); its contents on entry do not matter.
+ * Domain checks: values == NULL, slots == NULL, tables out of range, both reply tables given or a misaligned replies2
+ * returns BKT_ERR_ARG; the other checks are those of bkt_move_value_update and bkt_reply2_update_tables.  A refused call
+ * launches nothing and writes nothing. */
+#define BKT_MAX_MOVE_VALUE_TABLES 4096
+int bkt_move_value_playouts_tables(void *pos, int batch, uint64_t seed, const uint32_t *counters, const uint16_t *table,
+                                   const uint16_t *tactics, const uint16_t *values, const uint8_t *replies,
+                                   const uint8_t *replies2, int tables, const int32_t *slots, int max_plies, uint8_t *over,
+                                   int32_t *plies, int16_t *moves, int32_t *status, void *stream);
+size_t bkt_move_value_tables_scratch_bytes(int records, int tables);
+int bkt_move_value_update_tables(const void *pos, const int16_t *moves, int max_plies, const uint8_t *won, int records,
+                                 int playouts, int64_t *counts, uint16_t *values, const uint16_t *lut, int k, int limit,
+                                 int tables, const int32_t *slots, void *scratch, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
