@@ -410,6 +410,64 @@ bool weights_ok(const bk_policy_weights* policy, const bk_value_weights* value) 
     return true;
 }
 
+// Finite weights only (bokego_amd.h): the kernels' ReLUs are max(v, 0), which turns a NaN into 0, so a net with one NaN weight
+// would play finite garbage instead of failing.  -> "" when every element of every tensor is finite and every BatchNorm
+// variance gives a finite folded scale (var + eps > 0), else the state_dict name of the first tensor that does not, e.g.
+// "policy conv.6.weight".  Host memory only: runs beside weights_ok, before any HIP call.
+struct named_tensor { const float* p; size_t n; std::string name; bool var; };
+
+void trunk_tensors(const bk_trunk_weights& t, std::vector<named_tensor>& out) {
+    for (int l = 0; l < 7; ++l) {
+        const std::string conv = "conv." + std::to_string(3 * l), bn = "conv." + std::to_string(3 * l + 1);
+        out.push_back({t.conv_w[l], (size_t)128 * (l == 0 ? 27 * 25 : 128 * 9), conv + ".weight", false});
+        out.push_back({t.conv_b[l], 128, conv + ".bias", false});
+        out.push_back({t.bn_w[l], 128, bn + ".weight", false});
+        out.push_back({t.bn_b[l], 128, bn + ".bias", false});
+        out.push_back({t.bn_mean[l], 128, bn + ".running_mean", false});
+        out.push_back({t.bn_var[l], 128, bn + ".running_var", true});
+    }
+    out.push_back({t.head_w, 128, "conv.21.weight", false});
+    out.push_back({t.head_b, 81, "conv.21.bias", false});
+}
+
+std::string first_bad_tensor(const std::vector<named_tensor>& ts) {
+    for (const named_tensor& t : ts)
+        for (size_t i = 0; i < t.n; ++i) {
+            const double v = t.p[i];
+            if (!std::isfinite(v) || (t.var && !(v + kBnEps > 0.0))) return t.name;
+        }
+    return "";
+}
+
+std::string weights_not_finite(const bk_policy_weights* policy, const bk_value_weights* value) {
+    std::vector<named_tensor> ts;
+    if (policy) {
+        trunk_tensors(policy->trunk, ts);
+        const std::string bad = first_bad_tensor(ts);
+        if (!bad.empty()) return "policy " + bad;
+    }
+    if (value) {
+        const bk_value_head_weights& h = value->head;
+        ts.clear();
+        trunk_tensors(value->trunk, ts);
+        ts.push_back({h.bn_w, 1, "bn.weight", false});
+        ts.push_back({h.bn_b, 1, "bn.bias", false});
+        ts.push_back({h.bn_mean, 1, "bn.running_mean", false});
+        ts.push_back({h.bn_var, 1, "bn.running_var", true});
+        ts.push_back({h.lin1_w, 64 * 81, "lin1.weight", false});
+        ts.push_back({h.lin1_b, 64, "lin1.bias", false});
+        ts.push_back({h.lin_bn_w, 64, "lin_bn.weight", false});
+        ts.push_back({h.lin_bn_b, 64, "lin_bn.bias", false});
+        ts.push_back({h.lin_bn_mean, 64, "lin_bn.running_mean", false});
+        ts.push_back({h.lin_bn_var, 64, "lin_bn.running_var", true});
+        ts.push_back({h.lin2_w, 64, "lin2.weight", false});
+        ts.push_back({h.lin2_b, 1, "lin2.bias", false});
+        const std::string bad = first_bad_tensor(ts);
+        if (!bad.empty()) return "value " + bad;
+    }
+    return "";
+}
+
 // every device buffer a net's parameter block points at
 std::vector<const void*> net_buffers(const bk_net_params& np) {
     return {np.wfrag, np.bias, np.head_w, np.head_b, np.lin1_wt, np.lin1_b, np.lin2_w, np.wfrag16, np.bias16};
@@ -719,6 +777,10 @@ int bk_engine_create(const bk_policy_weights* policy, const bk_value_weights* va
     if (max_batch <= 0) return fail(nullptr, BK_ERR_ARG, "max_batch must be positive");
     if (!weights_ok(policy, nullptr)) return fail(nullptr, BK_ERR_ARG, "policy weights: NULL tensor pointer");
     if (!weights_ok(nullptr, value)) return fail(nullptr, BK_ERR_ARG, "value weights: NULL tensor pointer");
+    {
+        const std::string bad = weights_not_finite(policy, value);
+        if (!bad.empty()) return fail(nullptr, BK_ERR_ARG, "weights are not finite: " + bad);
+    }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
         return fail(nullptr, BK_ERR_NO_GPU, "no HIP device visible (the engine has no CPU fallback)");
@@ -833,6 +895,10 @@ int bk_engine_set_weights(bk_engine* e, const bk_policy_weights* policy, const b
     if ((policy && !e->has_policy) || (value && !e->has_value))
         return fail(e, BK_ERR_ARG, "the engine was created without that net");
     if (!weights_ok(policy, value)) return fail(e, BK_ERR_ARG, "weights: NULL tensor pointer");
+    {   // refused before anything is touched: the engine goes on serving the weights it has
+        const std::string bad = weights_not_finite(policy, value);
+        if (!bad.empty()) return fail(e, BK_ERR_ARG, "weights are not finite: " + bad);
+    }
     for (auto& s : e->slots)
         if (s.busy) return fail(e, BK_ERR_ARG, "tickets outstanding: bk_wait for them before replacing the weights");
     HIP_TRY(e, hipSetDevice(e->device));

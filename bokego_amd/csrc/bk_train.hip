@@ -17,6 +17,8 @@ constexpr int NT = 256;               // four waves: a 2x2 grid of 64x32 wave ti
 constexpr int RT = 256;               // threads of the per-channel reductions
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
+__device__ __forceinline__ bool not_finite(float v) { return (__float_as_uint(v) & 0x7F800000u) == 0x7F800000u; }
+
 // One BK-deep stage of the 128 x 64 workgroup tile: wave w owns rows (w & 1) * 64 .. +64, columns (w >> 1) * 32 .. +32,
 // as 4 x 2 tiles of 16 x 16.  16x16x4 f32 MFMA operands: lane l holds A[l & 15][k = l >> 4] and B[k = l >> 4][l & 15].
 __device__ __forceinline__ void mma_stage(const float (*As)[BM + PAD], const float (*Bs)[BN + PAD], f32x4 (&acc)[4][2],
@@ -40,7 +42,8 @@ __device__ __forceinline__ void mma_stage(const float (*As)[BM + PAD], const flo
 // A stage's 16-deep products go into fresh accumulators, which are then added to the running sums with Kahan
 // compensation: a dot product of K = 1152 carries the rounding of a 16-term MFMA chain plus O(eps^2), not of a
 // 1152-term chain.  This matters where a gradient is a small difference of large partial sums (measured: 5e-4 relative
-// error of the deep layers' gradients in the value net with plain chains).
+// error of the deep layers' gradients in the value net with plain chains).  A running sum that reaches +-Inf
+// becomes NaN at the next stage ((t - acc) - y is inf - inf): the allowance of bokego_train.h's "Non-finite values".
 __device__ __forceinline__ void stage_into(const float (*As)[BM + PAD], const float (*Bs)[BN + PAD], f32x4 (&acc)[4][2],
                                            f32x4 (&comp)[4][2], int lane, int wm, int wn) {
     f32x4 part[4][2];
@@ -62,7 +65,9 @@ __device__ __forceinline__ void stage_into(const float (*As)[BM + PAD], const fl
 
 // ---- forward: y[b][m][p] = sum_k wt[k][m] * im2col(x)[k][b*81 + p] (+ bias[m]) ----------------------------------------
 // Also the input gradient (wt = the rotated, channel-swapped filters, x = dy, no bias).
-template <int KS>
+// SAN (the input gradient): a weight that is not finite enters the GEMM as 0 and is added by dgrad_nonfinite_kernel, over
+// the taps that lie on the board only -- the GEMM would multiply it with the zero a tap off the board reads.
+template <int KS, bool SAN = false>
 __global__ __launch_bounds__(NT) void conv_fwd_kernel(const float *__restrict__ x, const float *__restrict__ wt,
                                                       const float *__restrict__ bias, float *__restrict__ y, int batch,
                                                       int cin) {
@@ -88,6 +93,7 @@ __global__ __launch_bounds__(NT) void conv_fwd_kernel(const float *__restrict__ 
         for (int i = 0; i < 8; ++i) {
             const int kk = k0 + ak + 2 * i;
             ra[i] = kk < K ? wt[(size_t)kk * BM + am] : 0.f;
+            if (SAN && not_finite(ra[i])) ra[i] = 0.f;
         }
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -135,6 +141,33 @@ __global__ __launch_bounds__(NT) void conv_fwd_kernel(const float *__restrict__ 
                 const int m = wm + 16 * i + (lane >> 4) * 4 + r;
                 yb[m * P] = acc[i][j][r] + (bias ? bias[m] : 0.f);
             }
+    }
+}
+
+// The input gradient's weights that are not finite (conv_fwd_kernel<3, true> took them as 0): workgroup m adds
+// w * dy[b][co][p + tap] to dx[b][m][p] for each of them, over the taps on the board -- the terms of the float64 input gradient,
+// no others.  With finite weights it reads the 1152 weights of its channel and returns.  One thread owns an element of dx.
+__global__ __launch_bounds__(256) void dgrad_nonfinite_kernel(const float *__restrict__ dy, const float *__restrict__ wt,
+                                                              float *__restrict__ dx, int batch) {
+    const int m = blockIdx.x, t = threadIdx.x;
+    int any = 0;
+    for (int k = t; k < BM * 9; k += 256) any |= not_finite(wt[(size_t)k * BM + m]);
+    if (!__syncthreads_or(any)) return;
+    for (int i = t; i < batch * P; i += 256) {
+        const int b = i / P, p = i - b * P, py = p / 9, px = p - (p / 9) * 9;
+        float s = 0.f;
+        bool hit = false;
+        for (int k = 0; k < BM * 9; ++k) {
+            const float w = wt[(size_t)k * BM + m];
+            if (!not_finite(w)) continue;
+            const int co = k / 9, tap = k - co * 9;
+            const int yy = py + tap / 3 - 1, xx = px + (tap - (tap / 3) * 3) - 1;
+            if ((unsigned)yy < 9u && (unsigned)xx < 9u) {
+                s += w * dy[((size_t)b * BM + co) * P + yy * 9 + xx];
+                hit = true;
+            }
+        }
+        if (hit) dx[((size_t)b * BM + m) * P + p] += s;
     }
 }
 
@@ -257,6 +290,21 @@ __device__ __forceinline__ void tree_sum2(double &a, double &b, double (*sh)[RT]
     b = sh[1][0];
 }
 
+// Non-finite values pass through (bokego_train.h, "Non-finite values"): fmaxf(v, 0) and `y > 0 ? dy : 0` would turn a NaN
+// into 0, so the ReLU and its mask are written with the one comparison that is false for a NaN.
+__device__ __forceinline__ float relu_keep_nan(float v) { return v <= 0.f ? 0.f : v; }
+__device__ __forceinline__ float relu_mask(float y, float dy) { return y <= 0.f ? 0.f : dy; }
+// (xc) * invstd * gamma + beta with xc = x - mean.  An infinite gamma takes float64 torch's form of the same expression,
+// x * a + (beta - mean * a) with a = invstd * gamma, whose Inf - Inf marks the element NaN where x and the mean have one sign:
+// the set the "Non-finite values" rule of bokego_train.h is stated against.  A finite gamma never takes that branch.
+__device__ __forceinline__ float bn_affine(float x, float mean, float invstd, float gamma, float beta) {
+    if ((__float_as_uint(gamma) & 0x7FFFFFFFu) == 0x7F800000u) {
+        const float a = invstd * gamma;
+        return x * a + (beta - mean * a);
+    }
+    return (x - mean) * invstd * gamma + beta;
+}
+
 enum { SUM_X_XX = 0, SUM_DZ_DZXHAT = 1, SUM_DY = 2 };
 
 // part[(s * C + c) * 2 + {0, 1}]:  SUM_X_XX: sum x, sum x^2;  SUM_DZ_DZXHAT: sum dz, sum dz * xhat (dz = dy where y > 0);
@@ -283,7 +331,7 @@ __global__ __launch_bounds__(RT) void chan_partial_kernel(const float *__restric
             s0 += v;
             s1 += v * v;
         } else if (MODE == SUM_DZ_DZXHAT) {
-            const float dz = y[j] > 0.f ? a[j] : 0.f;
+            const float dz = relu_mask(y[j], a[j]);
             s0 += dz;
             s1 += (double)dz * (double)((x[j] - mu) * is);
         } else {
@@ -319,7 +367,8 @@ __global__ __launch_bounds__(256) void bn_stats_finalize_kernel(const double *__
     slice_sums(part, slices, C, c, s0, s1);
     const double n = (double)batch * P;
     const double mean = s0 / n;
-    const double var = fmax(s1 / n - mean * mean, 0.0);
+    double var = s1 / n - mean * mean;
+    if (var < 0.0) var = 0.0;  // rounding only; a NaN (one Inf in the channel: inf - inf) stays a NaN
     save_mean[c] = (float)mean;
     save_invstd[c] = (float)(1.0 / sqrt(var + (double)eps));
     if (running_mean) running_mean[c] = (float)((1.0 - momentum) * running_mean[c] + momentum * mean);
@@ -353,7 +402,7 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const float *__restrict__
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= total) return;
     const int c = (int)((i / P) % C);
-    y[i] = fmaxf((x[i] - mean[c]) * invstd[c] * gamma[c] + beta[c], 0.f);
+    y[i] = relu_keep_nan(bn_affine(x[i], mean[c], invstd[c], gamma[c], beta[c]));
 }
 
 __global__ __launch_bounds__(256) void bn_eval_kernel(const float *__restrict__ x, const float *__restrict__ gamma,
@@ -363,7 +412,7 @@ __global__ __launch_bounds__(256) void bn_eval_kernel(const float *__restrict__ 
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= total) return;
     const int c = (int)((i / P) % C);
-    y[i] = fmaxf((x[i] - rmean[c]) * (1.f / sqrtf(rvar[c] + eps)) * gamma[c] + beta[c], 0.f);
+    y[i] = relu_keep_nan(bn_affine(x[i], rmean[c], 1.f / sqrtf(rvar[c] + eps), gamma[c], beta[c]));
 }
 
 __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float *__restrict__ dy, const float *__restrict__ y,
@@ -377,7 +426,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float *__restri
     if (i >= total) return;
     const int c = (int)((i / P) % C);
     const float is = invstd[c];
-    const float dz = y[i] > 0.f ? dy[i] : 0.f;
+    const float dz = relu_mask(y[i], dy[i]);
     const float xhat = (x[i] - mean[c]) * is;
     dx[i] = gamma[c] * is * (dz - dbeta[c] * inv_n - xhat * (dgamma[c] * inv_n));
 }
@@ -397,7 +446,7 @@ __global__ __launch_bounds__(RT) void bn_eval_bwd_partial_kernel(const float *__
     for (int i = threadIdx.x; i < nb * P; i += RT) {
         const int b = b0 + i / P;
         const size_t j = ((size_t)b * C + c) * P + (i - (i / P) * P);
-        const float dz = y[j] > 0.f ? dy[j] : 0.f;
+        const float dz = relu_mask(y[j], dy[j]);
         s0 += dz;
         s1 += (double)dz * (((double)x[j] - mu) * is);
     }
@@ -416,7 +465,7 @@ __global__ __launch_bounds__(256) void bn_eval_bwd_apply_kernel(const float *__r
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= total) return;
     const int c = (int)((i / P) % C);
-    const float dz = y[i] > 0.f ? dy[i] : 0.f;
+    const float dz = relu_mask(y[i], dy[i]);
     dx[i] = dz * (gamma[c] * (1.f / sqrtf(rvar[c] + eps)));
 }
 
@@ -562,7 +611,12 @@ int bkt_conv_forward(const float *x, const float *wt, const float *bias, float *
 }
 
 int bkt_conv_dgrad(const float *dy, const float *wt_dgrad, float *dx, int batch, void *stream) {
-    return bkt_conv_forward(dy, wt_dgrad, nullptr, dx, batch, BM, 3, stream);
+    if (!dy || !wt_dgrad || !dx || !ok_batch(batch)) return BKT_ERR_ARG;
+    hipLaunchKernelGGL((conv_fwd_kernel<3, true>), dim3(blocks((size_t)batch * P, BN)), dim3(NT), 0, S(stream), dy, wt_dgrad,
+                       (const float *)nullptr, dx, batch, BM);
+    if (launched() != BKT_OK) return BKT_ERR_HIP;
+    hipLaunchKernelGGL(dgrad_nonfinite_kernel, dim3(BM), dim3(256), 0, S(stream), dy, wt_dgrad, dx, batch);
+    return launched();
 }
 
 size_t bkt_bn_workspace(int batch, int channels) {

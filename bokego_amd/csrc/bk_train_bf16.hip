@@ -332,7 +332,44 @@ __global__ __launch_bounds__(256) void pack_bf16_kernel(const float *__restrict_
     const int k = s * BK + kk, tap = k / CP, c = k - tap * CP;
     float v = 0.f;
     if (tap < KK && c < cin) v = DGRAD ? w[((size_t)c * BM + m) * KK + (KK - 1 - tap)] : w[((size_t)m * cin + c) * KK + tap];
-    wt[i] = bf16_bits(v);
+    const uint16_t h = bf16_bits(v);
+    if (!DGRAD) {
+        wt[i] = h;
+        return;
+    }
+    // the input gradient: a weight that is not finite enters the GEMM as 0 and is kept in the second half of the operand,
+    // from where dgrad_nonfinite_bf16_kernel adds it over the taps on the board only
+    const bool bad = (h & 0x7F80u) == 0x7F80u;
+    wt[i] = bad ? (uint16_t)0 : h;
+    wt[total + i] = bad ? h : (uint16_t)0;
+}
+
+// bk_train.hip's dgrad_nonfinite_kernel for the packed operand: workgroup m adds w * dy[b][co][p + tap] to dx[b][m][p] for
+// each weight of its channel that is not finite, over the taps on the board.  side = the second half of the operand.
+__global__ __launch_bounds__(256) void dgrad_nonfinite_bf16_kernel(const float *__restrict__ dy,
+                                                                   const uint16_t *__restrict__ side,
+                                                                   float *__restrict__ dx, int batch) {
+    const int m = blockIdx.x, t = threadIdx.x;
+    auto at = [&](int k) { return side[((size_t)(k / BK) * BM + m) * BK + (k % BK)]; };  // k = tap * 128 + co
+    int any = 0;
+    for (int k = t; k < BM * 9; k += 256) any |= at(k) != 0;
+    if (!__syncthreads_or(any)) return;
+    for (int i = t; i < batch * P; i += 256) {
+        const int b = i / P, p = i - b * P, py = p / 9, px = p - (p / 9) * 9;
+        float s = 0.f;
+        bool hit = false;
+        for (int k = 0; k < BM * 9; ++k) {
+            const uint16_t h = at(k);
+            if (h == 0) continue;
+            const int tap = k / BM, co = k - tap * BM;
+            const int yy = py + tap / 3 - 1, xx = px + (tap - (tap / 3) * 3) - 1;
+            if ((unsigned)yy < 9u && (unsigned)xx < 9u) {
+                s += __uint_as_float((uint32_t)h << 16) * dy[((size_t)b * BM + co) * P + yy * 9 + xx];
+                hit = true;
+            }
+        }
+        if (hit) dx[((size_t)b * BM + m) * P + p] += s;
+    }
 }
 
 // ---- db: per-channel sums of the unrounded dy, as bk_train.hip's SUM_DY reduction: workgroup (c, s) sums slice s
@@ -380,12 +417,13 @@ extern "C" {
 
 size_t bkt_conv_packed_elems_bf16(int cin, int ksize) {
     if (!ok_conv(cin, ksize)) return 0;
-    return (size_t)stages_of(cin, ksize) * BM * BK;
+    const size_t n = (size_t)stages_of(cin, ksize) * BM * BK;
+    return cin == BM && ksize == 3 ? 2 * n : n;  // room for the input gradient's weights that are not finite (pack_bf16_kernel)
 }
 
 int bkt_conv_pack_bf16(const float *w, int cin, int ksize, uint16_t *wt, void *stream) {
     if (!w || !wt || !ok_conv(cin, ksize)) return BKT_ERR_ARG;
-    const int total = (int)bkt_conv_packed_elems_bf16(cin, ksize);
+    const int total = stages_of(cin, ksize) * BM * BK;
     hipLaunchKernelGGL(pack_bf16_kernel<false>, dim3(blocks(total, 256)), dim3(256), 0, S(stream), w, wt, cin, ksize,
                        total);
     return launched();
@@ -393,7 +431,7 @@ int bkt_conv_pack_bf16(const float *w, int cin, int ksize, uint16_t *wt, void *s
 
 int bkt_conv_pack_dgrad_bf16(const float *w, uint16_t *wt_dgrad, void *stream) {
     if (!w || !wt_dgrad) return BKT_ERR_ARG;
-    const int total = (int)bkt_conv_packed_elems_bf16(BM, 3);
+    const int total = stages_of(BM, 3) * BM * BK;
     hipLaunchKernelGGL(pack_bf16_kernel<true>, dim3(blocks(total, 256)), dim3(256), 0, S(stream), w, wt_dgrad, BM, 3,
                        total);
     return launched();
@@ -411,7 +449,11 @@ int bkt_conv_forward_bf16(const float *x, const uint16_t *wt, const float *bias,
 }
 
 int bkt_conv_dgrad_bf16(const float *dy, const uint16_t *wt_dgrad, float *dx, int batch, void *stream) {
-    return bkt_conv_forward_bf16(dy, wt_dgrad, nullptr, dx, batch, BM, 3, stream);
+    const int rc = bkt_conv_forward_bf16(dy, wt_dgrad, nullptr, dx, batch, BM, 3, stream);
+    if (rc != BKT_OK) return rc;
+    hipLaunchKernelGGL(dgrad_nonfinite_bf16_kernel, dim3(BM), dim3(256), 0, S(stream), dy,
+                       wt_dgrad + (size_t)stages_of(BM, 3) * BM * BK, dx, batch);
+    return launched();
 }
 
 size_t bkt_conv_wgrad_workspace_bf16(int batch, int cin, int ksize) {

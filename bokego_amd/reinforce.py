@@ -409,6 +409,18 @@ def engine_weights(net):
     return {k: v.detach() for k, v in net.state_dict().items()}
 
 
+def _set_weights(learner_eng, net, iteration):
+    """The updated weights into the learner's engine.  The engine refuses weights that are not finite (bk_engine_set_weights,
+    BK_ERR_ARG naming the tensor) and goes on serving the old ones: here that is the end of the run, as in _check_logp."""
+    try:
+        learner_eng.set_weights(engine_weights(net))
+    except ValueError as ex:
+        if "not finite" not in str(ex):
+            raise
+        raise FloatingPointError(f"iteration {iteration}: the update left the policy's weights not finite "
+                                 f"({str(ex).split('not finite: ')[-1]}); the engine keeps the weights it had") from ex
+
+
 def run_epoch(net, opt, learner_eng, opp_eng, n_iters, n_batches, batch_size, seed, epoch, log=None, finish=False):
     """n_iters iterations: play, update, hand the new weights to the learner's engine.  -> wins per batch, in order."""
     wins = []
@@ -416,7 +428,7 @@ def run_epoch(net, opt, learner_eng, opp_eng, n_iters, n_batches, batch_size, se
         t0 = time.perf_counter()
         games = play_games(learner_eng, opp_eng, n_batches, batch_size, seed, iteration=it, epoch=epoch, finish=finish)
         losses = update(net, opt, games, n_batches, batch_size)
-        learner_eng.set_weights(engine_weights(net))
+        _set_weights(learner_eng, net, it)
         w = wins_per_batch(games, n_batches, batch_size)
         wins += w
         if log:

@@ -108,6 +108,10 @@ int bk_device_count(void);
  * Replaces: PolicyNet()/ValueNet() construction + load_state_dict + .eval() + .to(device)
  * (boke.py:30-38, mcts.py:74-76).  Either net may be NULL (not both).  Weights are copied;
  * caller memory is not referenced after return.  max_batch bounds B of every later call.
+ * Weights must be finite: BK_ERR_ARG when any element of any tensor is NaN or +-Inf, or when a BatchNorm variance gives
+ * no finite folded scale (running_var + eps <= 0); bk_last_error(NULL) names the net and the tensor, e.g. "weights are not
+ * finite: policy conv.6.weight".  Checked on the host before any HIP call.  (The kernels' ReLUs are max(v, 0), which
+ * turns a NaN into 0: a net with one NaN weight would otherwise play finite garbage.)
  */
 int bk_engine_create(const bk_policy_weights *policy, const bk_value_weights *value, int device_id,
                      int max_batch, bk_engine **out);
@@ -121,6 +125,8 @@ int bk_engine_destroy(bk_engine *e);
  * packing and the copies happen before the call returns (~10 ms; creating an engine is 40-60 ms: streams, pinned
  * slots); every later request sees the new weights.  No ticket may be outstanding (BK_ERR_ARG), and device-pointer
  * calls the caller enqueued on its own streams must have completed.
+ * Weights that are not finite are refused as bk_engine_create refuses them (BK_ERR_ARG, bk_last_error(e) names the net and
+ * the tensor), before anything is touched: the engine goes on serving the weights it has, bit for bit.
  */
 int bk_engine_set_weights(bk_engine *e, const bk_policy_weights *policy, const bk_value_weights *value);
 
@@ -128,6 +134,8 @@ int bk_engine_set_weights(bk_engine *e, const bk_policy_weights *policy, const b
  * Replaces: policy(fts) / v(fts) on host tensors (nnet.py:272-273, 283-284), batched.
  * feats: host float32 [B,27,9,9]; logits/probs: host [B,81]; values: host [B].
  * Output pointers for bits not in `want` may be NULL.  Synchronous.
+ * Float planes must be finite (the reference's are 0/1 and small counts): with finite weights and finite planes no NaN
+ * arises, and the kernels do not promise to pass on one that is fed in.
  */
 int bk_eval(bk_engine *e, const float *feats, int B, int want, float *logits, float *probs, float *values);
 /* same with uint8 feature planes (4x less PCIe traffic) */

@@ -17,6 +17,26 @@
  *     an order fixed by the shapes alone (no float atomics), so equal inputs give equal bits.
  *   - The bkt_*_bf16 entry points are an opt-in mixed-precision form of the six convolution calls: the same fp32
  *     tensors, bf16 GEMM operands, fp32 accumulate (v_mfma_f32_16x16x32_bf16); see "bf16 mixed precision" below.
+ *   - Non-finite values.  The convolutions and the BatchNorm + ReLU calls pass a NaN or an Inf on; none of them turns
+ *     one into a finite number.  With ref the same operation in float64 (torch: conv2d and its two gradients,
+ *     batch_norm + relu with autograd), for every element of every output:
+ *       - got is finite exactly where ref is finite;
+ *       - where ref is NaN, got is NaN;
+ *       - where ref is +-Inf, got is the same Inf.  The fp32 convolutions may give NaN instead: their compensated
+ *         sums compute (t - acc) - y, which is inf - inf once a running sum is Inf.  The bf16 convolutions (plain
+ *         sums) and the BatchNorm calls give the Inf;
+ *       - where ref is finite and does not depend on the non-finite input, got has the bits of the same call on
+ *         finite inputs: no kernel's summation order depends on values, and a masked load mixes nothing in.
+ *     In particular relu(NaN) is NaN and relu's gradient passes at a NaN output (the mask is "not y <= 0", torch's),
+ *     a channel of bkt_bn_relu_train with one NaN or Inf in x is NaN in all its B*81 outputs, in save_invstd and in
+ *     running_var (the variance is inf - inf; its clamp at 0 is for rounding only), and its save_mean and
+ *     running_mean are the NaN or the Inf.  In the forward convolution zero padding is a multiplication by zero: a non-finite
+ *     weight makes every point of its output channel non-finite, and Inf * 0 is NaN.  The input gradient has no padding to multiply: a
+ *     non-finite weight reaches the points of its channel of dx whose tap lies on the board and no others (the
+ *     GEMM takes such a weight as 0 and a second kernel adds its terms).  An infinite gamma is evaluated in
+ *     torch's form x * a + (beta - mean * a), a = invstd * gamma, which is NaN where x and the mean have one sign.
+ *     tests/nonfinite_cases.py has the cases; what reads the weights for inference refuses non-finite ones instead
+ *     (include/bokego_amd.h, bk_engine_create).
  */
 #ifndef BOKEGO_TRAIN_H
 #define BOKEGO_TRAIN_H
@@ -56,7 +76,8 @@ int bkt_conv_forward(const float *x, const float *wt, const float *bias, float *
 int bkt_conv_pack_dgrad(const float *w, float *wt_dgrad, void *stream);
 
 /* dx = dL/dx of the 3x3 128->128 convolution: the forward problem on dy with the bkt_conv_pack_dgrad filters.
- * dy, dx [B, 128, 9, 9]. */
+ * dy, dx [B, 128, 9, 9].  Two launches: the second adds the terms of weights that are not finite ("Non-finite values")
+ * and returns at once when there are none. */
 int bkt_conv_dgrad(const float *dy, const float *wt_dgrad, float *dx, int batch, void *stream);
 
 /* The batch is reduced in fixed slices of BKT_WGRAD_CHUNK boards: one partial result per slice, then the slices are
@@ -91,7 +112,8 @@ int bkt_conv_wgrad(const float *x, const float *dy, float *dw, float *db, int ba
  * The packed layout is private to the library: allocate bkt_conv_packed_elems_bf16 elements and pass them through. */
 
 /* Number of uint16_t a packed operand of a [128, cin, k, k] weight holds, padding included (0 for unsupported
- * arguments).  bkt_conv_pack_dgrad_bf16 writes bkt_conv_packed_elems_bf16(128, 3). */
+ * arguments).  bkt_conv_pack_dgrad_bf16 writes bkt_conv_packed_elems_bf16(128, 3): for that shape the count includes
+ * a second half, in which the input gradient keeps the weights that are not finite. */
 size_t bkt_conv_packed_elems_bf16(int cin, int ksize);
 
 int bkt_conv_pack_bf16(const float *w, int cin, int ksize, uint16_t *wt, void *stream);
@@ -124,7 +146,7 @@ int bkt_bn_relu_train(const float *x, const float *gamma, const float *beta, flo
                       float *save_invstd, void *workspace, size_t workspace_bytes, int batch, int channels,
                       void *stream);
 
-/* Gradients of bkt_bn_relu_train: dy = dL/dy, y its output (the ReLU mask is y > 0), x its input.
+/* Gradients of bkt_bn_relu_train: dy = dL/dy, y its output (the ReLU mask is y > 0, and open at a NaN y), x its input.
  * Writes dx [B, channels, 9, 9], dgamma and dbeta [channels]. */
 int bkt_bn_relu_backward(const float *dy, const float *y, const float *x, const float *gamma, const float *save_mean,
                          const float *save_invstd, float *dx, float *dgamma, float *dbeta, void *workspace,
@@ -134,7 +156,7 @@ int bkt_bn_relu_backward(const float *dy, const float *y, const float *x, const 
 int bkt_bn_relu_eval(const float *x, const float *gamma, const float *beta, const float *running_mean,
                      const float *running_var, float eps, float *y, int batch, int channels, void *stream);
 
-/* Gradients of bkt_bn_relu_eval (frozen statistics): m = [y > 0], invstd = 1/sqrt(running_var + eps),
+/* Gradients of bkt_bn_relu_eval (frozen statistics): m = [y > 0] (1 at a NaN y), invstd = 1/sqrt(running_var + eps),
  * dx = dy * m * gamma * invstd, dbeta = sum dy * m, dgamma = sum dy * m * (x - running_mean) * invstd.
  * y is bkt_bn_relu_eval's output, x its input.  The sums use per-slice double partials added in slice order, as
  * bkt_bn_relu_backward does, in a bkt_bn_workspace(batch, channels) scratch.  Writes dx [B, channels, 9, 9],

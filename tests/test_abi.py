@@ -92,6 +92,49 @@ def test_no_cpu_fallback_without_gpu(lib):
         LeafEngine(load_bkw(os.path.join(GOLDEN, "policy_19.bkw")), None)
 
 
+def _create(lib, policy_sd, value_sd):
+    """bk_engine_create on the state_dicts -> (status, message); an engine that did come to life is destroyed again"""
+    from bokego_amd.engine import LeafEngine
+    pw, vw, keep = LeafEngine._weight_structs(policy_sd, value_sd)
+    h = ctypes.c_void_p()
+    rc = lib.bk_engine_create(ctypes.byref(pw) if pw is not None else None, ctypes.byref(vw) if vw is not None else None,
+                              0, 16, ctypes.byref(h))
+    msg = lib.bk_last_error(None).decode()
+    if rc == 0:
+        lib.bk_engine_destroy(h)
+    return rc, msg
+
+
+@pytest.mark.parametrize("net", ["policy", "value"])
+def test_create_refuses_weights_that_are_not_finite(lib, net):
+    """Every tensor of bk_policy_weights / bk_value_weights, a NaN, a +Inf and a -Inf in its first or its last element:
+    BK_ERR_ARG naming the net and the tensor, before any HIP call -- so also on a box without a GPU, where the clean weights
+    get as far as BK_ERR_NO_GPU.  The kernels' ReLUs are max(v, 0), which would turn such a weight into finite garbage."""
+    from bokego_amd.bkw import load_bkw
+    sd = load_bkw(os.path.join(GOLDEN, "policy_19.bkw" if net == "policy" else "value_synth.bkw"))
+    args = (lambda d: (d, None)) if net == "policy" else (lambda d: (None, d))
+    clean = 0 if lib.bk_device_count() > 0 else -6                      # BK_OK, or BK_ERR_NO_GPU: the weights passed
+    assert _create(lib, *args(sd))[0] == clean
+    names = [k for k in sd if not k.endswith("num_batches_tracked")]
+    assert len(names) == (44 if net == "policy" else 56)                 # every pointer of the struct (test_struct_layout...)
+    bad = []
+    for i, name in enumerate(names):
+        for j, value in enumerate((np.nan, np.inf, -np.inf)):
+            a = np.array(sd[name], np.float32)
+            a.reshape(-1)[0 if (i + j) % 2 == 0 else -1] = value
+            rc, msg = _create(lib, *args({**sd, name: a}))
+            if rc != -1 or not msg.endswith(f"{net} {name}"):
+                bad.append((name, value, rc, msg))
+    assert not bad, bad
+    # a folded BatchNorm scale gamma / sqrt(var + eps) must be finite: var + eps > 0
+    for name in [k for k in names if k.endswith("running_var")]:
+        for value, want in ((-1.0, -1), (-2e-5, -1), (0.0, clean)):
+            a = np.array(sd[name], np.float32)
+            a.reshape(-1)[-1] = value
+            rc, msg = _create(lib, *args({**sd, name: a}))
+            assert rc == want and (rc != -1 or msg.endswith(f"{net} {name}")), (name, value, rc, msg)
+
+
 def test_state_dict_validation(lib):
     from bokego_amd.bkw import load_bkw
     from bokego_amd.engine import LeafEngine
