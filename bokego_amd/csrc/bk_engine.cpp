@@ -208,6 +208,9 @@ struct bk_engine {
     CopyPool* copy_pool = nullptr;      // created by the first large host-buffer request
     std::vector<void*> dev_allocs;
     bk_net_params net[2]{};
+    // f16x2: does the net's folded trunk fit fp16 at the smallest per-layer exponent (pack_trunk16)?  A net that does not is
+    // served by the fp32 kernel (request_precision)
+    bool fits16[2] = {true, true};
     Slot slots[BK_MAX_INFLIGHT];
     int64_t next_ticket = 1;
     std::string err;
@@ -329,8 +332,13 @@ void pack_trunk(const bk_trunk_weights& t, std::vector<float>& wfrag, std::vecto
 // conv_layer16<> (bk_kernels_f16.hip):
 //   index = (((ks*4 + ntile)*2 + piece)*64 + lane)*8 + j,  ks = tap*S + s
 //   cout = 32*ntile + (lane&31), cin = 16s + 8(lane>>5) + j
+// The per-layer exponent is clamped to [-14, 24].  At the upper clamp (largest folded |w| below 2^-9) the layer only uses less
+// of the fp16 range.  At the lower one (above 2^29) a weight of 2^30 or more has no fp16 value: its hi half would be +-Inf, its
+// lo half the opposite Inf, and the matrix unit would make a NaN of it that the kernel's ReLU turns into a 0.  -> false for
+// such a net: the engine serves it on the fp32 kernel (request_precision), and what is packed here is never read.
 constexpr float kSa16 = 16.f;  // activation scale (power of two): |activation| < 65504/16 representable
-void pack_trunk16(const bk_trunk_weights& t, std::vector<_Float16>& wfrag, std::vector<float>& bias16, float* cscale) {
+bool pack_trunk16(const bk_trunk_weights& t, std::vector<_Float16>& wfrag, std::vector<float>& bias16, float* cscale) {
+    bool fits = true;
     wfrag.assign(BK16_WFRAG_HALFS + BK16_WFRAG_PAD_HALFS, (_Float16)0.f);
     bias16.assign(7 * 128, 0.f);
     size_t base = 0;
@@ -357,6 +365,7 @@ void pack_trunk16(const bk_trunk_weights& t, std::vector<_Float16>& wfrag, std::
                             double w = 0;
                             if (ci < cin) w = (double)t.conv_w[l][((size_t)co * cin + ci) * TAPS + tp] * scale[co] * sw;
                             const _Float16 hi = (_Float16)w;
+                            fits = fits && std::isfinite((float)hi);
                             const _Float16 lo = (_Float16)(w - (double)hi);
                             const size_t ks = (size_t)tp * S + sidx;
                             const size_t at = base + (((ks * 4 + nt) * 2) * 64 + lane) * 8 + j;
@@ -365,6 +374,7 @@ void pack_trunk16(const bk_trunk_weights& t, std::vector<_Float16>& wfrag, std::
                         }
         base += l == 0 ? BK16_L0_HALFS : BK16_L3_HALFS;
     }
+    return fits;
 }
 
 // a fresh device buffer holding h; recorded in `fresh` (the caller owns it until the whole set of weights is in place)
@@ -378,7 +388,7 @@ int upload(bk_engine* e, const std::vector<T>& h, const T** out, std::vector<voi
     return BK_OK;
 }
 
-int setup_trunk(bk_engine* e, const bk_trunk_weights& t, bk_net_params& np, double head_scale, double head_shift, std::vector<void*>& fresh) {
+int setup_trunk(bk_engine* e, const bk_trunk_weights& t, bk_net_params& np, bool& fits16, double head_scale, double head_shift, std::vector<void*>& fresh) {
     std::vector<float> wfrag, bias, hw(128), hb(81);
     pack_trunk(t, wfrag, bias);
     // Conv2dUntiedBias (nnet.py:175-180); for the value net BatchNorm2d(1) is folded in:
@@ -387,7 +397,7 @@ int setup_trunk(bk_engine* e, const bk_trunk_weights& t, bk_net_params& np, doub
     for (int q = 0; q < 81; ++q) hb[q] = (float)((double)t.head_b[q] * head_scale + head_shift);
     std::vector<_Float16> w16;
     std::vector<float> b16;
-    pack_trunk16(t, w16, b16, np.cscale16);
+    fits16 = pack_trunk16(t, w16, b16, np.cscale16);
     np.inv_sa16 = 1.f / kSa16;
     int rc;
     if ((rc = upload(e, wfrag, &np.wfrag, fresh))) return rc;
@@ -479,19 +489,20 @@ std::vector<const void*> net_buffers(const bk_net_params& np) {
 // a mixture of old and new weights.  The caller has made sure nothing on the device still reads the old buffers.
 int load_weights(bk_engine* e, const bk_policy_weights* policy, const bk_value_weights* value) {
     bk_net_params np[2] = {e->net[0], e->net[1]};
+    bool fits16[2] = {e->fits16[0], e->fits16[1]};
     std::vector<void*> fresh;
     auto build = [&]() -> int {
         int rc;
         if (policy) {
             np[0] = bk_net_params{};
-            if ((rc = setup_trunk(e, policy->trunk, np[0], 1.0, 0.0, fresh))) return rc;
+            if ((rc = setup_trunk(e, policy->trunk, np[0], fits16[0], 1.0, 0.0, fresh))) return rc;
         }
         if (value) {
             np[1] = bk_net_params{};
             const bk_value_head_weights& h = value->head;
             const double s = (double)h.bn_w[0] / std::sqrt((double)h.bn_var[0] + kBnEps);
             const double shift = (double)h.bn_b[0] - (double)h.bn_mean[0] * s;
-            if ((rc = setup_trunk(e, value->trunk, np[1], s, shift, fresh))) return rc;
+            if ((rc = setup_trunk(e, value->trunk, np[1], fits16[1], s, shift, fresh))) return rc;
             // lin1 (64,81) + BatchNorm1d(64) folded, stored transposed [81][64] for coalesced reads
             std::vector<float> w1t(81 * 64), b1(64), w2(64);
             for (int j = 0; j < 64; ++j) {
@@ -520,6 +531,7 @@ int load_weights(bk_engine* e, const bk_policy_weights* policy, const bk_value_w
             (void)hipFree(const_cast<void*>(old));
         }
         e->net[i] = np[i];
+        e->fits16[i] = fits16[i];
     }
     e->dev_allocs.insert(e->dev_allocs.end(), fresh.begin(), fresh.end());
     return BK_OK;
@@ -571,6 +583,15 @@ int check_want(bk_engine* e, int B, int n_policy, int want) {
     if ((want & BK_WANT_VALUE) && !e->has_value)
         return fail(e, BK_ERR_NO_NET, "value requested but the engine has no ValueNet");
     return BK_OK;
+}
+
+// The arithmetic one request runs in: the engine's -- but an f16x2 engine serves a request that asks anything of a net whose
+// folded weights do not fit fp16 (pack_trunk16) on the fp32 kernel, the whole request, so that it stays one launch plan.  The
+// caller counts such a request where it counts the redone ones (f16_overflow_fallbacks / f16_device_overflow).
+int request_precision(const bk_engine* e, int B, int n_policy, int want) {
+    if (e->precision != BK_PRECISION_F16X2) return e->precision;
+    const bool policy = (want & (BK_WANT_LOGITS | BK_WANT_PROBS)) && n_policy > 0, value = (want & BK_WANT_VALUE) && B > 0;
+    return (policy && !e->fits16[0]) || (value && !e->fits16[1]) ? BK_PRECISION_F32 : BK_PRECISION_F16X2;
 }
 
 // a redo word that changed since it was last looked at = one more device-path call redone in fp32 (called by the submitting
@@ -976,7 +997,9 @@ int64_t submit_body(bk_engine* e, Slot* s, const void* src, int src_kind, int B,
     // reads after the request's event.  Two of the five enqueues and ~12 us of copy kernels per round trip disappear
     // (rocprofv3 timeline, profiles/r03_genmove_timeline.md).  fp32 only: the f16x2 kernel's overflow flag is raised with
     // an atomic max, which is not used on host memory here.  Option no_direct = 1 restores the copies.
-    const bool direct = !chained && B > 0 && e->precision == BK_PRECISION_F32 && s->h_in_dev && s->h_out_dev && !e->no_direct;
+    const int precision = request_precision(e, B, n_policy, want);
+    if (precision != e->precision) bump(e->st.f16_overflow_fallbacks);   // a net that does not fit fp16: fp32 from the start
+    const bool direct = !chained && B > 0 && precision == BK_PRECISION_F32 && s->h_in_dev && s->h_out_dev && !e->no_direct;
     s->direct = direct;
     if (B > 0) {
         void* d_dst = src_kind == kSrcPositions ? s->d_pos : s->d_in;
@@ -1064,16 +1087,16 @@ int64_t submit_body(bk_engine* e, Slot* s, const void* src, int src_kind, int B,
         float* o_probs = reinterpret_cast<float*>(out_base + s->off_probs);
         float* o_values = reinterpret_cast<float*>(out_base + s->off_values);
         if (two_part) {
-            rc = enqueue(e, s->d_in, dtype, B, n_policy, want, o_logits, o_probs, o_values, e->stream, e->precision, d_flag, 1, false,
+            rc = enqueue(e, s->d_in, dtype, B, n_policy, want, o_logits, o_probs, o_values, e->stream, precision, d_flag, 1, false,
                          false, 0, kHeadRows);
             if (rc) return rc;
             if ((rc = stage((size_t)kHeadRows * row_bytes, bytes))) return rc;       // ... while the first part runs
             HIP_TRY(e, hipEventRecord(s->in_ready, e->s_in));
             HIP_TRY(e, hipStreamWaitEvent(e->stream, s->in_ready, 0));
-            rc = enqueue(e, s->d_in, dtype, B, n_policy, want, o_logits, o_probs, o_values, e->stream, e->precision, d_flag, 1, false,
+            rc = enqueue(e, s->d_in, dtype, B, n_policy, want, o_logits, o_probs, o_values, e->stream, precision, d_flag, 1, false,
                          false, kHeadRows, B);
         } else {
-            rc = enqueue(e, d_feats, dtype, B, n_policy, want, o_logits, o_probs, o_values, e->stream, e->precision, d_flag, 1, false,
+            rc = enqueue(e, d_feats, dtype, B, n_policy, want, o_logits, o_probs, o_values, e->stream, precision, d_flag, 1, false,
                          /*allow_coop=*/true);
         }
         if (rc) return rc;
@@ -1217,9 +1240,11 @@ int bk_eval_device_prefix(bk_engine* e, const void* d_feats, int feats_dtype, in
         std::lock_guard<std::mutex> g(e->ev_m);
         fold_redo(e, e->dev_seq % BK_DEV_FLAGS);
     }
-    if (e->precision == BK_PRECISION_F16X2 && B > 0) HIP_TRY(e, hipMemsetAsync(flag, 0, sizeof(unsigned int), static_cast<hipStream_t>(stream)));
+    const int precision = request_precision(e, B, n_policy, want);
+    if (precision != e->precision) bump(e->st.f16_device_overflow);   // a net that does not fit fp16: the fp32 kernel alone
+    if (precision == BK_PRECISION_F16X2 && B > 0) HIP_TRY(e, hipMemsetAsync(flag, 0, sizeof(unsigned int), static_cast<hipStream_t>(stream)));
     return enqueue(e, d_feats, feats_dtype, B, n_policy, want, d_logits, d_probs, d_values,
-                   static_cast<hipStream_t>(stream), e->precision, flag, e->dev_seq, true);
+                   static_cast<hipStream_t>(stream), precision, flag, e->dev_seq, true);
 }
 
 int bk_engine_set_precision(bk_engine* e, int precision) {

@@ -328,7 +328,7 @@ __global__ void __launch_bounds__(256) bk_leaf_eval_f16_kernel(const bk_eval_arg
     // ---- stage the feature planes as fp16 hi/lo: NCHW global -> [pos][hi 4x8 | lo 4x8] ----
     for (int i = tid; i < G::NP0 * 8; i += 256) reinterpret_cast<f32x4*>(actb)[i] = f32x4{0.f, 0.f, 0.f, 0.f};
     __syncthreads();
-    bool inexact = false;
+    bool inexact = false, unfit = false;
     if (tid < nb * 81) {
         // one thread per position: 27 channel loads (coalesced across threads: consecutive points of a
         // plane), split into fp16 hi/lo, stored as 4 groups x (16 B hi + 16 B lo)
@@ -354,12 +354,19 @@ __global__ void __launch_bounds__(256) bk_leaf_eval_f16_kernel(const bk_eval_arg
                 hi[j] = (_Float16)v[8 * g + j];
                 lo[j] = (_Float16)(v[8 * g + j] - (float)hi[j]);
                 inexact |= lo[j] != (_Float16)0.f;
+                unfit |= !(fabsf(v[8 * g + j]) < 65520.f);
             }
             char* d = actb + p * 128 + ((g ^ ((p >> 1) & 3)) << 4);
             *reinterpret_cast<f16x8*>(d) = hi;
             *reinterpret_cast<f16x8*>(d + 64) = lo;
         }
     }
+    // A float plane without an fp16 value (|v| >= 65520, or not finite) has hi = +-Inf and lo = -+Inf, and the matrix unit makes a NaN
+    // of them.  The epilogue's flag is a running fmaxf, which drops a NaN, and its ReLU turns one into 0: so the flag rises here, and
+    // the request is redone in fp32 like one whose activations overflowed.  With weights that fit fp16 (pack_trunk16; the engine keeps
+    // other nets off this kernel) this is the only way to a NaN: activations are clamped to 65504, and 3 x 1152 products of two fp16
+    // values stay far inside fp32.
+    if (__any(unfit) && lane == 0 && a.overflow) atomicMax(a.overflow, a.overflow_tag);
     // barrier + workgroup-wide OR: does any input need its lo half?
     const bool need_lo = __syncthreads_or(inexact ? 1 : 0) != 0;
 

@@ -112,6 +112,15 @@ int bk_device_count(void);
  * no finite folded scale (running_var + eps <= 0); bk_last_error(NULL) names the net and the tensor, e.g. "weights are not
  * finite: policy conv.6.weight".  Checked on the host before any HIP call.  (The kernels' ReLUs are max(v, 0), which
  * turns a NaN into 0: a net with one NaN weight would otherwise play finite garbage.)
+ * Weight domain: every finite net that passes this check is served, at both precisions, with the accuracy stated for the
+ * trained ones -- BatchNorm scales of either sign, of 0, of gamma / sqrt(eps) (running_var = 0), per-channel scales that
+ * differ by 2^11 and more, layers that are all zero (tests/weight_cases.py).  The fp32 kernel computes all of them itself.  The
+ * f16x2 kernel scales each layer's folded weights by one power of two, 2^el with el in [-14, 24], into the fp16 hi/lo range: a
+ * net with a folded trunk weight of 2^30 or more (gamma / sqrt(running_var + eps) times the conv weight) has no such
+ * exponent, and an f16x2 engine hands EVERY request that asks anything of that net to the fp32 kernel -- the whole request,
+ * counted in f16_overflow_fallbacks / f16_device_overflow like a request redone after an overflow.  Nets below that are packed
+ * as before, bit for bit; where their activations leave the fp16 range the kernel's flag does the same per request (below).
+ * Not checked: a folded weight or bias beyond fp32's own range (|gamma / sqrt(var + eps) * w| > 3.4e38).
  */
 int bk_engine_create(const bk_policy_weights *policy, const bk_value_weights *value, int device_id,
                      int max_batch, bk_engine **out);
@@ -205,7 +214,9 @@ int bk_encode_positions(bk_engine *e, const void *positions, int B, uint8_t *pla
  *                       (bk_stats().f16_overflow_fallbacks), and for bk_eval_device* by an fp32 launch enqueued
  *                       behind the f16x2 one on the caller's stream that is a no-op unless the flag was raised
  *                       (bk_stats().f16_device_overflow counts the calls redone).  Either way the caller never
- *                       sees a clamped result.
+ *                       sees a clamped result.  A float plane without an fp16 value (|x| >= 65520) raises the same
+ *                       flag when it is staged.  A net whose folded weights do not fit fp16 never reaches this
+ *                       kernel (bk_engine_create, "Weight domain").
  * The environment variable BK_PRECISION=f32|f16x2 sets the default of new engines.
  */
 #define BK_PRECISION_FP32 0
