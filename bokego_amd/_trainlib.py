@@ -72,6 +72,9 @@ SYMBOLS = {
     "bkt_move_value_playouts_tables": (_I, [_P, _I, _U64, _P, _P, _P, _P, _P, _P, _I, _P, _I, _P, _P, _P, _P, _P]),
     "bkt_move_value_tables_scratch_bytes": (_Z, [_I, _I]),
     "bkt_move_value_update_tables": (_I, [_P, _P, _I, _P, _I, _I, _P, _P, _P, _I, _I, _I, _P, _P, _P]),
+    "bkt_move_context_playouts": (_I, [_P, _I, _U64, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P]),
+    "bkt_move_context_scratch_bytes": (_Z, [_I]),
+    "bkt_move_context_update": (_I, [_P, _P, _I, _P, _I, _I, _P, _P, _P, _I, _I, _I, _P, _P]),
 }
 MAX_BATCH = 65536          # BKT_MAX_BATCH
 PRECISIONS = ("fp32", "bf16")
@@ -763,6 +766,71 @@ def move_value_update(pos, moves, won, records, playouts, counts, values, lut, k
                                  _dev(won, "won", (records * playouts,), torch.uint8), records, playouts,
                                  _dev(counts, "counts", shape, torch.int64), v, _dev(lut, "lut", (65,), torch.int16),
                                  k, limit, *extra, _dev(scratch, "scratch", dtype=torch.uint8), _stream(moves)), name)
+    return counts, values
+
+
+MOVE_CONTEXT_MAX_MIN_PLAYS = 1 << 30   # BKT_MOVE_CONTEXT_MAX_MIN_PLAYS
+
+
+def _move_contexts(values, dev, what):
+    if not isinstance(values, torch.Tensor) or values.device != dev:
+        raise ValueError(f"values must be int16 [2, 82, 81] (the bits of the uint16 entries) on the device of {what}")
+    return _dev(values, "values", (2, 82, 81), torch.int16)
+
+
+def move_context_scratch_bytes(records):
+    """bkt_move_context_scratch_bytes: the bytes of move_context_update's scratch (0 when records < 1)."""
+    return int(load().bkt_move_context_scratch_bytes(int(records)))
+
+
+def move_context_playouts(pos, seed, counters, table, tactics, values, max_plies, over=None, history=True, replies=None,
+                          replies2=None):
+    """move_value_playouts whose factor is keyed by the previous move as well (bkt_move_context_playouts;
+    include/bokego_train.h has the rule): values int16 [2,82,81] on the device of pos, the bits of the uint16 entries (256:
+    neutral), read only, plane 81 being move_value_playouts' table; one table for all rows.  table, tactics, replies and
+    replies2: as move_value_playouts takes them, at most one of the last two (ValueError)."""
+    weights = _weight_tables(pos, table, tactics)
+    if replies is not None and replies2 is not None:
+        raise ValueError("at most one of replies and replies2 may be given: a pair table contains the single one")
+    v = _move_contexts(values, pos.device, "pos")
+    r1 = None if replies is None else _reply_tables(replies, None, _pos_batch(pos), pos.device, "pos")[1][0]
+    r2 = None if replies2 is None else _reply2_table(replies2, pos.device, "pos")
+    return _playouts("bkt_move_context_playouts", pos, seed, counters, (*weights, v, r1, r2), max_plies, over, history)
+
+
+def move_context_update(pos, moves, won, records, playouts, counts, values, lut, k, limit, min_plays, scratch=None):
+    """Fold a batch of playouts into a move-context table, in place (bkt_move_context_update; include/bokego_train.h has the
+    rule): move_value_update's arguments with counts int64 [2,82,81,2] and values int16 [2,82,81], and min_plays
+    1..MOVE_CONTEXT_MAX_MIN_PLAYS, the plays a context entry needs before it counts.  scratch: None (allocated here) or a
+    uint8 tensor of at least bkt_move_context_scratch_bytes(records) bytes, 8-byte aligned.  Three launches on the current
+    stream; nothing waits.  -> (counts, values)."""
+    records, playouts, max_plies = _amaf_args(moves, won, records, playouts)
+    if not isinstance(pos, torch.Tensor) or tuple(pos.shape) != (records, POS_BYTES) or pos.device != moves.device:
+        raise ValueError(f"pos must be [{records}, {POS_BYTES}] on the device of moves")
+    k, limit, min_plays = int(k), int(limit), int(min_plays)
+    if not 1 <= k <= MOVE_VALUE_MAX_K:
+        raise ValueError(f"k must be 1..{MOVE_VALUE_MAX_K}, got {k}")
+    if limit != 0 and not 2 <= limit <= MOVE_VALUE_MAX_LIMIT:
+        raise ValueError(f"limit must be 0 or 2..{MOVE_VALUE_MAX_LIMIT}, got {limit}")
+    if not 1 <= min_plays <= MOVE_CONTEXT_MAX_MIN_PLAYS:
+        raise ValueError(f"min_plays must be 1..{MOVE_CONTEXT_MAX_MIN_PLAYS}, got {min_plays}")
+    if playouts * max_plies >= 2 ** 31:
+        raise ValueError("playouts * max_plies must be below 2^31, as for move_value_update")
+    for t, name in ((counts, "counts"), (lut, "lut")):
+        if not isinstance(t, torch.Tensor) or t.device != moves.device:
+            raise ValueError(f"{name} must be on the device of moves")
+    v = _move_contexts(values, moves.device, "moves")
+    need = load().bkt_move_context_scratch_bytes(records)
+    if scratch is None:
+        scratch = torch.empty((need,), dtype=torch.uint8, device=moves.device)
+    elif not isinstance(scratch, torch.Tensor) or scratch.device != moves.device or scratch.dim() != 1 or scratch.numel() < need:
+        raise ValueError(f"scratch must be uint8 [>= {need}] on the device of moves")
+    _check(load().bkt_move_context_update(_dev(pos, "pos", dtype=torch.uint8), _dev(moves, "moves", dtype=torch.int16), max_plies,
+                                          _dev(won, "won", (records * playouts,), torch.uint8), records, playouts,
+                                          _dev(counts, "counts", (2, 82, 81, 2), torch.int64), v,
+                                          _dev(lut, "lut", (65,), torch.int16), k, limit, min_plays,
+                                          _dev(scratch, "scratch", dtype=torch.uint8), _stream(moves)),
+           "bkt_move_context_update")
     return counts, values
 
 

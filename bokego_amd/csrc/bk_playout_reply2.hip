@@ -207,3 +207,5 @@ extern "C" int bkt_reply2_update(const void* pos, const int16_t* moves, int max_
     hipLaunchKernelGGL(lgr2_finish_kernel, entries, dim3(256), 0, s, keys, flags, replies2);
     return hipGetLastError() == hipSuccess ? BKT_OK : BKT_ERR_HIP;
 }
+
+#include "bk_playout_nast.hip" // move values keyed by the previous move (NAST): text, behind the entry points above

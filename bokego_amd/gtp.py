@@ -194,7 +194,7 @@ class _GTPProtocol:
         if replies is not None:                                      # --playout-replies: a new game learns its own replies
             replies.clear()
         move_values = getattr(getattr(self, "evaluator", None), "move_values", None)
-        if move_values is not None:                                  # --playout-move-values: and its own move values
+        if move_values is not None:                                  # --playout-move-values / -contexts: and its own move values
             move_values.clear()
         return True, ""
 

@@ -156,7 +156,11 @@ class NativeMCTS:
     `playout_move_values=tau` (> 0, with playout_value): MAST -- the evaluator keeps a movevalues.MoveValueTable of that
     temperature, `evaluator.move_values`, a win rate per colour and point that the playouts of this search's requests draw
     with and update in submit order (untuned); with or without either reply table.  Determinism, deepcopy and
-    pickle are as for playout_replies."""
+    pickle are as for playout_replies;
+    `playout_move_contexts=tau` (> 0, with playout_value; not with playout_move_values): NAST -- the same with a
+    movecontexts.MoveContextTable in `evaluator.move_values`, a win rate per colour, previous move and point whose plane 81
+    is the move-value table (untuned); with or without either reply table.  Determinism, deepcopy and pickle
+    are as for playout_replies."""
 
     def __init__(self, root=None, policy_net=None, value_net=None, **kwargs):
         # OPT-IN, not the reference's search: playout_value=N > 0 -- no value net; a leaf's value is the share of N uniformly
@@ -311,7 +315,7 @@ class NativeMCTS:
                 setattr(new, k, copy.deepcopy(v, memo))
         new.policy_net, new.value_net, new.evaluator = self.policy_net, self.value_net, self.evaluator
         if getattr(self, "playout_replies", False) or getattr(self, "playout_reply_pairs", False) \
-                or getattr(self, "playout_move_values", 0.0):
+                or getattr(self, "playout_move_values", 0.0) or getattr(self, "playout_move_contexts", 0.0):
             # a reply table, a move-value table of its own, empty (class docstring)
             new.evaluator = new._playout_evaluator(self.policy_net)
             new.evaluator.komi = self.evaluator.komi

@@ -7,7 +7,7 @@ and NativeMCTS as keywords, declared once, checked once, and turned into the key
     .search_keywords()                          the keywords of NativeMCTS / NativeGTP: only the options that are set
     .evaluator_keywords()                       the keywords of rollout.PlayoutEvaluator
     .name_suffix()                              what match calls such an engine: -mc64-pat-amaf1-rave4-lgr (-lgr2 with pairs,
-                                                -mast with move values)
+                                                -mast with move values, -nast with move contexts)
 
 Nothing here imports torch or rollout: a front end parses its command line before it loads either.
 """
@@ -47,13 +47,18 @@ FLAGS = {  # field -> (flag, what argparse needs, help)
     "playout_reply_pairs": ("--playout-reply-pairs", dict(action="store_true"),
                             "with --playout-value: as --playout-replies with replies keyed by the last two moves as well, the "
                             "single-move table being the fallback (LGRF-2; untuned; default off, DESIGN 26)"),
+    "playout_move_contexts": ("--playout-move-contexts", dict(type=float, nargs="?", const=0.25, default=0.0, metavar="TAU"),
+                              "with --playout-value: NAST -- as --playout-move-values with a win rate per colour, previous move "
+                              "and point as well, averaged with the plain one once it has 8 plays and falling back to it before "
+                              "(TAU 0.25 when no value is given: plausible and untuned; not with --playout-move-values; default "
+                              "0: off, DESIGN 32)"),
     "playout_move_values": ("--playout-move-values", dict(type=float, nargs="?", const=0.25, default=0.0, metavar="TAU"),
                             "with --playout-value: MAST -- the playouts of a search learn a win rate per colour and point from "
                             "each other, and a point's weight in their draw is multiplied by exp((rate - 1/2) / TAU) (0.25 when "
                             "no value is given, with 16 virtual plays and counts halved at 16384: plausible and untuned; "
                             "default 0: off, DESIGN 30)"),
 }
-LATE = ("playout_move_values", "playout_reply_pairs", "playout_replies")   # the fields that are none of the constructor's
+LATE = ("playout_move_contexts", "playout_move_values", "playout_reply_pairs", "playout_replies")   # the fields that are none of the constructor's
 
 
 @dataclasses.dataclass
@@ -69,6 +74,9 @@ class PlayoutOptions:
     playout_pattern_prior: float = 0.0  # 0: no pattern term in the prior
     prior_patterns: object = None       # the tables of that term; None: the playouts' own
     prior_tactics: object = None
+    # 0: no move-context table, else its temperature tau; in playout_move_values' form, and in front of it so that
+    # the order of the fields before and the last three are what they were.
+    playout_move_contexts: float = dataclasses.field(default=0.0, init=False)
     # 0: no move-value table, else its temperature tau; in playout_replies' form, and in front of the two reply
     # fields so that the order of the fields before and the last two are what they were.
     playout_move_values: float = dataclasses.field(default=0.0, init=False)
@@ -126,6 +134,7 @@ class PlayoutOptions:
         self.playout_replies = bool(kwargs.get("playout_replies"))
         self.playout_reply_pairs = bool(kwargs.get("playout_reply_pairs"))
         self.playout_move_values = float(kwargs.get("playout_move_values") or 0.0)
+        self.playout_move_contexts = float(kwargs.get("playout_move_contexts") or 0.0)
         self.check(str, fail)
         return self
 
@@ -135,12 +144,16 @@ class PlayoutOptions:
         value, prior = name("playout_value"), name("playout_prior")
         if self.playout_value < 0:
             fail(ValueError, f"{value} must not be negative")
-        if not 0.0 <= self.playout_move_values < float("inf"):               # (before `given`: a NaN is truthy)
-            fail(ValueError, f"{name('playout_move_values')} must be a finite number, 0 or more")
+        for field in ("playout_move_values", "playout_move_contexts"):       # (before `given`: a NaN is truthy)
+            if not 0.0 <= getattr(self, field) < float("inf"):
+                fail(ValueError, f"{name(field)} must be a finite number, 0 or more")
         for field in ("playout_patterns", "playout_tactics", "playout_prior", "playout_rave", "playout_replies",
-                      "playout_reply_pairs", "playout_move_values"):
+                      "playout_reply_pairs", "playout_move_values", "playout_move_contexts"):
             if self.given(field) and not self.playout_value:
                 fail(TypeError, f"{name(field)} goes with the playouts of {value}: it needs {value}")
+        if self.playout_move_contexts and self.playout_move_values:
+            fail(TypeError, f"{name('playout_move_contexts')} contains the move-value table (its plane 81): it goes without "
+                            f"{name('playout_move_values')}")
         if not 0.0 <= self.playout_prior <= 1.0:
             fail(ValueError, f"{prior} must be within 0..1")
         for field in ("playout_rave", "playout_criticality", "playout_pattern_prior"):
@@ -163,7 +176,8 @@ class PlayoutOptions:
         """The keywords of NativeMCTS / NativeGTP: the options that are set, and no others."""
         more = {f: getattr(self, f) for f in ("playout_value", "playout_patterns", "playout_tactics", "playout_prior",
                                               "playout_rave", "playout_criticality", "playout_replies",
-                                              "playout_reply_pairs", "playout_move_values") if self.given(f)}
+                                              "playout_reply_pairs", "playout_move_values", "playout_move_contexts")
+                if self.given(f)}
         if self.playout_pattern_prior:
             more.update(playout_pattern_prior=self.playout_pattern_prior, prior_patterns=self.prior_patterns,
                         prior_tactics=self.prior_tactics)
@@ -180,6 +194,8 @@ class PlayoutOptions:
             more["replies"] = 2 if self.playout_reply_pairs else True        # pairs contain singles
         if self.playout_move_values:
             more["move_values"] = self.playout_move_values
+        if self.playout_move_contexts:
+            more["move_contexts"] = self.playout_move_contexts
         if self.playout_pattern_prior:
             more.update(pattern_prior=self.playout_pattern_prior, prior_patterns=self.prior_patterns,
                         prior_tactics=self.prior_tactics)
@@ -187,10 +203,10 @@ class PlayoutOptions:
 
     def name_suffix(self):
         """-mc64, then -pat with a playout table, -amaf, -rave, -crit, -pp with their parameters for the terms that are on, and
-        -lgr with the reply table, -lgr2 when it is keyed by the last two moves, -mast with the move-value table."""
+        -lgr with the reply table, -lgr2 when it is keyed by the last two moves, -mast with the move-value table, -nast with the move-context table."""
         name = f"-mc{self.playout_value}" + ("-pat" if self.given("playout_patterns") or self.given("playout_tactics") else "")
         for tag, x in (("amaf", self.playout_prior), ("rave", self.playout_rave), ("crit", self.playout_criticality),
                        ("pp", self.playout_pattern_prior)):
             name += f"-{tag}{x:g}" if x else ""
         name += "-lgr2" if self.playout_reply_pairs else "-lgr" if self.playout_replies else ""
-        return name + ("-mast" if self.playout_move_values else "")
+        return name + ("-mast" if self.playout_move_values else "") + ("-nast" if self.playout_move_contexts else "")

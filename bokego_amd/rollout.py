@@ -81,6 +81,9 @@ bkt_move_value_update), alone or under either reply table; PlayoutEvaluator(move
 A movevalues.MoveValueTables with slots= is a move-value table per game of a batch (bkt_move_value_playouts_tables,
 bkt_move_value_update_tables; DESIGN 31), alone or beside a ReplyTables or a ReplyTables2 named by the same slots;
 PlayoutEvaluator(move_value_games=G) keeps G of them.
+A movecontexts.MoveContextTable as move_values= keys the same factor by the previous move as well (NAST): its
+plane 81 is the move-value table, the calls are bkt_move_context_playouts and bkt_move_context_update, alone or under
+a ReplyTable or a ReplyTable2 and never with slots=; PlayoutEvaluator(move_contexts=True) keeps one (opt-in, untuned).
 
     python -m bokego_amd.rollout --sgf FILE [--move K] --random --move-values [-n 256] [--chunk 16]   # what the table learned
 
@@ -101,6 +104,7 @@ from . import go
 from . import lockstep as L
 from .lockstep import playable_host, record_turns  # noqa: F401  (public here: see __all__)
 from .movevalues import DEFAULT_TAU, MoveValueTable, MoveValueTables, move_value_update_host, move_value_weights
+from .movecontexts import MoveContextTable, move_context_update_host, move_context_weights
 from .replies import (ReplyTable, ReplyTable2, ReplyTables, ReplyTables2, reply2_moves, reply2_plies_of, reply2_update_host, reply_moves, reply_plies_of,
                       reply_update_host, slots_of)
 
@@ -361,7 +365,8 @@ def _random_host(pos, key, ctr, max_plies, komi, history, table=None, tactics=No
     ReplyTables2 likewise, slots naming the pair table of every row.
     move_values (a MoveValueTable, read only here): the weights of the draw above -- 256 everywhere without
     tables -- go through movevalues.move_value_weights with the values as they stand on entry and the colour to move; with a
-    MoveValueTables, slots names the table of every row, the same slot as its reply table's."""
+    MoveValueTables, slots names the table of every row, the same slot as its reply table's; with a
+    MoveContextTable they go through movecontexts.move_context_weights with the row's last move."""
     def choose(k, recs, live, ok, x0):
         n = ok.sum(1)
         pick = np.argmax(np.cumsum(ok, 1) > select_index(x0, n).astype(np.int64)[:, None], 1)
@@ -379,6 +384,9 @@ def _random_host(pos, key, ctr, max_plies, komi, history, table=None, tactics=No
         part = recs[live]
         entries = None if table is None else table.entries(PT.codes_host(part))
         t = np.full(ok.shape, TC.NEUTRAL, np.uint16) if tactics is None else tactics.entries(TC.codes_host(part))
+        if contexts:                                                      # keyed by the move played just before
+            return PT.select_weighted(x0, move_context_weights(TC.combine(entries, t), values, record_turns(part) & 1,
+                                                               L.record_last_move(part)), ok)
         return PT.select_weighted(x0, move_value_weights(TC.combine(entries, t), values, record_turns(part) & 1,
                                                          None if value_slots is None else value_slots[live]), ok)
 
@@ -387,7 +395,7 @@ def _random_host(pos, key, ctr, max_plies, komi, history, table=None, tactics=No
     if tactics is not None or move_values is not None:
         from . import tactics as TC
     if move_values is not None:
-        values = move_values.values.copy()
+        values, contexts = move_values.values.copy(), isinstance(move_values, MoveContextTable)
         value_slots = np.asarray(slots) if isinstance(move_values, MoveValueTables) else None   # the table of every row
         choose = choose_valued
     elif tactics is not None:
@@ -457,7 +465,9 @@ def random_playouts(pos, seed, counters=None, max_plies=MAX_PLIES, rules="device
     then updated in place with all G games, after the reply table if any (bkt_move_value_update).  Not with slots=
     (TypeError): a MoveValueTable is one table for all games.  A movevalues.MoveValueTables (a table per game)
     needs slots= (TypeError without), alone or with a ReplyTables or a ReplyTables2 of the same count (ValueError), whose
-    tables the same slots name; a single ReplyTable or ReplyTable2 is refused with it (TypeError)."""
+    tables the same slots name; a single ReplyTable or ReplyTable2 is refused with it (TypeError).  A
+    movecontexts.MoveContextTable (NAST) is a MoveValueTable keyed by the previous move as well: the same
+    composition and the same refusal of slots=, on bkt_move_context_playouts and bkt_move_context_update."""
     L.check_rules(rules)
     table, tactics = _table(patterns), _tactics(tactics)
     slots = _check_tables(replies, move_values, slots, len(pos))
@@ -479,7 +489,7 @@ def random_playouts(pos, seed, counters=None, max_plies=MAX_PLIES, rules="device
             if replies is not None:
                 _update_host(replies, start, moves, won, G, 1, slots)
             if move_values is not None:
-                move_value_update_host(move_values, start, moves, won, G, 1, _value_slots(move_values, slots))
+                _update_move_values_host(move_values, start, moves, won, G, 1, slots)
             fin.moves = moves if history else None
         return fin
     dev = _device(device, None, pos)
@@ -518,10 +528,22 @@ def _update_device(recs, moves, won, records, playouts, replies, slots):
     return T.reply_update(recs, moves, won, records, playouts, replies.device(recs.device), slots=slots)
 
 
+def _update_move_values_host(move_values, recs, moves, won, records, playouts, slots=None):
+    """The update of the table's kind on the host: move_context_update_host for a MoveContextTable (no slots), else
+    move_value_update_host."""
+    if isinstance(move_values, MoveContextTable):
+        return move_context_update_host(move_values, recs, moves, won, records, playouts)
+    return move_value_update_host(move_values, recs, moves, won, records, playouts, _value_slots(move_values, slots))
+
+
 def _update_move_values_device(recs, moves, won, records, playouts, move_values, slots=None):
     """bkt_move_value_update on the current stream: the table's tensors on the device of recs are the table from here on.
-    With a MoveValueTables, bkt_move_value_update_tables with slots int32 [records] on the device."""
+    With a MoveValueTables, bkt_move_value_update_tables with slots int32 [records] on the device; with a MoveContextTable,
+    bkt_move_context_update."""
     counts, values, lut = move_values.device(recs.device)
+    if isinstance(move_values, MoveContextTable):
+        return T.move_context_update(recs, moves, won, records, playouts, counts, values, lut, move_values.k, move_values.limit,
+                                     move_values.min_plays)
     return T.move_value_update(recs, moves, won, records, playouts, counts, values, lut, move_values.k, move_values.limit,
                                slots=_value_slots(move_values, slots))
 
@@ -592,12 +614,16 @@ def _play_random_device(pos, key, ctr, max_plies, history, table=None, tactics=N
     tactics: None or a TacticTable; replies: None or a ReplyTable, which every launch reads as it stands, or a ReplyTables or
     a ReplyTables2 with slots int32 [G] on the device, the table of every row; move_values: None or a MoveValueTable, whose
     values every launch reads as they stand (bkt_move_value_playouts, with a ReplyTable or a ReplyTable2 put in; no slots),
-    or a MoveValueTables with the same slots (bkt_move_value_playouts_tables, with a ReplyTables or a ReplyTables2 put in).
+    or a MoveValueTables with the same slots (bkt_move_value_playouts_tables, with a ReplyTables or a ReplyTables2 put in),
+    or a MoveContextTable (bkt_move_context_playouts, with a ReplyTable or a ReplyTable2 put in; no slots).
     -> (over uint8 [G], plies int32 [G], moves int16 [G,max_plies] or None, status int32 [G]), T.MAX_BATCH rows per launch."""
     w, tac = (None if t is None else t.device(pos.device) for t in (table, tactics))
     if move_values is not None:
         put = {} if replies is None else {"replies2" if isinstance(replies, _PAIRS) else "replies": replies.device(pos.device)}
         values = move_values.device(pos.device)[1]
+        if isinstance(move_values, MoveContextTable):                     # the table's class picks the kernel (DESIGN 32)
+            return _per_batch(lambda p, c: T.move_context_playouts(p, key, c, w, tac, values, max_plies, history=history, **put),
+                              pos, ctr)
         return _per_batch(lambda p, c, s: T.move_value_playouts(p, key, c, w, tac, values, max_plies, history=history, slots=s,
                                                                 **put), pos, ctr, _value_slots(move_values, slots))
     if replies is not None:
@@ -668,7 +694,9 @@ def _playouts(recs, n, key, rules, komi=L.KOMI, table=None, tactics=None, max_pl
                                     them into it, in place and on the same stream.  It needs score=True, and refuses slots.
                                     A MoveValueTables needs slots, the table of every record -- the same that
                                     name a ReplyTables' or a ReplyTables2's -- and the launches are
-                                    bkt_move_value_playouts_tables and bkt_move_value_update_tables."""
+                                    bkt_move_value_playouts_tables and bkt_move_value_update_tables.  A MoveContextTable
+                                     goes as a MoveValueTable does, on bkt_move_context_playouts and
+                                    bkt_move_context_update."""
     R, host = len(recs), rules == "host"
     counted, owned = (R if x is True else int(x) for x in (counted, owned))
     slots = _check_tables(replies, move_values, slots, R)
@@ -701,7 +729,7 @@ def _playouts(recs, n, key, rules, komi=L.KOMI, table=None, tactics=None, max_pl
             _update_device(recs, moves, run.won.reshape(-1).to(torch.uint8), R, n, replies, slots)
     if move_values is not None:                                            # ... then the move values, on the same stream
         if host:
-            move_value_update_host(move_values, recs, moves, run.won.reshape(-1), R, n, _value_slots(move_values, slots))
+            _update_move_values_host(move_values, recs, moves, run.won.reshape(-1), R, n, slots)
         else:
             _update_move_values_device(recs, moves, run.won.reshape(-1).to(torch.uint8), R, n, move_values, slots)
     if counted:
@@ -1067,6 +1095,12 @@ class PlayoutEvaluator:
     with replies=True, games=G or with pair_games=G -- the same G (ValueError), the same games= naming both tables of a row
     -- and not with move_values=, nor with replies=True or replies=2 without tables per game (TypeError).  A one-game pool
     is then move_values=tau bit for bit.
+    move_contexts=True or a temperature tau > 0 (default False: exactly the above): `.move_values` is a
+    movecontexts.MoveContextTable, created empty (tau; True: DEFAULT_TAU; k, limit and min_plays the modules' defaults),
+    which reset_move_values() clears: the playouts of every request draw with its values (bkt_move_context_playouts,
+    composed with replies=True or replies=2) and are folded into it (bkt_move_context_update) where move_values= has its
+    two calls.  Not with move_values= (the table contains that one as its plane 81), games=, pair_games= or
+    move_value_games= (TypeError): a context table per game is not built.
     The engine is kept as `policy_engine`, not `engine`: selfplay.run_pools_native hands an evaluator's `engine` to the C
     step loop as its own bk_evaluator, which would compute no playouts -- this class goes through callback_evaluator."""
     wants_positions = True
@@ -1075,13 +1109,18 @@ class PlayoutEvaluator:
     def __init__(self, engine, playouts=64, seed=0, rules="device", komi=L.KOMI, patterns=None, tactics=None, prior=0.0,
                  prior_k=PRIOR_K, prior_temperature=PRIOR_TEMPERATURE, rave=False, criticality=0.0, pattern_prior=0.0,
                  prior_patterns=None, prior_tactics=None, move_values=False, move_value_games=None, move_value_tau=DEFAULT_TAU,
-                 replies=False, games=None, pair_games=None):
+                 move_contexts=False, replies=False, games=None, pair_games=None):
         L.check_rules(rules)
+        if move_contexts and (move_values or games is not None or pair_games is not None or move_value_games is not None):
+            raise TypeError("move_contexts= keeps one move-context table for all rows, whose plane 81 is the move-value table: "
+                            "it goes without move_values=, games=, pair_games= and move_value_games=")
         if move_values and (games is not None or pair_games is not None):
             raise TypeError("move_values= keeps one table for all rows: it goes without games= and pair_games= (a table per game)")
         # True: the default temperature; a number: tau; False, None or 0: no table
         self.move_values = (MoveValueTable.empty() if move_values is True else MoveValueTable.empty(tau=move_values)) \
             if move_values else None
+        if move_contexts:
+            self.move_values = MoveContextTable.empty() if move_contexts is True else MoveContextTable.empty(tau=move_contexts)
         if move_value_games is not None:
             if move_values:
                 raise TypeError("move_value_games= is the number of move-value tables, a MoveValueTables: it goes without "
@@ -1172,7 +1211,7 @@ class PlayoutEvaluator:
         """An empty move-value table again (move_values=True or tau; every table with move_value_games=G): what a new game
         starts with."""
         if self.move_values is None:
-            raise TypeError("this evaluator keeps no move-value table: move_values=True or move_value_games=G")
+            raise TypeError("this evaluator keeps no move-value table: move_values=True, move_contexts=True or move_value_games=G")
         self.move_values.clear()
 
     def finish(self, handle, normalise=None):
@@ -1334,8 +1373,11 @@ def _parse(argv):
                     help="with --random: play the playouts in chunks that learn a move-value table from each other (MAST), and "
                          "print the share of its entries that were played, its smallest and largest value and its ten "
                          "heaviest points instead of the score")
+    ap.add_argument("--move-contexts", action="store_true",
+                    help="with --random: as --move-values with a table keyed by the previous move as well (NAST): print also "
+                         "the share of its context entries that have their minimum of plays")
     ap.add_argument("--chunk", type=int, default=16, metavar="C",
-                    help="with --replies, --reply-pairs or --move-values: playouts per chunk")
+                    help="with --replies, --reply-pairs, --move-values or --move-contexts: playouts per chunk")
     ap.add_argument("--sides", type=int, default=1, choices=(1, 2),
                     help="with --amaf: 2 also prints the opponent's heaviest points (the two-sided counts RAVE is fed with)")
     ap.add_argument("-n", dest="n", type=int, default=256, help="playouts")
@@ -1357,6 +1399,10 @@ def _parse(argv):
     if args.move_values and (not args.random or args.amaf or args.ownership or args.weights or args.replies or args.reply_pairs):
         ap.error("--move-values reads the one-launch playouts: it needs --random, and not --amaf, --ownership, --weights, "
                  "--replies or --reply-pairs")
+    if args.move_contexts and (not args.random or args.amaf or args.ownership or args.weights or args.replies
+                               or args.reply_pairs or args.move_values):
+        ap.error("--move-contexts reads the one-launch playouts: it needs --random, and not --amaf, --ownership, --weights, "
+                 "--replies, --reply-pairs or --move-values (contexts contain the plain values)")
     if args.chunk < 1:
         ap.error("--chunk must be at least 1")
     if args.sides != 1 and not args.amaf:
@@ -1444,6 +1490,33 @@ def move_values_report(recs, n, seed, chunk, rules="device", komi=L.KOMI, **kw):
             "black_win": black / n}
 
 
+def move_contexts_report(recs, n, seed, chunk, rules="device", komi=L.KOMI, **kw):
+    """move_values_report with a MoveContextTable of the default parameters -> a dict: the plies played, the
+    share of plane 81's 162 entries with a play, the share of the 13,122 context entries with a play and with at least
+    min_plays of them, the smallest and largest value of the whole table, its ten heaviest context entries and black's share
+    of the wins."""
+    table, plies, black = MoveContextTable.empty(), 0, 0
+    ctr = default_counters(n, np.repeat(record_turns(recs), n))
+    for s in range(0, n, chunk):
+        c = min(chunk, n - s)
+        fin = random_playouts(np.repeat(recs, c, 0), seed, counters=ctr[s:s + c], rules=rules, komi=komi, move_values=table, **kw)
+        plies += int(fin.plies.sum())
+        black += int((fin.score > 0).sum())
+    values, counts = table.values, table.counts
+    ctx = values[:, :81].astype(np.int64).reshape(-1)
+    contexts = 2 * 81 * 81
+    return {"playouts": n, "chunk": chunk, "plies": plies, "min_plays": table.min_plays,
+            "played_share": int((counts[:, 81, :, 0] > 0).sum()) / 162,
+            "context_played_share": int((counts[:, :81, :, 0] > 0).sum()) / contexts,
+            "context_qualified_share": table.qualified() / contexts,
+            "min_value": int(values.min()), "max_value": int(values.max()),
+            "heaviest": [{"colour": "bw"[e // 6561], "after": go.unsquash(e // 81 % 81), "move": go.unsquash(e % 81),
+                          "value": int(ctx[e]), "played": int(counts[e // 6561, e // 81 % 81, e % 81, 0]),
+                          "won": int(counts[e // 6561, e // 81 % 81, e % 81, 1])}
+                         for e in np.argsort(-ctx, kind="stable")[:10].tolist()],
+            "black_win": black / n}
+
+
 def main(argv=None):
     args = _parse(argv)
     game = sgf_position(args.sgf, args.move)
@@ -1483,6 +1556,11 @@ def main(argv=None):
         print(json.dumps(move_values_report(_as_records(game), args.n, args.seed, args.chunk, komi=args.komi,
                                             patterns=args.patterns, tactics=args.tactics,
                                             device=torch.device("cuda", args.device))))
+        return
+    if args.move_contexts:
+        print(json.dumps(move_contexts_report(_as_records(game), args.n, args.seed, args.chunk, komi=args.komi,
+                                              patterns=args.patterns, tactics=args.tactics,
+                                              device=torch.device("cuda", args.device))))
         return
     if args.ownership:
         o = playout_ownership(_as_records(game), args.n, args.seed, komi=args.komi, device=torch.device("cuda", args.device),

@@ -644,6 +644,58 @@ int bkt_move_value_update_tables(const void *pos, const int16_t *moves, int max_
                                  int playouts, int64_t *counts, uint16_t *values, const uint16_t *lut, int k, int limit,
                                  int tables, const int32_t *slots, void *scratch, void *stream);
 
+/* NAST playouts: move values keyed by the previous move (the N-gram average sampling technique, Powley, Whitehouse & Cowling
+ * 2013; the N-gram selection of Tak, Winands & Bjornsson 2012; bokego_amd/movecontexts.py MoveContextTable).  A
+ * move-context table is the move-value table above with a plane per previous move, all integers:
+ *   counts  int64 [2][82][81][2] on the device, 8-byte aligned: counts[c][p][m] = {played, won} of colour c on point m played
+ *           directly after move p (by either side); p == 81: after anything -- the move-value table above, as plane 81 of a
+ *           pair reply table is the single one; 0 <= won <= played;
+ *   values  uint16 [2][82][81]: the factor of the draw's weight in units of 1/256, every entry >= 1, 256 = neutral;
+ *   lut     uint16 [65], k, limit: exactly the move-value table's;
+ *   min_plays, 1 <= min_plays <= BKT_MOVE_CONTEXT_MAX_MIN_PLAYS: the plays a context entry needs before it counts.
+ * The previous move.  In a playout it is the move played immediately before the ply, by either side, a pass included; at
+ * ply 0 the record's last move.  In the update, p of ply t is moves[row, t - 1], and the record's last move for t == 0.
+ * Anything outside 0..80 (a pass, none, junk) is p = 81; the value is compared before it indexes.
+ *
+ * Use.  bkt_move_context_playouts is bkt_move_value_playouts' contract in every respect -- the arguments, the NULL rules of
+ * table and tactics, the rules of replies and replies2, every refused call -- except that values is the [2][82][81] table and
+ *   w = min(2^24 - 1, max(1, ((uint64_t)w_in * values[c][p][q]) >> 8)).
+ * One launch; nothing is staged: a thread reads exactly one uint16 of values per ply from global memory, and all fallback
+ * logic lives in the update.  With values all 256 the games are those of bkt_tactical_playouts, bkt_random_playouts,
+ * bkt_reply_playouts and bkt_reply2_playouts byte for byte; with every plane of a colour equal to its plane 81 they are
+ * bkt_move_value_playouts' on that plane.
+ *
+ * Update.  bkt_move_context_update takes rows, won, the colour rule and the end-of-row rule exactly as bkt_move_value_update
+ * does.  For every ply with a board point m:
+ *   counts[c][81][m] += (1, mover won) always;   counts[c][p][m] += (1, mover won) when p < 81.
+ * After all rows are added, every one of the 13,284 entries on its own is shifted right until played < limit (limit > 0);
+ *   i1[c][m] = floor(64 * (2 * won + k) / (2 * (played + k))) of plane 81, and values[c][81][m] = lut[i1];
+ *   for p < 81: values[c][p][m] = lut[(i1 + i2) >> 1] if the entry's played >= min_plays (after the shift), i2 the same
+ *   index of the entry's own counts; else values[c][81][m].
+ * Every entry of values is written.  Plane 81 of counts and values is byte for byte what bkt_move_value_update leaves on the
+ * same inputs, and with min_plays >= limit > 0 no context ever qualifies.  Three launches on `stream`, nothing waits on the
+ * host: the first zeroes scratch; the second, a wave per row, adds every play into scratch -- plane 81 summed per workgroup
+ * in LDS first -- by 64-bit integer atomic adds; the third, a workgroup per (colour, point), adds the sums into counts and
+ * applies the shift, the two indices and the lut, one writer per entry.  Integers only, and an integer sum does not depend on
+ * the order of its terms: the result is the definition's for every input, whatever the scheduling.
+ * No wrap.  A workgroup of the second launch sees at most 16 * 1024 = 2^14 plays: its LDS partial counts are uint32.  A call
+ * adds at most records * playouts * max_plies <= 2^24 * 2^10 = 2^34 to an entry: the sums in scratch are uint64.  With limit >
+ * 0 an entry is below limit <= 2^30 after every call, so it never exceeds 2^30 + 2^34.  With limit == 0 the counts only grow,
+ * and the caller keeps played below 2^54: 64 * (2 * won + k) then stays below 2^62.
+ * scratch: bkt_move_context_scratch_bytes(records) = 13,284 * 16 = 212,544 bytes on the device whatever the number of records,
+ * 8-byte aligned (0 when records < 1); its contents on entry do not matter, and two updates back to back on one stream may
+ * share it.
+ * Domain: bkt_move_value_update's, scratch 8-byte aligned, and 1 <= min_plays <= BKT_MOVE_CONTEXT_MAX_MIN_PLAYS.  Else
+ * BKT_ERR_ARG: a refused call launches nothing and writes nothing. */
+#define BKT_MOVE_CONTEXT_MAX_MIN_PLAYS (1 << 30)
+int bkt_move_context_playouts(void *pos, int batch, uint64_t seed, const uint32_t *counters, const uint16_t *table,
+                              const uint16_t *tactics, const uint16_t *values, const uint8_t *replies, const uint8_t *replies2,
+                              int max_plies, uint8_t *over, int32_t *plies, int16_t *moves, int32_t *status, void *stream);
+size_t bkt_move_context_scratch_bytes(int records);
+int bkt_move_context_update(const void *pos, const int16_t *moves, int max_plies, const uint8_t *won, int records, int playouts,
+                            int64_t *counts, uint16_t *values, const uint16_t *lut, int k, int limit, int min_plays,
+                            void *scratch, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
